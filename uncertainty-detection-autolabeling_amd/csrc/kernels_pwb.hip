@@ -60,6 +60,10 @@ __global__ __launch_bounds__(256, OCC) void pwb_kernel(PwArgs a) {
   const int m0 = bx * BM, n0 = by * BN;
   const int nt0 = by * NTB;
   const float* A = a.in + (size_t)b_in * a.HW * a.Cin;
+  // one fp16 piece: the input may be an fp16 expanded tensor (2 bytes per element); its four halves travel in .x / .y of the
+  // staging float4 and are widened where the chunk is split, so the gate is applied in float32 and the product rounded once
+  const bool in_h = PARTS == UDA_SPLIT_F16X1 && a.in_f16;
+  const unsigned short* Ah = (const unsigned short*)a.in + (size_t)b_in * a.HW * a.Cin;
   const float* se = a.se ? a.se + (size_t)(b / a.se_div) * a.Cin : nullptr;
   const uint4* Wp = (const uint4*)a.wsplit;
   const int KS = (a.Cin + 15) >> 4;        // MFMA k-steps in the packed weights
@@ -94,6 +98,10 @@ __global__ __launch_bounds__(256, OCC) void pwb_kernel(PwArgs a) {
         // read the last row: row m of A only reaches row m of the result, which is never stored.
         const int mr = m0 + m < a.HW ? m0 + m : a.HW - 1;
         ra[i] = *(const float4*)(A + (size_t)mr * a.Cin + k);
+      } else if (in_h) {
+        uint2 h = make_uint2(0u, 0u);
+        if (m0 + m < a.HW && k < a.Cin) h = *(const uint2*)(Ah + (size_t)(m0 + m) * a.Cin + k);
+        ra[i] = make_float4(__uint_as_float(h.x), __uint_as_float(h.y), 0.f, 0.f);
       } else {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (m0 + m < a.HW && k < a.Cin) v = *(const float4*)(A + (size_t)(m0 + m) * a.Cin + k);
@@ -128,7 +136,8 @@ __global__ __launch_bounds__(256, OCC) void pwb_kernel(PwArgs a) {
     for (int i = 0; i < A_ITERS; ++i) {
       const int f = tid + 256 * i;
       const int m = f >> 3, kq = f & 7;
-      float r0 = ra[i].x * rg.x, r1 = ra[i].y * rg.y, r2 = ra[i].z * rg.z, r3 = ra[i].w * rg.w;
+      const float4 av = (!DEEP && in_h) ? f16x4_to_float4(__float_as_uint(ra[i].x), __float_as_uint(ra[i].y)) : ra[i];
+      float r0 = av.x * rg.x, r1 = av.y * rg.y, r2 = av.z * rg.z, r3 = av.w * rg.w;
       split_track<PARTS>(amax, r0, r1);
       split_track<PARTS>(amax, r2, r3);
 #pragma unroll
@@ -422,7 +431,7 @@ __global__ __launch_bounds__(256, 3) void pwb_shared_kernel(PwArgs a) {
 #define UDA_PWS_D 4
 #endif
 constexpr int PWS_D = UDA_PWS_D;
-template <int PARTS, int NT, bool GATE>
+template <int PARTS, int NT, bool GATE, bool IH = false>    // IH: fp16 input (one fp16 piece, a.in_f16)
 __global__ __launch_bounds__(64) void pws_kernel(PwArgs a) {
   constexpr int NPC = split_np(PARTS);
   const int lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
@@ -432,6 +441,8 @@ __global__ __launch_bounds__(64) void pws_kernel(PwArgs a) {
   const int NTL = (a.Cout + 31) >> 5;
   const int mr = m0 + li < a.HW ? m0 + li : a.HW - 1;       // (rows past the map: row m of A only reaches row m of the result, never stored)
   const float* arow = a.in + ((size_t)b_in * a.HW + mr) * a.Cin + 8 * lh;
+  constexpr bool in_h = IH;        // fp16 input: 8 halves per step in the bits of a0 (see pwb_kernel)
+  const unsigned short* arow_h = (const unsigned short*)a.in + ((size_t)b_in * a.HW + mr) * a.Cin + 8 * lh;
   const float* se = GATE ? a.se + (size_t)(b / a.se_div) * a.Cin + 8 * lh : nullptr;
   const uint4* Wp = (const uint4*)a.wsplit + lane;
   size_t woff[NT];                           // (a column tile past the end repeats the last one; not stored)
@@ -450,8 +461,14 @@ __global__ __launch_bounds__(64) void pws_kernel(PwArgs a) {
   struct Group { Step s[PWS_D]; };
   // plain, unconditional loads (a load under a condition gets a basic block of its own and a vmcnt(0) at its first use)
   auto load_step = [&](int ks, Step& t) {
-    t.a0 = *(const float4*)(arow + 16 * ks);
-    t.a1 = *(const float4*)(arow + 16 * ks + 4);
+    if constexpr (in_h) {
+      const uint4 h = *(const uint4*)(arow_h + 16 * ks);
+      t.a0 = make_float4(__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z), __uint_as_float(h.w));
+      t.a1 = t.a0;
+    } else {
+      t.a0 = *(const float4*)(arow + 16 * ks);
+      t.a1 = *(const float4*)(arow + 16 * ks + 4);
+    }
     if constexpr (GATE) {
       t.g0 = *(const float4*)(se + 16 * ks);
       t.g1 = *(const float4*)(se + 16 * ks + 4);
@@ -463,6 +480,10 @@ __global__ __launch_bounds__(64) void pws_kernel(PwArgs a) {
   };
   auto mma_step = [&](const Step& t) {
     float4 v0 = t.a0, v1 = t.a1;
+    if constexpr (in_h) {
+      v0 = f16x4_to_float4(__float_as_uint(t.a0.x), __float_as_uint(t.a0.y));
+      v1 = f16x4_to_float4(__float_as_uint(t.a0.z), __float_as_uint(t.a0.w));
+    }
     if constexpr (GATE) {
       v0.x *= t.g0.x; v0.y *= t.g0.y; v0.z *= t.g0.z; v0.w *= t.g0.w;
       v1.x *= t.g1.x; v1.y *= t.g1.y; v1.z *= t.g1.z; v1.w *= t.g1.w;
@@ -547,6 +568,8 @@ static int launch_pws(const PwArgs& a, int rows, hipStream_t s) {
   const dim3 grid(row_tiles, (NTL + nt - 1) / nt, rows), block(64);
   auto go = [&](auto k1, auto k2) { if (nt == 1) hipLaunchKernelGGL(k1, grid, block, 0, s, a); else hipLaunchKernelGGL(k2, grid, block, 0, s, a); };
   if (a.wparts == UDA_SPLIT_F16X2) { if (a.se) go(pws_kernel<4, 1, true>, pws_kernel<4, 2, true>); else go(pws_kernel<4, 1, false>, pws_kernel<4, 2, false>); }
+  else if (a.wparts == UDA_SPLIT_F16X1 && a.in_f16) { if (a.se) go(pws_kernel<5, 1, true, true>, pws_kernel<5, 2, true, true>); else go(pws_kernel<5, 1, false, true>, pws_kernel<5, 2, false, true>); }
+  else if (a.wparts == UDA_SPLIT_F16X1) { if (a.se) go(pws_kernel<5, 1, true>, pws_kernel<5, 2, true>); else go(pws_kernel<5, 1, false>, pws_kernel<5, 2, false>); }
   else if (a.wparts == UDA_SPLIT_BF16X3) { if (a.se) go(pws_kernel<3, 1, true>, pws_kernel<3, 2, true>); else go(pws_kernel<3, 1, false>, pws_kernel<3, 2, false>); }
   else if (a.wparts == UDA_SPLIT_BF16X2) { if (a.se) go(pws_kernel<2, 1, true>, pws_kernel<2, 2, true>); else go(pws_kernel<2, 1, false>, pws_kernel<2, 2, false>); }
   else return 0;
@@ -559,6 +582,11 @@ static void launch_pwb_cfg(const PwArgs& a, int rows, hipStream_t s) {
   const dim3 grid((a.HW + BM - 1) / BM, (a.Cout + BN - 1) / BN, rows), block(256);
   // three blocks per CU (<= 168 registers): measured 10-20 % faster than the unconstrained allocation (2 per CU)
   if (a.wparts == UDA_SPLIT_BF16X3) hipLaunchKernelGGL((pwb_kernel<MT, NT, WM, WN, 3, 2>), grid, block, 0, s, a);
+  else if (a.wparts == UDA_SPLIT_F16X1) {
+    // one piece: half the fragment registers of the two-piece kernel, so up to five accumulator tiles per wave (the 160-column
+    // tile included) fit three blocks per CU (<= 168 registers) without spilling; six (2 x 3, 192 columns) still spill there
+    hipLaunchKernelGGL((pwb_kernel<MT, NT, WM, WN, 5, (MT * NT > 5 ? 2 : 3)>), grid, block, 0, s, a);
+  }
   else if (a.wparts == UDA_SPLIT_F16X2) {
     // (K-heavy projections on the big tiles - two blocks per CU by registers anyway: two chunks in flight per block)
     static const bool deep_on = !(getenv("UDA_PWB_DEEP") && atoi(getenv("UDA_PWB_DEEP")) == 0);
@@ -709,7 +737,7 @@ __host__ __device__ constexpr MbxCfgB mbxb_cfg(int k, int s) {
 #define UDA_MBXB_MINW(K, S, KSF, PARTS) ((PARTS) == 3 ? (((KSF) <= 2 && (K) == 3) ? UDA_MBXB6_W : 2) : \
     ((KSF) <= 2 ? ((K) == 3 ? 4 : 3) : (((KSF) <= 3 && ((K) == 3 ? (S) == 2 : UDA_MBXB_WK_LDS)) ? 3 : 2)))
 #endif
-template <int K, int S, int KSF, bool FUSE0, int PARTS>   // KSF = 16-deep MFMA k-steps covering Cin + 1
+template <int K, int S, int KSF, bool FUSE0, int PARTS, bool OH = false>   // KSF = 16-deep MFMA k-steps covering Cin + 1; OH: fp16 output
 __global__ __launch_bounds__(256, UDA_MBXB_MINW(K, S, KSF, PARTS)) void mbxb_kernel(MbxArgs a) {
   constexpr int NW = 4;
   constexpr int NPC = split_np(PARTS);        // pieces per operand (PARTS names the scheme: UDA_SPLIT_*)
@@ -868,6 +896,8 @@ __global__ __launch_bounds__(256, UDA_MBXB_MINW(K, S, KSF, PARTS)) void mbxb_ker
   }
   float* const obase = a.out + (((size_t)b * a.Ho + oy0) * a.Wo + ox0) * a.Cmid;
   const unsigned cm = (unsigned)a.Cmid;
+  // OH (one fp16 piece, a.out_f16): the expanded tensor is stored as fp16 - the same element offsets in a 2-byte view
+  unsigned short* const hobase = (unsigned short*)a.out + (((size_t)b * a.Ho + oy0) * a.Wo + ox0) * a.Cmid;
   // a tile that lies inside the output takes the unguarded path (block-uniform decision; the channel guard of a last,
   // partial slab is one exec mask around the whole stage)
   const bool full = (oy0 + TH <= a.Ho) && (ox0 + TW <= a.Wo);
@@ -997,6 +1027,7 @@ __global__ __launch_bounds__(256, UDA_MBXB_MINW(K, S, KSF, PARTS)) void mbxb_ker
     const float sc1 = pcur[K * K * 32 + c] * mk0, sh1 = pcur[(K * K + 1) * 32 + c];
     float ssum = 0.f;
     float* const ob = obase + ch * 32;            // uniform
+    unsigned short* const hob = hobase + ch * 32;  // (OH)
     auto dw_units = [&](auto guard) {
       constexpr bool GUARD = decltype(guard)::value;
       constexpr int KYU = (UDA_MBXB_WK_LDS && K == 5 && KSF == 3) ? 1 : K;      // (an unrolled tap-row loop hoists the tap reads back into registers)
@@ -1036,7 +1067,8 @@ __global__ __launch_bounds__(256, UDA_MBXB_MINW(K, S, KSF, PARTS)) void mbxb_ker
           if constexpr (GUARD) ok = ox0 + (int)((g + NG * ui) % UPR) * XW + o < a.Wo;
           if (ok) {
             const float v = swish_folded(fmaf(acc[o], sc1, sh1), mk1);
-            store_uniform_base(ob + (size_t)o * cm, ooff[ui], v);
+            if constexpr (OH) store_uniform_base_h(hob + (size_t)o * cm, ooff[ui], v);
+            else store_uniform_base(ob + (size_t)o * cm, ooff[ui], v);
             ssum += v;
           }
         }
@@ -1097,6 +1129,7 @@ size_t mbxb_w0frag_elems(int gate_rows, int scheme) { return (size_t)gate_rows *
 void launch_w0gate(const float* gate, const float* w0t, int c0, int gate_rows, int scheme, uint4* out, unsigned* oor, hipStream_t s) {
   if (scheme == UDA_SPLIT_BF16X3) hipLaunchKernelGGL(w0gate_kernel<3>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
   else if (scheme == UDA_SPLIT_F16X2) hipLaunchKernelGGL(w0gate_kernel<4>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
+  else if (scheme == UDA_SPLIT_F16X1) hipLaunchKernelGGL(w0gate_kernel<5>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
   else hipLaunchKernelGGL(w0gate_kernel<2>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
 }
 
@@ -1129,6 +1162,15 @@ static void launch_mbxb_t(const MbxArgs& a, int rows, hipStream_t s) {
       grid = dim3((unsigned)total, 1, 1);
     }
   }
+  if constexpr (PARTS == UDA_SPLIT_F16X1) {
+    if (a.out_f16) {
+      if constexpr (KSF == 2) {
+        if (a.gate) { hipLaunchKernelGGL((mbxb_kernel<K, S, KSF, true, PARTS, true>), grid, dim3(256), lds, s, b); return; }
+      }
+      hipLaunchKernelGGL((mbxb_kernel<K, S, KSF, false, PARTS, true>), grid, dim3(256), lds, s, b);
+      return;
+    }
+  }
   if constexpr (KSF == 2) {
     if (a.gate) { hipLaunchKernelGGL((mbxb_kernel<K, S, KSF, true, PARTS>), grid, dim3(256), lds, s, b); return; }
   }
@@ -1156,6 +1198,7 @@ static void launch_mbxb_p(const MbxArgs& a, int rows, int k, int stride, hipStre
 void launch_mbxb(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
   if (a.wparts == UDA_SPLIT_BF16X3) launch_mbxb_p<3>(a, rows, k, stride, s);
   else if (a.wparts == UDA_SPLIT_F16X2) launch_mbxb_p<4>(a, rows, k, stride, s);
+  else if (a.wparts == UDA_SPLIT_F16X1) launch_mbxb_p<5>(a, rows, k, stride, s);
   else launch_mbxb_p<2>(a, rows, k, stride, s);
 }
 
@@ -1190,9 +1233,13 @@ bool mbxd_wide(int Ho, int Wo, int k, int stride) {
   return on && stride == 1 && mbxd_slots(Ho, Wo, k, true) < mbxd_slots(Ho, Wo, k, false);
 }
 
-template <int K, int KSF, int PARTS, int S, bool WIDE>
-__global__ __launch_bounds__(512, (KSF <= 8 && PARTS != 3) ? 4 : 2) void mbxd_kernel(MbxArgs a) {
-  constexpr bool WK_LDS = (K == 5 && (KSF <= 8 || PARTS == 3));     // the 25 taps from LDS at their use, not 25 registers
+// One fp16 piece (PARTS = UDA_SPLIT_F16X1): the operand fragments of 13-14 k-steps are 56 registers instead of 112, so the deep
+// variants fit two blocks per CU as well (the two-piece ones run mbxp_kernel, one block per CU, instead).
+// (stride 1: the stride-2 3x3 variants at 13-14 k-steps spill at 128 registers)
+__host__ __device__ constexpr bool mbxd_two_per_cu(int ksf, int parts, int s) { return (ksf <= 8 && parts != 3) || (parts == UDA_SPLIT_F16X1 && s == 1); }
+template <int K, int KSF, int PARTS, int S, bool WIDE, bool OH = false>    // OH: fp16 output (one fp16 piece, a.out_f16)
+__global__ __launch_bounds__(512, mbxd_two_per_cu(KSF, PARTS, S) ? 4 : 2) void mbxd_kernel(MbxArgs a) {
+  constexpr bool WK_LDS = (K == 5 && (KSF <= 8 || PARTS == 3 || PARTS == UDA_SPLIT_F16X1));     // the 25 taps from LDS at their use, not 25 registers
 
   constexpr int NW = 8;
   constexpr int NPC = split_np(PARTS);        // pieces per operand (PARTS names the scheme: UDA_SPLIT_*)
@@ -1292,6 +1339,8 @@ __global__ __launch_bounds__(512, (KSF <= 8 && PARTS != 3) ? 4 : 2) void mbxd_ke
   }
   float* const obase = a.out + (((size_t)b * a.Ho + oy0) * a.Wo + ox0) * a.Cmid;
   const unsigned cm = (unsigned)a.Cmid;
+  // OH (one fp16 piece, a.out_f16): the expanded tensor is stored as fp16 - the same element offsets in a 2-byte view
+  unsigned short* const hobase = (unsigned short*)a.out + (((size_t)b * a.Ho + oy0) * a.Wo + ox0) * a.Cmid;
   const bool full = (oy0 + TH <= a.Ho) && (ox0 + TW <= a.Wo);
 
   for (int ch = chb; ch < che; ++ch) {
@@ -1365,6 +1414,7 @@ __global__ __launch_bounds__(512, (KSF <= 8 && PARTS != 3) ? 4 : 2) void mbxd_ke
     const float sc1 = pcur[K * K * 32 + c] * mk0c, sh1 = pcur[(K * K + 1) * 32 + c];
     float ssum = 0.f;
     float* const ob = obase + ch * 32;            // uniform
+    unsigned short* const hob = hobase + ch * 32;  // (OH)
     auto dw_units = [&](auto guard) {
       constexpr bool GUARD = decltype(guard)::value;
 #pragma unroll
@@ -1405,7 +1455,8 @@ __global__ __launch_bounds__(512, (KSF <= 8 && PARTS != 3) ? 4 : 2) void mbxd_ke
           if constexpr (GUARD) ok = ox0 + (int)((g + NG * ui) % UPR) * XW + o < a.Wo;
           if (ok) {
             const float v = swish_folded(fmaf(acc[o], sc1, sh1), mk1);
-            store_uniform_base(ob + (size_t)o * cm, ooff[ui], v);
+            if constexpr (OH) store_uniform_base_h(hob + (size_t)o * cm, ooff[ui], v);
+            else store_uniform_base(ob + (size_t)o * cm, ooff[ui], v);
             ssum += v;
           }
         }
@@ -1901,12 +1952,17 @@ static void launch_mbxd_tw(const MbxArgs& a, int rows, hipStream_t s) {
   static size_t attr_lds = 64 * 1024;      // above the default limit the kernel needs an explicit opt-in
   if (lds > attr_lds) {
     hipFuncSetAttribute((const void*)mbxd_kernel<K, KSF, PARTS, S, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if constexpr (PARTS == UDA_SPLIT_F16X1)
+      hipFuncSetAttribute((const void*)mbxd_kernel<K, KSF, PARTS, S, WIDE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_lds = lds;
   }
   dim3 grid((a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH, rows);
   MbxArgs b = a;
-  b.ch_groups = mbx_ch_groups((long long)grid.x * grid.y * rows, (KSF <= 8 && PARTS != 3) ? 2 : 1, (a.Cmid + 31) / 32);
+  b.ch_groups = mbx_ch_groups((long long)grid.x * grid.y * rows, mbxd_two_per_cu(KSF, PARTS, S) ? 2 : 1, (a.Cmid + 31) / 32);
   grid.z = (unsigned)(rows * b.ch_groups);
+  if constexpr (PARTS == UDA_SPLIT_F16X1) {
+    if (a.out_f16) { hipLaunchKernelGGL((mbxd_kernel<K, KSF, PARTS, S, WIDE, true>), grid, dim3(512), lds, s, b); return; }
+  }
   hipLaunchKernelGGL((mbxd_kernel<K, KSF, PARTS, S, WIDE>), grid, dim3(512), lds, s, b);
 }
 
@@ -1942,6 +1998,7 @@ void launch_mbxd(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
   if (stride == 2) {                // the first block of a stage: the two-phase kernel on the stride-2 tiles
     if (a.wparts == UDA_SPLIT_BF16X3) launch_mbxd_p<3, 2>(a, rows, k, ksf, s);
     else if (a.wparts == UDA_SPLIT_F16X2) launch_mbxd_p<4, 2>(a, rows, k, ksf, s);
+    else if (a.wparts == UDA_SPLIT_F16X1) launch_mbxd_p<5, 2>(a, rows, k, ksf, s);
     else launch_mbxd_p<2, 2>(a, rows, k, ksf, s);
     return;
   }
@@ -1949,6 +2006,10 @@ void launch_mbxd(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
   if (pipe < 0) { const char* e = getenv("UDA_MBXP"); pipe = e ? atoi(e) : 1; }
   if (a.wparts == UDA_SPLIT_BF16X3) {     // six cross terms: three pieces per operand, the two-phase kernel
     launch_mbxd_p<3, 1>(a, rows, k, ksf, s);
+    return;
+  }
+  if (a.wparts == UDA_SPLIT_F16X1) {      // one piece: the two-phase kernel at two blocks per CU (mbxp_kernel is laid out for two pieces)
+    launch_mbxd_p<5, 1>(a, rows, k, ksf, s);
     return;
   }
   if (pipe && ksf >= 13) {          // one block per CU anyway: the self-overlapping variant
@@ -2081,7 +2142,7 @@ float split_weight_scale(const float* w, size_t n) {
 // lane l holds B[16 s + 8 (l >> 5) + e][32 j + (l & 31)], e = 0..7
 void pwb_pack_weights(const float* w, int K, int N, int scheme, uint16_t* out, float scale) {
   const int KS = (K + 15) / 16, NTL = (N + 31) / 32, parts = uda_split_pieces(scheme);
-  const bool half = scheme == UDA_SPLIT_F16X2;
+  const bool half = uda_split_f16(scheme);
   for (int s = 0; s < KS; ++s)
     for (int j = 0; j < NTL; ++j)
       for (int l = 0; l < 64; ++l)

@@ -22,6 +22,17 @@ namespace uda {
 // fragment into its three pieces when it loads them - every wave owns its 32 pixel rows, so an element is still split once.
 constexpr int SEP_TH = 8, SEP_TW = 16;
 
+// Bytes in front of the weight image: the A image (NPC piece images, or the float32 one of three pieces).  In the deferred-input
+// mode the per-sample epilogue staging aliases that region and must end before the weight image; one fp16 piece (UDA_SPLIT_F16X1)
+// leaves an A image smaller than the staging at 64 channels, so there the region is widened to the staging (the other schemes'
+// layouts are unchanged: their A images hold it wherever the mode exists, sep_tin_supported).
+__host__ __device__ inline size_t sep_a_region(int KS, int Cout, int nt, int scheme, bool tin) {
+  const size_t a_img = scheme == UDA_SPLIT_BF16X3 ? (size_t)128 * (KS * 64 + 16) : (size_t)split_np(scheme) * 128 * (KS * 32 + 16);
+  if (!tin || scheme != UDA_SPLIT_F16X1) return a_img;
+  const size_t stg = (Cout & 3) ? (size_t)4 * 32 * nt * 32 * 4 : (size_t)4 * 32 * PWB_STG * 4;
+  return a_img < stg ? stg : a_img;
+}
+
 // TIN > 0 (round 5): the input is shared by the T = in_div samples of an image and carries a DEFERRED dropout site -
 // keep-scales mask_in[sample row][channel] that the producing op did not apply (plan.py: the first layer of a head under
 // head-only MC dropout).  A per-channel factor commutes with the depthwise conv, so the block computes the depthwise result
@@ -66,7 +77,7 @@ __global__ __launch_bounds__(256, OCC) void sep_kernel(SepMulti m) {
   // bytes per A image row: KS * 16 bf16 (float32) + 16 pad (conflict-free ds_read_b128: 36- / 68-dword pitch at C = 64)
   const int arow = F32A ? KS * 64 + 16 : KS * 32 + 16;
   unsigned char* As = slds;                // [NPC][BM][arow] pieces, or [BM][arow] float32
-  uint4* Bs = (uint4*)(slds + (size_t)(F32A ? 1 : NPC) * BM * arow);   // [KS][NT][NPC][64 lanes] x 16 B
+  uint4* Bs = (uint4*)(slds + sep_a_region(KS, a.Cout, NT, PARTS, TIN > 0));   // [KS][NT][NPC][64 lanes] x 16 B
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int b_in = TIN ? b : b / a.in_div;       // (TIN: the grid runs over images)
@@ -752,6 +763,7 @@ static void launch_sepf_nt(const SepArgs& a, const FuseArgs& f, int rows, hipStr
     constexpr int PC = decltype(pcv)::value;
     if (a.wparts == UDA_SPLIT_BF16X3) go(sepf_kernel<NT, 3, FIN, PC>);
     else if (a.wparts == UDA_SPLIT_F16X2) go(sepf_kernel<NT, 4, FIN, PC>);
+    else if (a.wparts == UDA_SPLIT_F16X1) go(sepf_kernel<NT, 5, FIN, PC>);
     else go(sepf_kernel<NT, 2, FIN, PC>);
   };
   if (pc == 16) by_scheme(std::integral_constant<int, 16>{});
@@ -781,7 +793,7 @@ bool sep_tin_supported(int C, int Cout, int scheme) {
   if (scheme == UDA_SPLIT_NONE || !sep_supported(C, Cout) || C < 64) return false;
   const int KS = (C + 15) / 16, ntl = (Cout + 31) / 32, npc = uda_split_pieces(scheme);
   if (ntl < 2 || ntl > 4) return false;
-  const size_t a_img = scheme == UDA_SPLIT_BF16X3 ? (size_t)128 * (KS * 64 + 16) : (size_t)npc * 128 * (KS * 32 + 16);
+  const size_t a_img = sep_a_region(KS, Cout, ntl, scheme, true);
   const size_t stg = (Cout & 3) ? (size_t)4 * 32 * ntl * 32 * 4 : (size_t)4 * 32 * PWB_STG * 4;
   if (stg > a_img) return false;
   return a_img + (size_t)KS * ntl * npc * 1024 <= 120 * 1024;      // (the launcher would split the columns over several blocks otherwise)
@@ -794,15 +806,15 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
   const SepArgs& a = m.one;
   const int KS = (a.C + 15) / 16;
   const int npc = uda_split_pieces(a.wparts);
-  const size_t a_img = a.wparts == UDA_SPLIT_BF16X3 ? (size_t)128 * (KS * 64 + 16) : (size_t)npc * 128 * (KS * 32 + 16);   // float32 image | pieces
+  // deferred-input mode: one block serves the in_div samples of an image - the grid runs over images
+  const int tin = a.mask_in ? (a.C <= 64 ? 1 : 2) : 0;
+  const size_t a_img = sep_a_region(KS, a.Cout, NT, a.wparts, tin > 0);   // float32 image | pieces
   size_t lds = a_img + (size_t)KS * NT * npc * 1024;
   const size_t stg = (a.Cout & 3) ? (size_t)4 * 32 * NT * 32 * 4 : (size_t)4 * 32 * PWB_STG * 4;     // epilogue staging (packed rows | float4 tiles)
   if (lds < stg) lds = stg;
   SepMulti mm = m;
   mm.tiles = m.n_lv > 0 ? m.tile0[m.n_lv] : sep_tiles(a.H, a.W);
   static const bool remap = !(getenv("UDA_SEP_REMAP") && atoi(getenv("UDA_SEP_REMAP")) == 0);     // (0: plain block order, A/B)
-  // deferred-input mode: one block serves the in_div samples of an image - the grid runs over images
-  const int tin = a.mask_in ? (a.C <= 64 ? 1 : 2) : 0;
   if (tin) rows /= a.in_div;
   mm.rows = remap ? rows : 0;
   const dim3 grid(mm.tiles * rows, gy);
@@ -823,10 +835,12 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
         // (two blocks per CU: the 32 registers of the kept depthwise result spill at the 168 of three)
         if (a.wparts == UDA_SPLIT_BF16X3) go(sep_kernel<NT, 3, 2, 1>);
         else if (a.wparts == UDA_SPLIT_F16X2) go(sep_kernel<NT, 4, 2, 1>);
+        else if (a.wparts == UDA_SPLIT_F16X1) go(sep_kernel<NT, 5, 2, 1>);
         else go(sep_kernel<NT, 2, 2, 1>);
       } else {
         if (a.wparts == UDA_SPLIT_BF16X3) go(sep_kernel<NT, 3, 2, 2>);
         else if (a.wparts == UDA_SPLIT_F16X2) go(sep_kernel<NT, 4, 2, 2>);
+        else if (a.wparts == UDA_SPLIT_F16X1) go(sep_kernel<NT, 5, 2, 2>);
         else go(sep_kernel<NT, 2, 2, 2>);
       }
     }
@@ -834,14 +848,15 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
   }
   if (a.wparts == UDA_SPLIT_BF16X3) { if (occ >= 3 && NT <= 2) go(sep_kernel<NT, 3, 3>); else go(sep_kernel<NT, 3, 2>); }
   else if (a.wparts == UDA_SPLIT_F16X2) { if (occ >= 3 && NT <= 2) go(sep_kernel<NT, 4, 3>); else go(sep_kernel<NT, 4, 2>); }
+  else if (a.wparts == UDA_SPLIT_F16X1) { if (occ >= 3 && NT <= 2) go(sep_kernel<NT, 5, 3>); else go(sep_kernel<NT, 5, 2>); }
   else if (occ >= 3 && NT <= 2) go(sep_kernel<NT, 2, 3>);
   else go(sep_kernel<NT, 2, 2>);
 }
 
 // Dynamic LDS of the launch launch_sep_any will make for a C -> Cout separable conv (see launch_sep_nt): checked by uda_create
-size_t sep_lds_bytes(int C, int Cout, int scheme) {
+size_t sep_lds_bytes(int C, int Cout, int scheme, bool tin) {
   const int KS = (C + 15) / 16, ntl = (Cout + 31) / 32, npc = uda_split_pieces(scheme);
-  const size_t a_img = scheme == UDA_SPLIT_BF16X3 ? (size_t)128 * (KS * 64 + 16) : (size_t)npc * 128 * (KS * 32 + 16);
+  const size_t a_img = sep_a_region(KS, Cout, ntl <= 4 ? ntl : 3, scheme, tin);
   int nt = ntl <= 4 ? ntl : 3;
   if (ntl > 2 && a_img + (size_t)KS * (ntl < 4 ? ntl : 3) * npc * 1024 > 120 * 1024) nt = 2;
   const size_t lds = a_img + (size_t)KS * nt * npc * 1024;

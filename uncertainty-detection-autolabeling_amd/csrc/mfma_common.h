@@ -43,6 +43,20 @@ __device__ __forceinline__ void store_uniform_base(float* base, unsigned byte_of
   asm volatile("global_store_dword %0, %1, %2" : : "v"(byte_off), "v"(v), "s"(g) : "memory");
 }
 
+// The fp16 counterpart of store_uniform_base (global_store_short v, v, s[..]) for a tensor stored as fp16 in a float32-sized
+// slot: base = the uniform fp16 view of the same element the float base names, byte_off = the float byte offset (halved here).
+typedef __attribute__((address_space(1))) unsigned short uda_gu16;
+__device__ __forceinline__ void store_uniform_base_h(unsigned short* base, unsigned byte_off, float v) {
+  uda_gchar* g = (uda_gchar*)(uda_gu16*)base;
+  const unsigned h = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)v);
+  asm volatile("global_store_short %0, %1, %2" : : "v"(byte_off >> 1), "v"(h), "s"(g) : "memory");
+}
+// four fp16 values (two packed pairs) -> float4
+__device__ __forceinline__ float4 f16x4_to_float4(unsigned lo, unsigned hi) {
+  const f16x2 a = __builtin_bit_cast(f16x2, lo), b = __builtin_bit_cast(f16x2, hi);
+  return make_float4((float)a[0], (float)a[1], (float)b[0], (float)b[1]);
+}
+
 // two floats -> packed bf16 pair (round to nearest even; v_cvt_pk_bf16_f32), element 0 in the low half
 __device__ __forceinline__ unsigned pack_bf16(float a, float b) {
   const f32x2 v = {a, b};
@@ -65,29 +79,32 @@ __device__ __forceinline__ float bf16_hi_f32(unsigned p) { return __uint_as_floa
 // conv's 1x1 is scaled up the same way (pre-scaled taps, uda_api.hip).  Measured on the heads of D0 / D2 against the float32
 // CPU oracle (tools/head_error_probe.py): 2.4e-7 / 3.1e-7 relative rms - the float32 floor (three bf16 pieces: 2.3e-7 / 3.3e-7;
 // two bf16 pieces: 5.9e-6 / 5.1e-6).
-__host__ __device__ constexpr int split_np(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : 2; }   // pieces per operand
+// 5 = ONE fp16 piece / one product (UDA_SPLIT_F16X1, the operands of Keras mixed_float16): no split, a third of the matrix-core
+// work of the two-piece schemes, ~2^-11 per operand; range tracked exactly as for two fp16 pieces.
+__host__ __device__ constexpr int split_np(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : (scheme == UDA_SPLIT_F16X1 ? 1 : 2); }   // pieces per operand
+__host__ __device__ constexpr bool split_f16(int scheme) { return scheme == UDA_SPLIT_F16X2 || scheme == UDA_SPLIT_F16X1; }
 
 // two floats -> one packed piece pair (round to nearest even), element 0 in the low half
 template <int SCH>
 __device__ __forceinline__ unsigned pack_piece(float a, float b) {
   const f32x2 v = {a, b};
-  if constexpr (SCH == UDA_SPLIT_F16X2) return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));   // v_cvt_pk_f16_f32
+  if constexpr (split_f16(SCH)) return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));   // v_cvt_pk_f16_f32
   else return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));                                   // v_cvt_pk_bf16_f32
 }
 template <int SCH>
 __device__ __forceinline__ float piece_lo(unsigned p) {
-  if constexpr (SCH == UDA_SPLIT_F16X2) return (float)__builtin_bit_cast(f16x2, p)[0];
+  if constexpr (split_f16(SCH)) return (float)__builtin_bit_cast(f16x2, p)[0];
   else return __uint_as_float(p << 16);
 }
 template <int SCH>
 __device__ __forceinline__ float piece_hi(unsigned p) {
-  if constexpr (SCH == UDA_SPLIT_F16X2) return (float)__builtin_bit_cast(f16x2, p)[1];
+  if constexpr (split_f16(SCH)) return (float)__builtin_bit_cast(f16x2, p)[1];
   else return __uint_as_float(p & 0xffff0000u);
 }
 // fragments travel as bf16x8 (16 bytes) whatever the scheme; the matrix instruction reinterprets them
 template <int SCH>
 __device__ __forceinline__ f32x16 mfma16(const bf16x8& a, const bf16x8& b, f32x16 acc) {
-  if constexpr (SCH == UDA_SPLIT_F16X2)
+  if constexpr (split_f16(SCH))
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
   else
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
@@ -99,11 +116,11 @@ template <int SCH>
 __device__ __forceinline__ void split_track(float& amax, float a, float b) {
   // (written as the one instruction it is: fmaxf() first quiets each operand with a v_max_f32 x, |x|, |x| of its own -
   // seven instructions and 16 more live registers per four values in pwb_kernel, which then spilled at three blocks per CU)
-  if constexpr (SCH == UDA_SPLIT_F16X2) asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(a), "v"(b));
+  if constexpr (split_f16(SCH)) asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(a), "v"(b));
 }
 template <int SCH>
 __device__ __forceinline__ void split_report(float amax, unsigned* flag) {
-  if constexpr (SCH == UDA_SPLIT_F16X2) {
+  if constexpr (split_f16(SCH)) {
     // wave-uniform branch (one ballot): nothing in the kernel's hot path becomes control-dependent on a divergent condition
     if (flag && __builtin_amdgcn_ballot_w64(!(amax <= UDA_F16_MAX)) != 0ull) atomicOr(flag, 1u);
   }
@@ -135,6 +152,7 @@ __device__ __forceinline__ void split_parts(const float4& v0, const float4& v1, 
 // per product, fp16: ~2^-22), three bf16 pieces -> + a2 b0 + a0 b2 + a1 b1 in front (~2^-24)
 template <int SCH>
 __device__ __forceinline__ f32x16 mfma_terms(const bf16x8* a, const bf16x8* b, f32x16 acc) {
+  if constexpr (SCH == UDA_SPLIT_F16X1) return mfma16<SCH>(a[0], b[0], acc);     // one piece: the one product
   if constexpr (SCH == UDA_SPLIT_BF16X3) {
     acc = mfma16<SCH>(a[2], b[0], acc);
     acc = mfma16<SCH>(a[0], b[2], acc);

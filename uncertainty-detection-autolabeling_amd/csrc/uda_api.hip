@@ -43,6 +43,7 @@ struct uda_ctx {
   std::vector<int> wscheme;        // per op: the scheme its packed weights use (an op whose weights do not suit fp16 pieces keeps bf16 x3)
   std::vector<float> wunscale;     // per op: 1 / (power-of-two factor folded into the packed weights); 1 unless fp16 pieces
   int n_f16_ops = 0, n_f16_demoted = 0;
+  std::vector<char> buf_f16;       // per buffer: stored as fp16 in its float32-sized slot (set_f16_storage)
   // fp16 pieces: a kernel that splits an operand above 65504 sets bit 0 of ITS OP's flag word.  Two arrays of n_ops + 1
   // words (index n_ops: launches outside the op list): pipelined run s raises its flags in array s, everything else in array 0.
   unsigned* d_oor = nullptr;
@@ -207,6 +208,7 @@ struct uda_ctx {
   uint32_t prof_mask = 0;
   ProfSlot prof[32];
 };
+static void set_f16_storage(uda_ctx* c);
 
 static void free_prefix_ws(uda_ctx::PrefixWs& w);
 
@@ -232,7 +234,7 @@ static hipError_t dalloc(T** p, size_t n) {
   return hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
 }
 
-// UDA_PW_SCHEME = f16x2 | bf16x3 | bf16x2 | f32 (mirror: plan.pw_scheme); the older UDA_PW_TERMS = 6 | 3 | 0 names the last three
+// UDA_PW_SCHEME = f16x2 | bf16x3 | bf16x2 | f32 | f16 (mirror: plan.pw_scheme); the older UDA_PW_TERMS = 6 | 3 | 0 names three of them
 static int parse_pw_scheme(std::string* err) {
   const char* v = getenv("UDA_PW_SCHEME");
   if (v && *v) {
@@ -240,7 +242,8 @@ static int parse_pw_scheme(std::string* err) {
     if (!strcmp(v, "bf16x3")) return UDA_SPLIT_BF16X3;
     if (!strcmp(v, "bf16x2")) return UDA_SPLIT_BF16X2;
     if (!strcmp(v, "f32")) return UDA_SPLIT_NONE;
-    if (err) *err = std::string("UDA_PW_SCHEME=") + v + ": expected f16x2, bf16x3, bf16x2 or f32";
+    if (!strcmp(v, "f16")) return UDA_SPLIT_F16X1;
+    if (err) *err = std::string("UDA_PW_SCHEME=") + v + ": expected f16x2, bf16x3, bf16x2, f32 or f16";
     return -1;
   }
   const char* t = getenv("UDA_PW_TERMS");
@@ -584,6 +587,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
     c->wsplit_off.assign(n_ops, -1);
     c->wpar_off.assign(n_ops, -1);
     c->wscheme.assign(n_ops, c->pw_parts);
+    c->buf_f16.assign(n_bufs, 0);
     c->wunscale.assign(n_ops, 1.0f);
     CK(dalloc(&c->d_oor, 2 * ((size_t)n_ops + 1)));
     CK(hipMemset(c->d_oor, 0, 2 * ((size_t)n_ops + 1) * sizeof(unsigned)));
@@ -608,8 +612,8 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
           // weight that matters is then a normal fp16 number; the epilogue multiplies the accumulator by the inverse (exact)
           float scale = 1.0f;
           int sch = c->pw_parts;
-          if (sch == UDA_SPLIT_F16X2 && !kind_f16) sch = UDA_SPLIT_BF16X3;
-          if (sch == UDA_SPLIT_F16X2) {
+          if (uda_split_f16(sch) && !kind_f16) sch = UDA_SPLIT_BF16X3;
+          if (uda_split_f16(sch)) {
             scale = split_weight_scale(weights + o.w_off, (size_t)K * Nn);
             c->wunscale[i] = 1.0f / scale;
             ++c->n_f16_ops;
@@ -625,7 +629,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
           // the range flag watches the scaled values (65504 / 64 = 1023 for the depthwise result itself).
           size_t dw_fl = 0;
           float ascale = 1.0f;
-          if (o.kind == UDA_OP_SEP && sch == UDA_SPLIT_F16X2 && o.w2_off >= 0) {
+          if (o.kind == UDA_OP_SEP && uda_split_f16(sch) && o.w2_off >= 0) {
             static const int shift = getenv("UDA_F16_SEP_SHIFT") ? atoi(getenv("UDA_F16_SEP_SHIFT")) : 6;
             ascale = ldexpf(1.0f, shift < 0 ? 0 : (shift > 12 ? 12 : shift));
             dw_fl = (size_t)9 * K;
@@ -649,13 +653,16 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
           // the BN scale, with the BN shift row) cannot carry a power-of-two factor.  It keeps fp16 pieces when its entries
           // sit where two pieces resolve them (largest below 2^15, rms at least 2^-6: a low piece that is subnormal resolves
           // 2^-25 absolutely); otherwise THIS op keeps three bf16 pieces - decided here, per op, never silently degraded.
+          // One fp16 piece (UDA_SPLIT_F16X1) has no low piece to keep normal: as in Keras mixed_float16, an entry below 2^-14 is
+          // simply a subnormal fp16 operand, so only the range test applies.
           int sch = c->pw_parts;
-          if (sch == UDA_SPLIT_F16X2) {
-            std::vector<uint16_t> probe(mbxb_packed_elems(Ke, Nn, UDA_SPLIT_F16X2));
+          if (uda_split_f16(sch)) {
+            std::vector<uint16_t> probe(mbxb_packed_elems(Ke, Nn, sch));
             float st[2] = {0.f, 0.f};
-            mbxb_pack_weights(weights + o.w_off, weights + o.bn_scale_off, weights + o.bn_shift_off, Ke, Nn, probe.data(), fuse0, UDA_SPLIT_F16X2, st);
+            mbxb_pack_weights(weights + o.w_off, weights + o.bn_scale_off, weights + o.bn_shift_off, Ke, Nn, probe.data(), fuse0, sch, st);
             static const float min_rms = getenv("UDA_F16_MIN_RMS") ? (float)atof(getenv("UDA_F16_MIN_RMS")) : 0.015625f;
-            if (!(st[0] < 32768.0f) || !(st[1] >= min_rms) || !kind_f16) { sch = UDA_SPLIT_BF16X3; ++c->n_f16_demoted; }
+            const bool rms_ok = sch == UDA_SPLIT_F16X1 || st[1] >= min_rms;
+            if (!(st[0] < 32768.0f) || !rms_ok || !kind_f16) { sch = UDA_SPLIT_BF16X3; ++c->n_f16_demoted; }
             else ++c->n_f16_ops;
           }
           c->wscheme[i] = sch;
@@ -674,6 +681,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
         }
         c->wsplit_off[i] = (int64_t)at;
       }
+      set_f16_storage(c);
       // LDS budget of every fused launch, checked now and by name (a template / shape pair that asks for more than a CU has
       // would otherwise surface as a refused launch in the middle of the first run: round 3, D2 under six-term products)
       for (int i = 0; i < n_ops; ++i) {
@@ -683,7 +691,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
         size_t lds = 0;
         if (o.kind == UDA_OP_MBX) lds = mbx_lds_bytes(o.se_scale >= 0 ? o.se_mid : K, Nn, o.k, o.stride, c->wscheme[i], bufs[o.out].H, bufs[o.out].W);
         else if (o.kind == UDA_OP_SEP) {
-          lds = o.fuse_in ? sepf_lds_bytes(K, Nn, c->wscheme[i]) : sep_lds_bytes(K, Nn, c->wscheme[i]);
+          lds = o.fuse_in ? sepf_lds_bytes(K, Nn, c->wscheme[i]) : sep_lds_bytes(K, Nn, c->wscheme[i], o.drop_site2 >= 0);
           if (o.fuse_in && !sepf_supported(K, Nn, c->wscheme[i])) {
             fail(nullptr, "op %d: separable conv %d -> %d (split scheme %d) has no fused-input kernel (planner: plan.sepf_supported)", i, K, Nn, c->wscheme[i]);
             uda_destroy(c);
@@ -1168,6 +1176,7 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
       a.bn_scale = v.wt(o.bn_scale_off);
       a.bn_shift = v.wt(o.bn_shift_off);
       a.se = o.se_scale >= 0 ? v.ptr(o.se_scale) : nullptr;
+      a.in_f16 = c->buf_f16[o.in[0]];
       a.se_div = 1;
       if (o.se_scale >= 0) {
         const uda_buf_desc_t& sb = c->bufs[o.se_scale];
@@ -1186,7 +1195,7 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
         a.wparts = c->wscheme[oi];
         a.wunscale = c->wunscale[oi];
         a.oor = c->oor_cur + oi;
-        if (a.wparts == UDA_SPLIT_F16X2) c->oor_armed = true;
+        if (uda_split_f16(a.wparts)) c->oor_armed = true;
         launch_pwb(a, rows, v.stream());
       } else {
         launch_pw(a, rows, v.stream());
@@ -1254,8 +1263,9 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
         a.wsplit = wsplit_of(c, oi);
         a.wparts = c->wscheme[oi];
         a.oor = c->oor_cur + oi;
-        if (a.wparts == UDA_SPLIT_F16X2) c->oor_armed = true;
+        if (uda_split_f16(a.wparts)) c->oor_armed = true;
         a.wpar = (const float*)wpar_of(c, oi);
+        a.out_f16 = c->buf_f16[o.out];
         if (fuse0) {
           const uda_buf_desc_t& gb = c->bufs[o.se_scale];
           if (gb.per_sample && !ob.per_sample) return fail(c, "op %d: per-sample gate on a per-image output", oi);
@@ -1300,7 +1310,7 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
       a.wparts = c->wscheme[oi];
       a.wunscale = c->wunscale[oi];
       a.oor = c->oor_cur + oi;
-      if (a.wparts == UDA_SPLIT_F16X2) c->oor_armed = true;
+      if (uda_split_f16(a.wparts)) c->oor_armed = true;
       a.bias = v.wt(o.bias_off);
       a.bn_scale = v.wt(o.bn_scale_off);
       a.bn_shift = v.wt(o.bn_shift_off);
@@ -1429,7 +1439,7 @@ static int run_sep_group(uda_ctx* c, const ChunkView& v, int oi, int n) {
   a.wparts = c->wscheme[oi];
   a.wunscale = c->wunscale[oi];
   a.oor = c->oor_cur + oi;            // (one word for the layer's launch: its levels share the 1x1 kernel and are re-packed together)
-  if (a.wparts == UDA_SPLIT_F16X2) c->oor_armed = true;
+  if (uda_split_f16(a.wparts)) c->oor_armed = true;
   launch_sep_multi(a, lv, n, v.rows(ob0), v.stream());
   return 0;
 }
@@ -1792,7 +1802,7 @@ static int run_post(uda_ctx* c, int n, int post_mode) {
 }
 
 // ------------------------------------------------------------------------------------ fp16 range: demote and serve again
-// fp16-piece contractions (UDA_SPLIT_F16X2): an activation above 65504 cannot be split and its products are infinite.
+// fp16-piece contractions (UDA_SPLIT_F16X2, UDA_SPLIT_F16X1): an activation above 65504 cannot be split and its products are infinite.
 // Every kernel that splits operands reports that through its op's flag word; every reader of a run's results comes
 // through check_split_range first.  A raised flag does not fail the run (the reference computes in float32 and always
 // returns, infer_lib.py:337-343): the FIRST flagged op in op order - everything behind it only saw its infinities - is
@@ -1815,6 +1825,30 @@ static bool can_replay(const uda_ctx* c, const uda_ctx::RunRec* r) {
   return true;
 }
 
+// One fp16 piece (UDA_SPLIT_F16X1): the expanded tensor between a fused MBConv front half and its projection is stored as
+// fp16 (half the bytes of the largest round trip of the step).  A buffer qualifies when its producer is a fused front half
+// running one piece and EVERY reference to it in the op list is the input of a 1x1 conv that runs one piece as well, or the
+// geometry-only second input of its SE op (the gated A-load of pwb_kernel / pws_kernel reads halves); anything else - an unfused fallback, another scheme on either side
+// after a range demotion, a fused-prologue consumer - keeps float32.  Recomputed after every demotion (plan.py mirrors the
+// rule for the ops it plans; this is the authoritative copy: it also sees the per-op schemes uda_create chose).
+static void set_f16_storage(uda_ctx* c) {
+  const int n_ops = (int)c->ops.size(), n_bufs = (int)c->bufs.size();
+  c->buf_f16.assign(n_bufs, 0);
+  std::vector<int> refs(n_bufs, 0), ok_refs(n_bufs, 0);
+  for (int i = 0; i < n_ops; ++i) {
+    const uda_op_t& o = c->ops[i];
+    const bool pw1 = o.kind == UDA_OP_PW && c->wsplit_off[i] >= 0 && c->wscheme[i] == UDA_SPLIT_F16X1;
+    auto ref = [&](int b, bool ok) { if (b >= 0 && b < n_bufs) { ++refs[b]; if (ok) ++ok_refs[b]; } };
+    for (int j = 0; j < UDA_MAX_FUSE_INPUTS; ++j) ref(o.in[j], (j == 0 && pw1) || (j == 1 && o.kind == UDA_OP_SE));   // (SE: geometry only)
+    ref(o.se_scale, false); ref(o.se_partial, false); ref(o.residual, false);
+  }
+  for (int i = 0; i < n_ops; ++i) {
+    const uda_op_t& o = c->ops[i];
+    if (o.kind != UDA_OP_MBX || c->wsplit_off[i] < 0 || c->wscheme[i] != UDA_SPLIT_F16X1 || o.out < 0) continue;
+    if (c->bufs[o.out].kind == 0 && refs[o.out] > 0 && refs[o.out] == ok_refs[o.out]) c->buf_f16[o.out] = 1;
+  }
+}
+
 // Re-pack op `oi` (and the ops that share its launch: the pyramid levels of a head layer) with three bf16 pieces.
 static int demote_ops(uda_ctx* c, int oi) {
   const int n_ops = (int)c->ops.size();
@@ -1828,7 +1862,7 @@ static int demote_ops(uda_ctx* c, int oi) {
   int done = 0;      // (0: re-packed already - a pipelined run queued before that demotion raised the same flag)
   for (int i = g0; i < g1 && i < n_ops; ++i) {
     const uda_op_t& o = c->ops[i];
-    if (c->wscheme[i] != UDA_SPLIT_F16X2 || c->wsplit_off[i] < 0) continue;
+    if (!uda_split_f16(c->wscheme[i]) || c->wsplit_off[i] < 0) continue;
     const int K = c->bufs[o.in[0]].C, Nn = c->bufs[o.out].C;
     const int sch = UDA_SPLIT_BF16X3;
     std::vector<uint16_t> packed;
@@ -1841,6 +1875,11 @@ static int demote_ops(uda_ctx* c, int oi) {
         lds = o.fuse_in ? sepf_lds_bytes(K, Nn, sch) : sep_lds_bytes(K, Nn, sch);
         if (o.fuse_in && !sepf_supported(K, Nn, sch))
           return fail(c, "op %d raised the fp16 range flag and has no three-piece kernel (fused-input separable conv %d -> %d): "
+                         "re-create the handle with UDA_PW_SCHEME=bf16x3", i, K, Nn);
+        // (one fp16 piece frees LDS: a deferred-input conv that fits it may have no three-piece deferred-input mode.  Checked
+        // before anything is re-packed, so the op's scheme stays as it was)
+        if (c->wscheme[i] == UDA_SPLIT_F16X1 && !o.fuse_in && o.drop_site2 >= 0 && !sep_tin_supported(K, Nn, sch))
+          return fail(c, "op %d raised the fp16 range flag and its deferred-input separable conv %d -> %d has no three-piece kernel: "
                          "re-create the handle with UDA_PW_SCHEME=bf16x3", i, K, Nn);
       }
     } else if (o.kind == UDA_OP_MBX) {
@@ -1876,6 +1915,7 @@ static int demote_ops(uda_ctx* c, int oi) {
                     "(demotion %lld of this handle); the run is served again\n", i, o.kind, K, Nn, (long long)c->range_demotions);
   }
   (void)done;      // serving the run again is all that is left to do in that case
+  set_f16_storage(c);      // a demoted producer or consumer takes its expanded tensor back to float32
   return 0;
 }
 
@@ -2701,6 +2741,12 @@ extern "C" int uda_read_buffer(uda_ctx_t* c, int32_t buf, float* host, int64_t n
   }
   const int64_t have = (int64_t)v.rows(b) * b.H * b.W * b.C;
   if (n_floats > have) return fail(c, "read_buffer: asked %lld floats, buffer holds %lld", (long long)n_floats, (long long)have);
+  if (c->buf_f16[buf]) {          // an fp16 expanded tensor (set_f16_storage): widened to float32 here
+    std::vector<uint16_t> h((size_t)n_floats);
+    HIPC(c, hipMemcpy(h.data(), v.ptr(buf), (size_t)n_floats * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n_floats; ++i) host[i] = (float)__builtin_bit_cast(_Float16, h[(size_t)i]);
+    return 0;
+  }
   HIPC(c, hipMemcpy(host, v.ptr(buf), n_floats * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }

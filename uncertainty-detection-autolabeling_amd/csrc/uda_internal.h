@@ -75,8 +75,10 @@ enum {
   UDA_SPLIT_BF16X2 = 2,   // two bf16 pieces per operand, three cross terms (~2^-17 per product)
   UDA_SPLIT_BF16X3 = 3,   // three bf16 pieces, six cross terms (~2^-24)
   UDA_SPLIT_F16X2 = 4,    // two fp16 pieces, three cross terms (~2^-22; operands must stay below 65504)
+  UDA_SPLIT_F16X1 = 5,    // one fp16 piece, one product (~2^-11: Keras mixed_float16 operands; same range limit)
 };
-inline int uda_split_pieces(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : 2; }
+inline int uda_split_pieces(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : (scheme == UDA_SPLIT_F16X1 ? 1 : 2); }
+inline bool uda_split_f16(int scheme) { return scheme == UDA_SPLIT_F16X2 || scheme == UDA_SPLIT_F16X1; }   // fp16 pieces: range-tracked
 
 // ---------------------------------------------------------------- kernel argument blocks
 struct PreGeo;
@@ -102,6 +104,7 @@ struct StemArgs {
 struct PwArgs {
   const float* in;       // [rows_in, HW, Cin]
   float* out;            // [rows, HW, Cout]
+  int in_f16;            // one fp16 piece only: `in` holds fp16 values (the expanded tensor of a fused MBConv front half)
   const float* w;        // [Cin, Cout]
   const float* bias;     // [Cout] or null
   const float* bn_scale; // [Cout] or null
@@ -166,7 +169,7 @@ struct SepMulti {
 };
 void launch_sep_multi(const SepArgs& common, const SepLevel* lv, int n_lv, int rows, hipStream_t s);
 bool sep_supported(int C, int Cout);
-size_t sep_lds_bytes(int C, int Cout, int scheme);      // dynamic LDS of the launch an op of this shape gets
+size_t sep_lds_bytes(int C, int Cout, int scheme, bool tin = false);      // dynamic LDS of the launch an op of this shape gets
 struct FuseArgs;
 // The same conv on an LDS-staged 16 x 16 tile (kernels_sep.hip: sepf_kernel); with `fused` the input is the BiFPN fusion
 // described there, computed on the fly (a.in unused).  Outputs are bit-identical to launch_sep's.
@@ -195,6 +198,7 @@ struct DwArgs {
 struct MbxArgs {
   const float* in;        // [rows_in, H, W, Cin]
   float* out;             // [rows, Ho, Wo, Cmid]
+  int out_f16;            // one fp16 piece only: `out` is stored as fp16 (round to nearest; the SE tile sums stay float32)
   const float* we;        // expand kernel [Cin, Cmid]
   const float* sc0;       // BN after expand
   const float* sh0;

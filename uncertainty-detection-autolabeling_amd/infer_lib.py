@@ -76,7 +76,7 @@ class ServingDriver:
         self.weights = weights
         if chunk_images is None:
             chunk_images = min(self._cap, int(self.params.get("uda_chunk_images", 16)))
-        # `uda_pw_scheme` in model_params (f16x2 | bf16x3 | bf16x2 | f32): the split scheme of THIS handle's 1x1 contractions.  The
+        # `uda_pw_scheme` in model_params (f16x2 | bf16x3 | bf16x2 | f32 | f16): the split scheme of THIS handle's 1x1 contractions.  The
         # planner and uda_create both read UDA_PW_SCHEME when they run; the key sets it for exactly that long (a
         # per-handle choice instead of a process-wide environment variable).
         import os

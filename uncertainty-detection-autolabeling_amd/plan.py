@@ -49,14 +49,15 @@ def dw_tiles(C, Ho, Wo, k, stride):
     return -(-Ho // dw_rows(k, stride)) * dw_tiles_x(C, Wo, k, stride)
 
 
-PW_SCHEMES = ("f16x2", "bf16x3", "bf16x2", "f32")
+PW_SCHEMES = ("f16x2", "bf16x3", "bf16x2", "f32", "f16")
 PW_SCHEME_DEFAULT = "f16x2"
 
 
 def pw_scheme():
     """Split scheme of the 1x1 contractions (mirror of parse_pw_scheme in csrc/uda_api.hip): UDA_PW_SCHEME =
     f16x2 (two fp16 pieces, three cross terms, ~2^-22 per product: the default) | bf16x3 (three bf16 pieces, six terms,
-    ~2^-24) | bf16x2 (two bf16 pieces, three terms, ~2^-17) | f32 (exact f32-input MFMA kernels, unfused);
+    ~2^-24) | bf16x2 (two bf16 pieces, three terms, ~2^-17) | f32 (exact f32-input MFMA kernels, unfused) | f16 (ONE fp16
+    piece, one product, ~2^-11: the operands of Keras mixed_float16, fp32 accumulation; opt-in, see split_pieces);
     the older UDA_PW_TERMS = 6 | 3 | 0 selects the last three when UDA_PW_SCHEME is not set."""
     import os
     v = os.environ.get("UDA_PW_SCHEME")
@@ -71,6 +72,11 @@ def pw_scheme():
     if t not in (0, 3, 6):
         raise ValueError("UDA_PW_TERMS=%r: expected 6, 3 or 0" % (t,))
     return {0: "f32", 3: "bf16x2", 6: "bf16x3"}[t]
+
+
+def split_pieces(sch):
+    """Pieces per operand of a split scheme (mirror of uda_split_pieces in csrc/uda_internal.h)."""
+    return {"bf16x3": 3, "f16": 1}.get(sch, 2)
 
 
 def mbx_deep(cin):
@@ -127,26 +133,28 @@ def sepf_supported(C, Cout):
     sch = pw_scheme()
     if sch == "f32" or not int(os.environ.get("UDA_FUSE_IN", "1")):
         return False
-    npc = 3 if sch == "bf16x3" else 2
+    npc = split_pieces(sch)
     lds = 18 * 18 * 36 * 4 + 2 * (-(-Cout // 32)) * npc * 1024
     return C % 8 == 0 and 16 <= C <= 128 and Cout % 4 == 0 and 4 <= Cout <= 128 and lds <= 80 * 1024
 
 
-def sep_tin_supported(C, Cout):
+def sep_tin_supported(C, Cout, sch=None):
     """A plain separable conv can take a DEFERRED dropout site of its producer (mirror of sep_tin_supported in
     csrc/kernels_sep.hip): 64 .. 128 input channels, two to four 32-column tiles in one block, the per-sample epilogue staging
-    inside the A image."""
+    inside the A image.  `sch`: the split scheme (default: the handle's, pw_scheme())."""
     import os
-    sch = pw_scheme()
+    sch = pw_scheme() if sch is None else sch
     if sch == "f32" or not int(os.environ.get("UDA_DEFER_HEAD", "1")):
         return False
     if C % 8 or not 64 <= C <= 128 or Cout < 1:
         return False
-    ks, ntl, npc = -(-C // 16), -(-Cout // 32), (3 if sch == "bf16x3" else 2)
+    ks, ntl, npc = -(-C // 16), -(-Cout // 32), split_pieces(sch)
     if not 2 <= ntl <= 4:
         return False
     a_img = 128 * (ks * 64 + 16) if sch == "bf16x3" else npc * 128 * (ks * 32 + 16)
     stg = 4 * 32 * ntl * 32 * 4 if Cout % 4 else 4 * 32 * 68 * 4
+    if sch == "f16":
+        a_img = max(a_img, stg)         # (sep_a_region: one piece widens the A region to hold the staging)
     return stg <= a_img and a_img + ks * ntl * npc * 1024 <= 120 * 1024
 
 
@@ -265,12 +273,15 @@ def check_model_params(cfg):
 
 
 class _Buf:
-    __slots__ = ("H", "W", "C", "per_sample", "kind", "level", "offset", "first", "last", "name")
+    __slots__ = ("H", "W", "C", "per_sample", "kind", "level", "offset", "first", "last", "name", "storage")
 
     def __init__(self, H, W, C, per_sample, kind=0, level=0, name=""):
         self.H, self.W, self.C, self.per_sample = int(H), int(W), int(C), bool(per_sample)
         self.kind, self.level, self.offset = kind, level, 0
         self.first, self.last, self.name = None, None, name
+        # element type on the device: "f32", or "f16" for the expanded tensor of a fused MBConv front half under the one-piece
+        # scheme (mark_f16_storage).  The arena slot stays float32-sized either way.
+        self.storage = "f32"
 
 
 class Plan:
@@ -305,6 +316,7 @@ class Plan:
         self._build_sites()
         self._lower()
         self._plan_memory()
+        self.mark_f16_storage()
 
     def _post_only_layout(self):
         """A handle that only post-processes injected head outputs (postprocess.generate_detections on arrays that
@@ -869,6 +881,28 @@ class Plan:
             sites[i].channels, sites[i].rate = ch, np.float32(r)
         blob = np.concatenate(self.blob) if self.blob else np.zeros(4, np.float32)
         return m, bufs, ops, sites, blob, self.anchors()
+
+    def mark_f16_storage(self):
+        """Under the one-piece scheme (pw_scheme() == "f16") the output of a fused MBConv front half is stored as fp16 when every
+        reference to it is the input of a 1x1 conv (its projection) or the geometry-only input of its SE op - mirror of set_f16_storage in csrc/uda_api.hip, which also
+        keeps float32 where uda_create or a range demotion gives either side another scheme."""
+        for b in self.bufs:
+            b.storage = "f32"
+        if pw_scheme() != "f16":
+            return
+        refs, ok = [0] * len(self.bufs), [0] * len(self.bufs)
+        for o in self.ops:
+            for j, b in enumerate(o["ins"]):
+                if b >= 0:
+                    refs[b] += 1
+                    ok[b] += int((j == 0 and o["kind"] == capi.OP_PW) or (j == 1 and o["kind"] == capi.OP_SE))   # (SE: geometry)
+            for key in ("se_scale", "se_partial", "residual"):
+                if o[key] >= 0:
+                    refs[o[key]] += 1
+        for o in self.ops:
+            b = o["out"]
+            if o["kind"] == capi.OP_MBX and self.bufs[b].kind == 0 and refs[b] > 0 and refs[b] == ok[b]:
+                self.bufs[b].storage = "f16"
 
     def summary(self):
         return dict(n_ops=len(self.ops), n_bufs=len(self.bufs), arena_mb=self.arena_floats * 4 / 2 ** 20,
