@@ -228,6 +228,11 @@ int uda_drain(uda_ctx_t* ctx);
  * three bf16 pieces (float32 exponent range), the run is served again from its unchanged inputs before any reader sees
  * it, and the op stays that way.  This counts the ops re-packed so far (0 for every weight set the tests initialise). */
 int64_t uda_range_demotions(const uda_ctx_t* ctx);
+/* Debug: how op `op` of the handle's op list runs now (after any range demotion).  *scheme = its split scheme (UDA_SPLIT_*
+ * of uda_internal.h; -1: no packed weights, the op has no split contraction), *w_scale = the power-of-two factor its packed
+ * weights carry (1 unless fp16 pieces), *a_scale = the factor on its A operand (the pre-scaled depthwise taps of an fp16
+ * separable conv; else 1), *out_f16 = 1 if its output tensor is stored as fp16.  Any pointer may be NULL. */
+int uda_debug_op_scheme(const uda_ctx_t* ctx, int32_t op, int32_t* scheme, float* w_scale, float* a_scale, int32_t* out_f16);
 /* Global NMS over the whole anchor set runs on the score prefix that can be selected at all, checked on the
  * device; this counts the images / problems that failed the check and were redone on the full set (the results
  * are identical either way). */
@@ -318,8 +323,9 @@ int uda_set_num_images(uda_ctx_t* ctx, int32_t n);
  * head outputs of the last run of `src` (a deterministic member network, T = 1) into sample slot
  * `sample` of `dst` (a handle whose model has mc_samples = number of members and stacked heads);
  * uda_postprocess_heads(dst) then aggregates the members exactly like MC samples (a8 / a14).
- * Device-to-device on dst's stream; both handles must live on the same GPU and share the geometry. */
-int uda_copy_heads(uda_ctx_t* dst, const uda_ctx_t* src, int32_t n, int32_t sample);
+ * Device-to-device on dst's stream; both handles must live on the same GPU and share the geometry.  src is read like
+ * any reader reads a run (uda_range_demotions): a member whose run raised the fp16 range flag is served again first. */
+int uda_copy_heads(uda_ctx_t* dst, uda_ctx_t* src, int32_t n, int32_t sample);
 /* predict = set_images_f32 + run(no post) ; read back with uda_get_head_outputs */
 int uda_predict(uda_ctx_t* ctx, const float* images, int32_t n);
 
@@ -342,9 +348,10 @@ int uda_nms(uda_ctx_t* ctx, const float* boxes, const float* scores, int32_t n_i
  * out[r, p, :] = (act(bn(in[r / in_div, p, :] * se[r / in_div, :] @ w + bias)) * mask[r, :]) + res[r, p, :]
  * in [rows/in_div, hw, cin], w [cin, cout], se [rows/in_div, cin], mask [rows, cout], res/out [rows, hw, cout];
  * optional arguments may be NULL.  terms: 0 = f32-input MFMA, 3 / 6 = split-bf16 MFMA with 3 / 6 cross terms, 16 = two fp16
- * pieces per operand with 3 cross terms (the default scheme of the network, UDA_PW_SCHEME=f16x2; fails - it does not
- * return infinities - when an input exceeds fp16's 65504) (kernels_pwb.hip).  The launch is repeated `reps` times for
- * *avg_ms (HIP events). */
+ * pieces per operand with 3 cross terms (the default scheme of the network, UDA_PW_SCHEME=f16x2), 1 = one fp16 piece, one
+ * product (UDA_PW_SCHEME=f16).  Both fp16 schemes pack the weights times split_weight_scale as the network does, and fail -
+ * they do not return infinities - when an input exceeds fp16's 65504 (kernels_pwb.hip).  The launch is repeated `reps`
+ * times for *avg_ms (HIP events). */
 int uda_debug_pw(int32_t device, const float* in, const float* w, const float* bias, const float* bn_scale,
                  const float* bn_shift, const float* se, const float* mask, const float* res,
                  int32_t rows, int32_t in_div, int32_t hw, int32_t cin, int32_t cout, int32_t act,

@@ -42,6 +42,7 @@ struct uda_ctx {
   int pw_parts = UDA_SPLIT_F16X2;  // requested split scheme of the 1x1 contractions (UDA_PW_SCHEME / UDA_PW_TERMS, parse_pw_scheme)
   std::vector<int> wscheme;        // per op: the scheme its packed weights use (an op whose weights do not suit fp16 pieces keeps bf16 x3)
   std::vector<float> wunscale;     // per op: 1 / (power-of-two factor folded into the packed weights); 1 unless fp16 pieces
+  std::vector<float> wascale;      // per op: factor on the A operand (fp16 separable conv: pre-scaled depthwise taps); part of wunscale
   int n_f16_ops = 0, n_f16_demoted = 0;
   std::vector<char> buf_f16;       // per buffer: stored as fp16 in its float32-sized slot (set_f16_storage)
   // fp16 pieces: a kernel that splits an operand above 65504 sets bit 0 of ITS OP's flag word.  Two arrays of n_ops + 1
@@ -589,6 +590,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
     c->wscheme.assign(n_ops, c->pw_parts);
     c->buf_f16.assign(n_bufs, 0);
     c->wunscale.assign(n_ops, 1.0f);
+    c->wascale.assign(n_ops, 1.0f);
     CK(dalloc(&c->d_oor, 2 * ((size_t)n_ops + 1)));
     CK(hipMemset(c->d_oor, 0, 2 * ((size_t)n_ops + 1) * sizeof(unsigned)));
     c->oor_cur = c->d_oor;
@@ -642,6 +644,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
             memcpy(packed.data() + at + w_elems, wd.data(), dw_fl * sizeof(float));
             c->wpar_off[i] = (int64_t)(at + w_elems);
             c->wunscale[i] /= ascale;
+            c->wascale[i] = ascale;
           }
         } else if (o.kind == UDA_OP_MBX && mbx_bf16 && o.bn_scale_off >= 0 && o.bn_shift_off >= 0 &&
                    (mbxb_supported(o.se_scale >= 0 ? o.se_mid : K, Nn, o.k, o.stride) || mbxd_supported(K, Nn, o.k, o.stride))) {
@@ -1859,29 +1862,43 @@ static int demote_ops(uda_ctx* c, int oi) {
     if (lg > 1 && i <= oi && oi < i + lg) { g0 = i; g1 = i + lg; break; }
   }
   const float* weights = c->h_weights.data();
+  const int sch = UDA_SPLIT_BF16X3;
+  // Every reason to refuse is checked for the whole launch group before anything is re-packed: a refused demotion leaves
+  // the handle as it was (each op keeps its scheme and weights), so it goes on serving the batches that stay in range.
+  for (int i = g0; i < g1 && i < n_ops; ++i) {
+    const uda_op_t& o = c->ops[i];
+    if (!uda_split_f16(c->wscheme[i]) || c->wsplit_off[i] < 0) continue;
+    const int K = c->bufs[o.in[0]].C, Nn = c->bufs[o.out].C;
+    size_t lds = 0;
+    if (o.kind == UDA_OP_SEP) {
+      const bool tin = !o.fuse_in && o.drop_site2 >= 0;
+      lds = o.fuse_in ? sepf_lds_bytes(K, Nn, sch) : sep_lds_bytes(K, Nn, sch, tin);
+      if (o.fuse_in && !sepf_supported(K, Nn, sch))
+        return fail(c, "op %d raised the fp16 range flag and has no three-piece kernel (fused-input separable conv %d -> %d): "
+                       "re-create the handle with UDA_PW_SCHEME=bf16x3", i, K, Nn);
+      // (fp16 pieces need less LDS than three bf16 pieces, one or two of them: a deferred-input conv that fits them may
+      // have no three-piece deferred-input mode - D2's 112 -> 112 head layers under head-only MC dropout)
+      if (tin && !sep_tin_supported(K, Nn, sch))
+        return fail(c, "op %d raised the fp16 range flag and its deferred-input separable conv %d -> %d has no three-piece kernel: "
+                       "re-create the handle with UDA_PW_SCHEME=bf16x3", i, K, Nn);
+    } else if (o.kind == UDA_OP_MBX) {
+      const int Ke = o.se_scale >= 0 ? o.se_mid : K;
+      lds = mbx_lds_bytes(Ke, Nn, o.k, o.stride, sch, c->bufs[o.out].H, c->bufs[o.out].W);
+    }
+    if (lds > (size_t)160 * 1024)
+      return fail(c, "op %d raised the fp16 range flag and its three-piece launch needs %zu bytes of LDS (a CU has 163840): "
+                     "re-create the handle with UDA_PW_SCHEME=bf16x3", i, lds);
+  }
   int done = 0;      // (0: re-packed already - a pipelined run queued before that demotion raised the same flag)
   for (int i = g0; i < g1 && i < n_ops; ++i) {
     const uda_op_t& o = c->ops[i];
     if (!uda_split_f16(c->wscheme[i]) || c->wsplit_off[i] < 0) continue;
     const int K = c->bufs[o.in[0]].C, Nn = c->bufs[o.out].C;
-    const int sch = UDA_SPLIT_BF16X3;
     std::vector<uint16_t> packed;
     int64_t par = -1;
-    size_t lds = 0;
     if (o.kind == UDA_OP_PW || o.kind == UDA_OP_SEP) {
       packed.resize((pwb_packed_elems(K, Nn, sch) + 7) / 8 * 8);
       pwb_pack_weights(weights + o.w_off, K, Nn, sch, packed.data(), 1.0f);
-      if (o.kind == UDA_OP_SEP) {
-        lds = o.fuse_in ? sepf_lds_bytes(K, Nn, sch) : sep_lds_bytes(K, Nn, sch);
-        if (o.fuse_in && !sepf_supported(K, Nn, sch))
-          return fail(c, "op %d raised the fp16 range flag and has no three-piece kernel (fused-input separable conv %d -> %d): "
-                         "re-create the handle with UDA_PW_SCHEME=bf16x3", i, K, Nn);
-        // (one fp16 piece frees LDS: a deferred-input conv that fits it may have no three-piece deferred-input mode.  Checked
-        // before anything is re-packed, so the op's scheme stays as it was)
-        if (c->wscheme[i] == UDA_SPLIT_F16X1 && !o.fuse_in && o.drop_site2 >= 0 && !sep_tin_supported(K, Nn, sch))
-          return fail(c, "op %d raised the fp16 range flag and its deferred-input separable conv %d -> %d has no three-piece kernel: "
-                         "re-create the handle with UDA_PW_SCHEME=bf16x3", i, K, Nn);
-      }
     } else if (o.kind == UDA_OP_MBX) {
       const bool fuse0 = o.se_scale >= 0;
       const int Ke = fuse0 ? o.se_mid : K;
@@ -1894,13 +1911,9 @@ static int demote_ops(uda_ctx* c, int oi) {
       if (fuse0) mbxb_pack_proj(weights + o.se_w1_off, weights + o.se_b1_off, weights + o.se_w2_off, K, Ke, pf.data() + par_fl);
       memcpy(packed.data() + we, pf.data(), pf.size() * sizeof(float));
       par = (int64_t)we;
-      lds = mbx_lds_bytes(Ke, Nn, o.k, o.stride, sch, c->bufs[o.out].H, c->bufs[o.out].W);
     } else {
       continue;
     }
-    if (lds > (size_t)160 * 1024)
-      return fail(c, "op %d raised the fp16 range flag and its three-piece launch needs %zu bytes of LDS (a CU has 163840): "
-                     "re-create the handle with UDA_PW_SCHEME=bf16x3", i, lds);
     uint16_t* d = nullptr;
     HIPC(c, hipMalloc((void**)&d, packed.size() * sizeof(uint16_t)));
     HIPC(c, hipMemcpy(d, packed.data(), packed.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -1909,6 +1922,7 @@ static int demote_ops(uda_ctx* c, int oi) {
     c->wovr_par[i] = par;
     c->wscheme[i] = sch;
     c->wunscale[i] = 1.0f;
+    c->wascale[i] = 1.0f;
     ++c->range_demotions;
     ++done;
     fprintf(stderr, "[uda] fp16 range: op %d (kind %d, %d -> %d channels) saw an operand above 65504 and now runs on three bf16 pieces "
@@ -2357,6 +2371,18 @@ extern "C" int uda_drain(uda_ctx_t* c) {
 }
 
 extern "C" int64_t uda_range_demotions(const uda_ctx_t* c) { return c ? c->range_demotions : -1; }
+
+extern "C" int uda_debug_op_scheme(const uda_ctx_t* c, int32_t op, int32_t* scheme, float* w_scale, float* a_scale, int32_t* out_f16) {
+  if (!c) return 1;
+  if (op < 0 || op >= (int32_t)c->ops.size()) return fail(const_cast<uda_ctx_t*>(c), "debug_op_scheme: op %d outside [0, %d)", op, (int)c->ops.size());
+  const bool packed = !c->wsplit_off.empty() && c->wsplit_off[op] >= 0;
+  const float as = packed ? c->wascale[op] : 1.0f;
+  if (scheme) *scheme = packed ? c->wscheme[op] : -1;
+  if (a_scale) *a_scale = as;
+  if (w_scale) *w_scale = packed ? 1.0f / (c->wunscale[op] * as) : 1.0f;     // (powers of two: exact)
+  if (out_f16) *out_f16 = (c->ops[op].out >= 0 && !c->buf_f16.empty()) ? c->buf_f16[c->ops[op].out] : 0;
+  return 0;
+}
 extern "C" int64_t uda_nms_prefix_fallbacks(const uda_ctx_t* c) { return c ? c->pfx_fallbacks : -1; }
 extern "C" int64_t uda_nms_coop_fallbacks(const uda_ctx_t* c) { return c ? c->coop_fallbacks : -1; }
 extern "C" int64_t uda_nms_coop_not_launched(const uda_ctx_t* c) { return c ? c->coop_not_launched : -1; }
@@ -2613,6 +2639,7 @@ extern "C" int uda_set_head_outputs(uda_ctx_t* c, int32_t level, int32_t n, cons
   if (level < 0 || level >= c->model.num_levels) return fail(c, "set_head_outputs: bad level %d", level);
   if (n < 1 || n > c->model.max_images) return fail(c, "set_head_outputs: n=%d", n);
   HIPC(c, hipSetDevice(c->device));
+  if (int rc = check_split_range(c)) return rc;        // settled now: a later replay of that run would overwrite these heads
   const uda_model_t& m = c->model;
   const size_t hw = (size_t)m.level_h[level] * m.level_w[level];
   {   // the host buffers must hold exactly what is read from them: [T_x, n, h, w, ch] (T_x = 1 for an unstacked head)
@@ -2645,6 +2672,8 @@ extern "C" int uda_head_outputs_device(uda_ctx_t* c, int32_t level, int32_t whic
   if (!c || !dev_ptr) return c ? fail(c, "head_outputs_device: NULL argument") : 1;
   if (level < 0 || level >= c->model.num_levels) return fail(c, "head_outputs_device: bad level %d", level);
   if (which != 0 && which != 1) return fail(c, "head_outputs_device: which must be 0 (class) or 1 (box)");
+  HIPC(c, hipSetDevice(c->device));
+  if (int rc = check_split_range(c)) return rc;      // (whoever reads or writes the buffer sees the run's in-range heads)
   const uda_model_t& m = c->model;
   const int64_t hw = (int64_t)m.level_h[level] * m.level_w[level];
   *dev_ptr = which ? (void*)c->d_box[level] : (void*)c->d_cls[level];
@@ -2661,7 +2690,7 @@ extern "C" int uda_set_num_images(uda_ctx_t* c, int32_t n) {
   return 0;
 }
 
-extern "C" int uda_copy_heads(uda_ctx_t* dst, const uda_ctx_t* src, int32_t n, int32_t sample) {
+extern "C" int uda_copy_heads(uda_ctx_t* dst, uda_ctx_t* src, int32_t n, int32_t sample) {
   if (dst) { if (int rc_ = no_async(dst, "uda_copy_heads")) return rc_; }
   if (!dst || !src) return 1;
   const uda_model_t& md = dst->model;
@@ -2675,6 +2704,8 @@ extern "C" int uda_copy_heads(uda_ctx_t* dst, const uda_ctx_t* src, int32_t n, i
   if (n < 1 || n > md.max_images || n > ms.max_images) return fail(dst, "copy_heads: n=%d", n);
   HIPC(dst, hipSetDevice(dst->device));
   HIPC(dst, hipStreamSynchronize(src->stream));       // the member's heads must be complete
+  if (check_split_range(src))                          // ... and in range: an ensemble member is a reader like any other
+    return fail(dst, "copy_heads: the source handle failed: %s", uda_last_error(src));
   const int T = md.mc_samples;
   for (int l = 0; l < md.num_levels; ++l) {
     if (md.level_h[l] != ms.level_h[l] || md.level_w[l] != ms.level_w[l]) return fail(dst, "copy_heads: level %d size differs", l);
@@ -2695,6 +2726,9 @@ extern "C" int uda_postprocess_heads(uda_ctx_t* c, int32_t n, const float* image
   if (!c) return 1;
   if (n < 1 || n > c->model.max_images) return fail(c, "postprocess_heads: n=%d", n);
   HIPC(c, hipSetDevice(c->device));
+  // heads left by a network-only run (uda_run(.., 0), uda_predict) are read here first: a run that raised the fp16 range flag
+  // is served again before its heads are post-processed (its replay re-runs the network only)
+  if (int rc = check_split_range(c)) return rc;
   for (int i = 0; i < n; ++i) c->h_scales[i] = image_scales ? image_scales[i] : 1.0f;
   HIPC(c, hipMemcpyAsync(c->d_scales, c->h_scales.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   c->n_images = n;
@@ -2868,8 +2902,8 @@ extern "C" int uda_debug_pw(int32_t device, const float* in, const float* w, con
                             int32_t terms, int32_t reps, float* out, float* avg_ms) {
   if (!in || !w || !out || rows < 1 || in_div < 1 || rows % in_div || hw < 1 || cin < 4 || cin % 4 || cout < 1)
     return fail(nullptr, "uda_debug_pw: bad argument");
-  if (terms != 0 && terms != 3 && terms != 6 && terms != 16)
-    return fail(nullptr, "uda_debug_pw: terms must be 0 (f32 MFMA), 3 (bf16 x2), 6 (bf16 x3) or 16 (fp16 x2)");
+  if (terms != 0 && terms != 1 && terms != 3 && terms != 6 && terms != 16)
+    return fail(nullptr, "uda_debug_pw: terms must be 0 (f32 MFMA), 1 (fp16 x1), 3 (bf16 x2), 6 (bf16 x3) or 16 (fp16 x2)");
   HIPC(nullptr, hipSetDevice(device));
   const size_t rows_in = rows / in_div;
   std::vector<void*> owned;
@@ -2898,8 +2932,9 @@ extern "C" int uda_debug_pw(int32_t device, const float* in, const float* w, con
   uint16_t* d_ws = nullptr;
   unsigned* d_oor = nullptr;
   if (terms) {
-    const int scheme = terms == 6 ? UDA_SPLIT_BF16X3 : (terms == 16 ? UDA_SPLIT_F16X2 : UDA_SPLIT_BF16X2);
-    const float scale = scheme == UDA_SPLIT_F16X2 ? split_weight_scale(w, (size_t)cin * cout) : 1.0f;
+    const int scheme = terms == 6 ? UDA_SPLIT_BF16X3 : (terms == 16 ? UDA_SPLIT_F16X2 : (terms == 1 ? UDA_SPLIT_F16X1 : UDA_SPLIT_BF16X2));
+    // (as uda_create packs a 1x1 conv: fp16 pieces, one or two, carry the power-of-two weight scale)
+    const float scale = uda_split_f16(scheme) ? split_weight_scale(w, (size_t)cin * cout) : 1.0f;
     std::vector<uint16_t> packed(pwb_packed_elems(cin, cout, scheme));
     pwb_pack_weights(w, cin, cout, scheme, packed.data(), scale);
     HIPC(nullptr, hipMalloc((void**)&d_ws, packed.size() * sizeof(uint16_t)));
@@ -2936,7 +2971,7 @@ extern "C" int uda_debug_pw(int32_t device, const float* in, const float* w, con
   hipStreamDestroy(st);
   for (void* p : owned) hipFree(p);
   if (err != hipSuccess) return fail(nullptr, "uda_debug_pw: %s", hipGetErrorString(err));
-  if (oor) return fail(nullptr, "uda_debug_pw: an input above 65504 cannot be split into fp16 pieces (terms = 16)");
+  if (oor) return fail(nullptr, "uda_debug_pw: an input above 65504 cannot be split into fp16 pieces (terms = %d)", terms);
   return 0;
 }
 

@@ -263,6 +263,14 @@ class ServingDriver:
         """Ops re-packed with three bf16 pieces because an operand exceeded fp16's range (`uda_range_demotions`)."""
         return int(self._lib.uda_range_demotions(self._h))
 
+    def op_scheme(self, op):
+        """(scheme, weight scale, A-side scale, output stored as fp16) of op `op` of `plan.ops` as it runs now, after any
+        range demotion (`uda_debug_op_scheme`; scheme: UDA_SPLIT_* of csrc/uda_internal.h, -1 = no split contraction)."""
+        sch, ws, as_, f16 = C.c_int32(), C.c_float(), C.c_float(), C.c_int32()
+        self._ck(self._lib.uda_debug_op_scheme(self._h, int(op), C.byref(sch), C.byref(ws), C.byref(as_), C.byref(f16)),
+                 "uda_debug_op_scheme")
+        return sch.value, ws.value, as_.value, bool(f16.value)
+
     def collect(self, ticket):
         """The detections of a `run_async` (same tuple as `serve`): waits for that run's post-process only."""
         n, mode = self._tickets.pop(ticket)
