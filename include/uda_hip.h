@@ -215,6 +215,26 @@ int uda_synchronize(uda_ctx_t* ctx);
  * (the batch has to be run again); entry points that rewrite head buffers refuse while a run is in flight.  Results are
  * bit-identical to uda_run's. */
 int uda_run_async(uda_ctx_t* ctx, int32_t post_mode, int32_t* ticket);
+/* Augmentation-consistency check (reference infer_model.py:768-848, model_params["consistency_ssl"], hparams_config.py:240;
+ * set for the consistency-based SSL / SSAL datasets, inspector.py:127-128).  The n staged uint8 images (uniform or ragged)
+ * and three variants of each, built on the device, run as ONE batch of 4n through preprocess, network and post-process:
+ *   images n..2n-1   left-right flip (tf.image.flip_left_right, :775-776)
+ *   images 2n..3n-1  cv2.GaussianBlur(im, (9, 9), 0) on uint8 as OpenCV's 8-bit fixed-point filter (:777-781;
+ *                    taps 4 13 30 51 60 51 30 13 4 / 256, REFLECT_101 borders; DESIGN.md "Consistency check")
+ *   images 3n..4n-1  im + N(0, 0.5) in float64, unclipped (:782-792): Philox normal stream, counter (raw pixel, image offset
+ *                    + image, channel, tag 0x4E), keyed by the dropout seed
+ * Variant n + N v keeps image n's raw size and scale; image j draws the dropout rows (offset + j) T + t, so the originals'
+ * detections are bit-identical to uda_run's for the same seed.  Needs max_images >= 4n.  Afterwards the run's readers
+ * (uda_get_detections, uda_get_class_probs, calibrators, uda_get_preprocessed) hold all 4n images, the originals first. */
+int uda_run_consistency(uda_ctx_t* ctx, int32_t post_mode);
+/* Scores of the last uda_run_consistency, [n, M] for its n originals, detection rank k (utils_box.py:56-89, :822-835):
+ *   iou[k]   = mean over the three variants of max_j IoU(original box k, variant box j), all M rows of the variant (padded
+ *              rows included), the flip's boxes un-flipped to [y1, W - x2, y2, W - x1] (W = raw width), float64
+ *   agree[k] = 1 when the mean of the three variants' class ids at rank k is an integer (the reference's rank-wise test;
+ *              the original's class is not consulted) */
+int uda_get_consistency(uda_ctx_t* ctx, double* iou, uint8_t* agree);
+/* The device-built flips then blurs of the current consistency input, packed like the originals (n_bytes = 2 x their bytes). */
+int uda_get_augmented_u8(uda_ctx_t* ctx, uint8_t* out, int64_t n_bytes);
 int uda_collect(uda_ctx_t* ctx, int32_t ticket, float* boxes, float* scores, float* classes, int32_t* valid, float* logits);
 /* The same for the multi-GPU gather: the run's detections as ONE device-resident record buffer (see uda_detections_device
  * for the layout and `rows`); packed on a stream of its own, complete when the call returns; closes the ticket. */

@@ -87,6 +87,9 @@ _SIGNATURES = {
     "uda_run": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "uda_synchronize": (C.c_int, [_P]),
     "uda_run_async": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32)]),
+    "uda_run_consistency": (C.c_int, [_P, C.c_int32]),
+    "uda_get_consistency": (C.c_int, [_P, _P, _P]),
+    "uda_get_augmented_u8": (C.c_int, [_P, _P, C.c_int64]),
     "uda_collect": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "uda_collect_device": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int32)]),
     "uda_drain": (C.c_int, [_P]),

@@ -3,7 +3,11 @@
 // comparable bit for bit with the CPU oracle's statement of the same arithmetic.
 //
 //   preprocess_kernel  normalise + bilinear resize (half-pixel centres) + zero pad
-//                      (reference dataloader.py:69-75,123-152; efficientdet_keras.py:1076-1100)
+//                      (reference dataloader.py:69-75,123-152; efficientdet_keras.py:1076-1100); its NOISE
+//                      instantiation serves the noise variant of the consistency check (infer_model.py:784-793)
+//   augment_u8_kernel  flip + 9x9 Gaussian blur of the staged uint8 images (consistency check, infer_model.py:775-783)
+//   consistency_kernel IoU / class agreement of the originals' detections with the variants' (infer_model.py:768-848,
+//                      utils_box.py:56-89)
 //   aggregate_kernel   MC mean / population std of the class logits, argmax + sigmoid,
 //                      per-sample anchor decode (plain f32 or variance-propagating f64),
 //                      mean / std over samples of the decoded corners, mean of decoded sigma
@@ -25,10 +29,25 @@
 namespace uda {
 
 // ------------------------------------------------------------------------------------ preprocess
-__device__ __forceinline__ float norm_px(const uint8_t* p, int c, const PreprocArgs& a) {
-  return ((float)p[c] - a.mean[c]) / a.stdv[c];
+// Raw value of channel c of raw pixel `px` of image `img` (index in the batch).  NOISE (the consistency check's noise variant,
+// infer_model.py:784-793: im + np.random.normal(0, sqrt(0.5)), summed in float64, neither clipped nor rounded, served as a
+// float image that preprocessing casts to float32): the draw is philox_normal(seed, px, image offset + img, c, tag 0x4E),
+// keyed by the run's dropout seed - a property of the noisy RAW image, so the bilinear taps of one raw pixel agree.
+template <bool NOISE>
+__device__ __forceinline__ float raw_px(const uint8_t* img, size_t px, int c, int n, const PreprocArgs& a) {
+  if constexpr (NOISE)
+    return (float)((double)img[px * 3 + c] +
+                   0.70710678118654752440 * philox_normal(a.noise_seed, (uint32_t)px, a.noise_img0 + (uint32_t)n, (uint32_t)c, 0x4Eu));
+  else
+    return (float)img[px * 3 + c];
 }
 
+template <bool NOISE>
+__device__ __forceinline__ float norm_px(const uint8_t* img, size_t px, int c, int n, const PreprocArgs& a) {
+  return (raw_px<NOISE>(img, px, c, n, a) - a.mean[c]) / a.stdv[c];
+}
+
+template <bool NOISE>
 __global__ __launch_bounds__(256) void preprocess_kernel(PreprocArgs a) {
   const int64_t total = (int64_t)a.n * a.H * a.W;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -44,8 +63,8 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreprocArgs a) {
   }
   const uint8_t* img = a.in + g.off;
   if (g.sh == g.h && g.sw == g.w) {
-    const uint8_t* p = img + ((size_t)y * g.w + x) * 3;
-    for (int c = 0; c < 3; ++c) o[c] = norm_px(p, c, a);
+    const size_t p = (size_t)y * g.w + x;
+    for (int c = 0; c < 3; ++c) o[c] = norm_px<NOISE>(img, p, c, n, a);
     return;
   }
   const float fy = ((float)y + 0.5f) * g.scale_y - 0.5f;
@@ -54,13 +73,13 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreprocArgs a) {
   const int ylo = (int)fmaxf(fly, 0.f), yhi = min((int)ceilf(fy), g.h - 1);
   const int xlo = (int)fmaxf(flx, 0.f), xhi = min((int)ceilf(fx), g.w - 1);
   const float ly = fy - fly, lx = fx - flx;
-  const uint8_t* ptl = img + ((size_t)ylo * g.w + xlo) * 3;
-  const uint8_t* ptr = img + ((size_t)ylo * g.w + xhi) * 3;
-  const uint8_t* pbl = img + ((size_t)yhi * g.w + xlo) * 3;
-  const uint8_t* pbr = img + ((size_t)yhi * g.w + xhi) * 3;
+  const size_t ptl = (size_t)ylo * g.w + xlo;
+  const size_t ptr = (size_t)ylo * g.w + xhi;
+  const size_t pbl = (size_t)yhi * g.w + xlo;
+  const size_t pbr = (size_t)yhi * g.w + xhi;
   for (int c = 0; c < 3; ++c) {
-    const float tl = norm_px(ptl, c, a), tr = norm_px(ptr, c, a);
-    const float bl = norm_px(pbl, c, a), br = norm_px(pbr, c, a);
+    const float tl = norm_px<NOISE>(img, ptl, c, n, a), tr = norm_px<NOISE>(img, ptr, c, n, a);
+    const float bl = norm_px<NOISE>(img, pbl, c, n, a), br = norm_px<NOISE>(img, pbr, c, n, a);
     const float top = tl + (tr - tl) * lx;
     const float bot = bl + (br - bl) * lx;
     o[c] = top + (bot - top) * ly;
@@ -69,7 +88,126 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreprocArgs a) {
 
 void launch_preprocess(const PreprocArgs& a, hipStream_t s) {
   const int64_t total = (int64_t)a.n * a.H * a.W;
-  hipLaunchKernelGGL(preprocess_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+  if (a.noise)
+    hipLaunchKernelGGL(preprocess_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(preprocess_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+}
+
+// ------------------------------------------------------------------------------------ consistency check: flip + blur
+// cv2.GaussianBlur(im, (9, 9), 0) on uint8 (infer_model.py:779-781).  sigma 0 means 0.3 ((9 - 1) / 2 - 1) + 0.8 = 1.7; OpenCV's
+// 8-bit path filters with fixed-point taps of 8 fractional bits (getGaussianKernelBitExact + getGaussianKernelFixedPoint_ED):
+// c[i] = exp(-i^2 / (2 sigma^2)) / sum, times 256, rounded from the outside in with the rounding error carried to the next
+// tap, the centre tap taking what is left so that the taps sum to exactly 256.  That gives 4 13 30 51 60 51 30 13 4.  Row pass
+// r = sum c[i] p (exact, < 2^16), column pass s = sum c[j] r (exact, < 2^24), output (s + 32768) >> 16.  Borders: REFLECT_101
+// (BORDER_DEFAULT) with borderInterpolate's iteration for images narrower than the 4-pixel halo.  The numpy restatement
+// (tests) reproduces this bit for bit; agreement with cv2 itself is not verified here (cv2 is not a dependency).
+constexpr int AUG_TX = 64, AUG_TY = 16, AUG_R = 4;
+__device__ __forceinline__ int blur_tap(int i) {
+  return i == 0 ? 60 : (i == 1 || i == -1) ? 51 : (i == 2 || i == -2) ? 30 : (i == 3 || i == -3) ? 13 : 4;
+}
+__device__ __forceinline__ int reflect101(int p, int len) {
+  if (len == 1) return 0;
+  while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
+  return p;
+}
+
+// One block per 64 x 16 output tile of one image: the tile and its 4-pixel halo are staged in LDS once; the flip copies
+// the tile's centre mirrored, the blur filters rows then columns.  Images may differ in raw size (grid = the largest).
+__global__ __launch_bounds__(256) void augment_u8_kernel(AugArgs a) {
+  constexpr int LW = AUG_TX + 2 * AUG_R, LH = AUG_TY + 2 * AUG_R;
+  __shared__ uint8_t tile[LH][LW * 3];
+  __shared__ int rowp[LH][AUG_TX * 3];
+  const PreGeo g = a.geo[blockIdx.z];
+  const int x0 = blockIdx.x * AUG_TX, y0 = blockIdx.y * AUG_TY;
+  if (x0 >= g.w || y0 >= g.h) return;                  // (block-uniform)
+  const uint8_t* src = a.img + g.off;
+  for (int e = threadIdx.x; e < LH * LW; e += blockDim.x) {
+    const int ly = e / LW, lx = e - ly * LW;
+    const int sy = reflect101(y0 + ly - AUG_R, g.h), sx = reflect101(x0 + lx - AUG_R, g.w);
+    const uint8_t* p = src + ((size_t)sy * g.w + sx) * 3;
+    tile[ly][lx * 3 + 0] = p[0];
+    tile[ly][lx * 3 + 1] = p[1];
+    tile[ly][lx * 3 + 2] = p[2];
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < LH * AUG_TX * 3; e += blockDim.x) {
+    const int ly = e / (AUG_TX * 3), r = e - ly * (AUG_TX * 3);
+    int s = 0;
+#pragma unroll
+    for (int i = -AUG_R; i <= AUG_R; ++i) s += blur_tap(i) * (int)tile[ly][r + (AUG_R + i) * 3];
+    rowp[ly][r] = s;
+  }
+  __syncthreads();
+  uint8_t* flip = a.img + a.variant_stride + g.off;
+  uint8_t* blur = a.img + 2 * a.variant_stride + g.off;
+  for (int e = threadIdx.x; e < AUG_TY * AUG_TX * 3; e += blockDim.x) {
+    const int ly = e / (AUG_TX * 3), r = e - ly * (AUG_TX * 3);
+    const int lx = r / 3, ch = r - lx * 3;
+    const int y = y0 + ly, x = x0 + lx;
+    if (y >= g.h || x >= g.w) continue;
+    int s = 0;
+#pragma unroll
+    for (int j = -AUG_R; j <= AUG_R; ++j) s += blur_tap(j) * rowp[ly + AUG_R + j][r];
+    blur[((size_t)y * g.w + x) * 3 + ch] = (uint8_t)((s + 32768) >> 16);
+    flip[((size_t)y * g.w + (g.w - 1 - x)) * 3 + ch] = tile[ly + AUG_R][(lx + AUG_R) * 3 + ch];
+  }
+}
+
+void launch_augment_u8(const AugArgs& a, int max_h, int max_w, hipStream_t s) {
+  const dim3 grid((unsigned)((max_w + AUG_TX - 1) / AUG_TX), (unsigned)((max_h + AUG_TY - 1) / AUG_TY), (unsigned)a.n);
+  hipLaunchKernelGGL(augment_u8_kernel, grid, dim3(256), 0, s, a);
+}
+
+// ------------------------------------------------------------------------------------ consistency check: scores
+// Per original image (one block) and detection rank k (one thread), against all M rows of each variant, padded rows included
+// (infer_model.py:811-827): the flip variant's boxes are un-flipped to [y1, W - x2, y2, W - x1] in float32 (W = raw width);
+// IoU = calc_iou_np (utils_box.py:56-89): float32 coordinate differences, float64 products, union = (areaA + areaB) - inter,
+// 0 where the union is 0; cons_iou = ((max_flip + max_blur) + max_noise) / 3 in float64 (np.mean of three);
+// cons_cls = np.mean of the three variants' classes at rank k in float32 .is_integer() - the original's class is not
+// consulted (the reference's rank-wise comparison, reproduced as it is).
+__device__ __forceinline__ double iou_np(const float* a, const float* b) {
+  const float yA = fmaxf(a[0], b[0]), xA = fmaxf(a[1], b[1]);
+  const float yB = fminf(a[2], b[2]), xB = fminf(a[3], b[3]);
+  const double inter = (double)fmaxf(0.0f, xB - xA) * (double)fmaxf(0.0f, yB - yA);
+  const double areaA = (double)fabsf(a[3] - a[1]) * (double)fabsf(a[2] - a[0]);
+  const double areaB = (double)fabsf(b[3] - b[1]) * (double)fabsf(b[2] - b[0]);
+  const double uni = (areaA + areaB) - inter;
+  return uni != 0.0 ? inter / uni : 0.0;
+}
+
+__global__ __launch_bounds__(128) void consistency_kernel(ConsArgs a) {
+  __shared__ float vb[3][128][4];
+  const int i = blockIdx.x, k = threadIdx.x, M = a.M;
+  const float W = (float)a.geo[i].w;
+  for (int e = k; e < 3 * M; e += blockDim.x) {
+    const int v = e / M, j = e - v * M;
+    const float* b = a.boxes + ((size_t)(v + 1) * a.n + i) * M * a.bc + (size_t)j * a.bc;
+    if (v == 0) {
+      vb[0][j][0] = b[0]; vb[0][j][1] = W - b[3]; vb[0][j][2] = b[2]; vb[0][j][3] = W - b[1];
+    } else {
+      for (int q = 0; q < 4; ++q) vb[v][j][q] = b[q];
+    }
+  }
+  __syncthreads();
+  if (k >= M) return;
+  const float* ob = a.boxes + ((size_t)i * M + k) * a.bc;
+  const float box[4] = {ob[0], ob[1], ob[2], ob[3]};
+  double best[3];
+  for (int v = 0; v < 3; ++v) {
+    double m = iou_np(box, vb[v][0]);
+    for (int j = 1; j < M; ++j) m = fmax(m, iou_np(box, vb[v][j]));
+    best[v] = m;
+  }
+  a.iou[(size_t)i * M + k] = ((best[0] + best[1]) + best[2]) / 3.0;
+  float cls[3];
+  for (int v = 0; v < 3; ++v) cls[v] = a.classes[(((size_t)(v + 1) * a.n + i) * M + k) * a.cc];
+  const float mean = ((cls[0] + cls[1]) + cls[2]) / 3.0f;
+  a.agree[(size_t)i * M + k] = (uint8_t)(isfinite(mean) && mean == truncf(mean));
+}
+
+void launch_consistency(const ConsArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(consistency_kernel, dim3((unsigned)a.n), dim3(128), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------ aggregate + decode

@@ -114,6 +114,13 @@ struct uda_ctx {
   int stem_co = 0;             // output channels of the stem op (0: no stem op in the plan)
   float* d_images = nullptr;   // [max_images, H, W, 3]
   float* d_scales = nullptr;   // [max_images]
+  // consistency check (uda_run_consistency): images [noise_from, n_images) of the run are the noise variant of images
+  // [0, n_images - noise_from), preprocessed by the NOISE instantiation of the preprocess kernel (-1: an ordinary run)
+  int noise_from = -1;
+  std::vector<PreGeo> cons_geo;      // geometry table of the 4n images of the last consistency run
+  double* d_cons_iou = nullptr;      // [max_images, M] cons_iou of the last consistency run (lazy)
+  uint8_t* d_cons_agree = nullptr;   // [max_images, M] cons_cls
+  int cons_n = 0;                    // originals of the last consistency run (0: none)
   std::vector<float> h_scales;
   int n_images = 0;
   int sh = 0, sw = 0;
@@ -338,7 +345,7 @@ extern "C" void uda_destroy(uda_ctx_t* c) {
                   c->d_site_off, c->d_site_ch, c->d_site_rate, c->d_cboxes, c->d_cscores, c->d_clogits,
                   c->d_cclasses, c->d_ucls, c->d_ual, c->d_uep, c->d_clsmean, c->d_cand_flat, c->d_merge_keys,
                   c->d_oboxes, c->d_oscores, c->d_oclasses, c->d_ologits, c->d_ovalid, c->d_oprobs, c->d_oentropy,
-                  c->d_opacked};
+                  c->d_opacked, c->d_cons_iou, c->d_cons_agree};
   for (void* p : ptrs)
     if (p) hipFree(p);
   free_prefix_ws(c->pfx);
@@ -939,6 +946,7 @@ static int make_current(uda_ctx* c, int si) {
   HIPC(c, hipStreamWaitEvent(c->stream, sl.ev, 0));
   c->cur = si;
   c->n_images = sl.n;
+  c->noise_from = -1;
   c->have_u8 = true;
   for (int i = 0; i < sl.n; ++i) c->h_scales[i] = sl.scales[i];
   HIPC(c, hipMemcpyAsync(c->d_scales, c->h_scales.data(), sl.n * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -1012,6 +1020,7 @@ extern "C" int uda_set_images_f32(uda_ctx_t* c, const float* images, int32_t n, 
   for (int i = 0; i < n; ++i) c->h_scales[i] = image_scales ? image_scales[i] : 1.0f;
   HIPC(c, hipMemcpyAsync(c->d_scales, c->h_scales.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   c->n_images = n;
+  c->noise_from = -1;
   c->have_u8 = false;
   c->stem_from_u8 = false;
   ++c->f32_gen;
@@ -1457,7 +1466,18 @@ static int run_preprocess(uda_ctx* c) {
   a.in = sl.d_img; a.out = c->d_images; a.geo = sl.d_geo;
   a.n = c->n_images; a.H = m.image_h; a.W = m.image_w;
   for (int k = 0; k < 3; ++k) { a.mean[k] = m.mean_rgb[k]; a.stdv[k] = m.stddev_rgb[k]; }
-  launch_preprocess(a, c->stream);
+  if (c->noise_from >= 0) {
+    // consistency run: the originals, flips and blurs are slot images [0, noise_from); the noise variant reads the originals
+    PreprocArgs b = a;
+    a.n = c->noise_from;
+    b.n = c->n_images - c->noise_from;
+    b.out = c->d_images + (size_t)c->noise_from * m.image_h * m.image_w * 3;
+    b.noise = 1; b.noise_seed = c->seed; b.noise_img0 = (uint32_t)c->image_offset;
+    launch_preprocess(a, c->stream);
+    launch_preprocess(b, c->stream);
+  } else {
+    launch_preprocess(a, c->stream);
+  }
   HIPC(c, hipGetLastError());
   c->pre_valid = true;
   return 0;
@@ -1473,7 +1493,7 @@ static int run_network(uda_ctx* c, int post_mode = 0, bool chunk_post = false, h
   if (c->have_u8) {
     static const bool on = !(getenv("UDA_STEM_U8") && atoi(getenv("UDA_STEM_U8")) == 0);
     const uda_ctx::U8Slot& sl = c->u8[c->cur];
-    stem_u8 = on && c->stem_co > 0 && stem_u8_supported(c->stem_co) && c->stem_act == UDA_ACT_SWISH;
+    stem_u8 = on && c->noise_from < 0 && c->stem_co > 0 && stem_u8_supported(c->stem_co) && c->stem_act == UDA_ACT_SWISH;
     for (int i = 0; i < n && stem_u8; ++i) stem_u8 = sl.geo[i].sh == sl.geo[i].h && sl.geo[i].sw == sl.geo[i].w;
     c->pre_valid = false;
     if (!stem_u8) {
@@ -2122,6 +2142,107 @@ extern "C" int uda_run(uda_ctx_t* c, int32_t post_mode, int32_t do_post) {
   if (rc) return rc;
   if (do_post) rc = run_post(c, c->n_images, post_mode);
   return rc;
+}
+
+// ---- consistency check (reference infer_model.py:768-848, hparams_config.py:240)
+// The n staged uint8 images become a batch of 4n: the originals, their left-right flips (n..2n-1) and 9x9 Gaussian blurs
+// (2n..3n-1), written by augment_u8_kernel behind the originals in the same input slot, and their noise variants
+// (3n..4n-1), drawn inside the preprocess pass from the originals.  Variant n + N v keeps image n's raw size and scale;
+// image j draws the Philox dropout rows (offset + j) T + t, so the originals draw the masks of a plain uda_run of the same
+// n images (and the chunks only regroup images: their detections are bit-identical to it).  The whole batch goes through
+// the preprocess kernel (the noise variant is a float image, infer_model.py:790-792) and the float32 stem.
+extern "C" int uda_run_consistency(uda_ctx_t* c, int32_t post_mode) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  uda_ctx::U8Slot& sl = c->u8[c->cur];
+  if (!c->have_u8 || !sl.valid) return fail(c, "run_consistency: no uint8 batch is set");
+  const int n = sl.n;
+  if (4 * n > m.max_images)
+    return fail(c, "run_consistency: %d images and their 3 variants need max_images >= %d, the handle has %d", n, 4 * n, m.max_images);
+  const int pm = post_mode < 0 ? m.post_mode : post_mode;
+  if (pm != UDA_POST_GLOBAL && pm != UDA_POST_PER_CLASS) return fail(c, "unknown post mode %d", pm);
+  HIPC(c, hipSetDevice(c->device));
+  if (c->as[0].open || c->as[1].open) return fail(c, "run_consistency: a pipelined run (uda_run_async) is in flight - uda_collect it first");
+  size_t total = 0;
+  int max_h = 0, max_w = 0;
+  for (int i = 0; i < n; ++i) {
+    total += (size_t)sl.geo[i].h * sl.geo[i].w * 3;
+    max_h = std::max(max_h, sl.geo[i].h);
+    max_w = std::max(max_w, sl.geo[i].w);
+  }
+  // the slot holds the originals; the flips and blurs go behind them (the slot grows once, keeping its contents)
+  const size_t hdr = ((size_t)m.max_images * sizeof(PreGeo) + 255) & ~(size_t)255;
+  if (hdr + 3 * total > sl.cap) {
+    uint8_t* d = nullptr;
+    HIPC(c, hipMalloc((void**)&d, hdr + 3 * total + 16));
+    HIPC(c, hipMemcpyAsync(d, sl.d, hdr + total, hipMemcpyDeviceToDevice, c->stream));    // (the stream is ordered after the upload)
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipFree(sl.d));
+    sl.d = d; sl.cap = hdr + 3 * total;
+    sl.d_geo = (PreGeo*)sl.d;
+    sl.d_img = sl.d + hdr;
+  }
+  c->cons_geo.assign(4 * (size_t)n, PreGeo{});
+  for (int v = 0; v < 4; ++v)
+    for (int i = 0; i < n; ++i) {
+      PreGeo g = sl.geo[i];
+      if (v == 1 || v == 2) g.off += (unsigned long long)v * total;
+      c->cons_geo[(size_t)v * n + i] = g;
+      c->h_scales[(size_t)v * n + i] = sl.scales[i];
+    }
+  HIPC(c, hipMemcpyAsync(sl.d_geo + n, c->cons_geo.data() + n, 3 * (size_t)n * sizeof(PreGeo), hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(c->d_scales, c->h_scales.data(), 4 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  {
+    ProfScope ps(c, 18);
+    AugArgs a{};
+    a.img = sl.d_img; a.geo = sl.d_geo; a.variant_stride = (unsigned long long)total; a.n = n;
+    launch_augment_u8(a, max_h, max_w, c->stream);
+    HIPC(c, hipGetLastError());
+  }
+  c->n_images = 4 * n;
+  c->noise_from = 3 * n;
+  c->cons_n = 0;
+  int rc = uda_run(c, pm, 1);
+  if (!rc) rc = finish_post(c);         // range replay / prefix redo / NMS fallback: the scores read final detections
+  if (rc) return rc;
+  const size_t M = (size_t)m.max_output_size;
+  if (!c->d_cons_iou) {
+    HIPC(c, dalloc(&c->d_cons_iou, (size_t)m.max_images * M));
+    HIPC(c, dalloc(&c->d_cons_agree, (size_t)m.max_images * M));
+  }
+  ConsArgs a{};
+  a.boxes = c->d_oboxes; a.classes = c->d_oclasses; a.geo = sl.d_geo;
+  a.iou = c->d_cons_iou; a.agree = c->d_cons_agree;
+  a.n = n; a.M = (int)M; a.bc = box_cols_of(m, pm); a.cc = cls_cols_of(m, pm);
+  launch_consistency(a, c->stream);
+  HIPC(c, hipGetLastError());
+  HIPC(c, hipEventRecord(c->ev_pre_done[c->cur], c->stream));      // (it reads the slot's geometry table)
+  c->cons_n = n;
+  return 0;
+}
+
+extern "C" int uda_get_consistency(uda_ctx_t* c, double* iou, uint8_t* agree) {
+  if (!c) return 1;
+  if (c->cons_n < 1) return fail(c, "get_consistency: no consistency run (uda_run_consistency)");
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  const size_t cnt = (size_t)c->cons_n * c->model.max_output_size;
+  if (iou) HIPC(c, hipMemcpy(iou, c->d_cons_iou, cnt * sizeof(double), hipMemcpyDeviceToHost));
+  if (agree) HIPC(c, hipMemcpy(agree, c->d_cons_agree, cnt, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int uda_get_augmented_u8(uda_ctx_t* c, uint8_t* out, int64_t n_bytes) {
+  if (!c || !out) return c ? fail(c, "get_augmented_u8: NULL output") : 1;
+  if (c->cons_n < 1 || c->noise_from != 3 * c->cons_n) return fail(c, "get_augmented_u8: the current input is not that of a consistency run");
+  const uda_ctx::U8Slot& sl = c->u8[c->cur];
+  size_t total = 0;
+  for (int i = 0; i < sl.n; ++i) total += (size_t)sl.geo[i].h * sl.geo[i].w * 3;
+  if ((size_t)n_bytes != 2 * total) return fail(c, "get_augmented_u8: the flips and blurs take %zu bytes, not %lld", 2 * total, (long long)n_bytes);
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  HIPC(c, hipMemcpy(out, sl.d_img + total, 2 * total, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // ---- pipelined runs

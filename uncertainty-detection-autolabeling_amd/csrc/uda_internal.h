@@ -347,8 +347,29 @@ struct PreprocArgs {
   const PreGeo* geo;   // [n] (device)
   int n, H, W;
   float mean[3], stdv[3];
+  int noise;           // 1: the consistency check's noise variant (raw + sqrt(0.5) N(0, 1) in float64, kernels_post.hip raw_px)
+  uint64_t noise_seed; //   Philox key of the draws (the run's dropout seed)
+  uint32_t noise_img0; //   image index of image 0 in the counter (the dropout image offset)
 };
 void launch_preprocess(const PreprocArgs& a, hipStream_t s);
+
+// consistency check (reference infer_model.py:768-848): flip and blur of n staged uint8 images, written behind them
+struct AugArgs {
+  uint8_t* img;                     // packed raw images (image i at img + geo[i].off); flips at + variant_stride, blurs at + 2 variant_stride
+  const PreGeo* geo;                // [n] (device)
+  unsigned long long variant_stride;  // bytes of the n originals
+  int n;
+};
+void launch_augment_u8(const AugArgs& a, int max_h, int max_w, hipStream_t s);
+struct ConsArgs {
+  const float* boxes;    // [4n, M, bc] detections: originals, then the flip, blur and noise variants
+  const float* classes;  // [4n, M, cc] (column 0: class id)
+  const PreGeo* geo;     // [n] raw sizes of the originals (the flip is undone with the raw width)
+  double* iou;           // [n, M] cons_iou
+  uint8_t* agree;        // [n, M] cons_cls
+  int n, M, bc, cc;
+};
+void launch_consistency(const ConsArgs& a, hipStream_t s);
 
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]

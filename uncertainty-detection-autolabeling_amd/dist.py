@@ -279,6 +279,9 @@ class SampleShardedDriver:
     def set_dropout_seed(self, seed):
         self.net.set_dropout_seed(seed)
 
+    def serve_consistency(self, images, *args, **kwargs):
+        raise NotImplementedError("the consistency check (consistency_ssl) is served by a single ServingDriver")
+
     def close(self):
         self.net.close()
         self.post.close()

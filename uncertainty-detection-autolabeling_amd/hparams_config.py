@@ -192,6 +192,7 @@ def default_detection_configs():
     h.calibrate_regression = True
     h.calib_method_box = "iso_perclscoo"
     h.infer_draw_uncert = True
+    h.consistency_ssl = False           # flip / blur / noise agreement columns in prediction_data (hparams_config.py:240)
     h.early_stopping_patience = 0
 
     # --- training-only keys that the shipped YAMLs set (kept so they load) ---

@@ -70,12 +70,15 @@ class ServingDriver:
             raise ValueError("nms_configs.pyfunc=True selects the numpy NMS path (nms_np), "
                              "which is dead in the reference (postprocess.py:806) and not served here")
         self._cap = int(batch_size or 1)              # images one uda_run holds (batch_size None/0 = the reference's dynamic batch)
+        # consistency_ssl (infer_model.py:768-848): serve_consistency runs each image with its flip, blur and noise variants, so
+        # the handle is planned for 4 x batch_size images (the chunking bounds the arena; head outputs and candidates scale)
+        self._plan_images = self._cap * (4 if self.params.get("consistency_ssl") else 1)
 
         if weights is None and not post_only:
             weights = weights_mod.resolve_weights(weights_path, self.params)
         self.weights = weights
         if chunk_images is None:
-            chunk_images = min(self._cap, int(self.params.get("uda_chunk_images", 16)))
+            chunk_images = min(self._plan_images, int(self.params.get("uda_chunk_images", 16)))
         # `uda_pw_scheme` in model_params (f16x2 | bf16x3 | bf16x2 | f32 | f16): the split scheme of THIS handle's 1x1 contractions.  The
         # planner and uda_create both read UDA_PW_SCHEME when they run; the key sets it for exactly that long (a
         # per-handle choice instead of a process-wide environment variable).
@@ -107,7 +110,7 @@ class ServingDriver:
         self._run_id = 0                              # bumped by every call that rewrites the resident head outputs
 
     def _create(self, weights, chunk_images, post_only, post_mode, device):
-        self.plan = plan_mod.Plan(self.params, weights, chunk_images=chunk_images, max_images=self._cap, post_only=post_only)
+        self.plan = plan_mod.Plan(self.params, weights, chunk_images=chunk_images, max_images=self._plan_images, post_only=post_only)
         if self.plan.unknown_keys:
             # not one of hparams_config's keys and not a `uda_*` knob: nothing here reads it (plan.MODEL_PARAM_HANDLING)
             logging.warning("model_params keys the HIP path does not know (ignored): %s", ", ".join(self.plan.unknown_keys))
@@ -367,6 +370,58 @@ class ServingDriver:
         self._last_n = n
         return self._collect(n, mode)
 
+    def serve_consistency(self, image_arrays, post_mode=None):
+        """The augmentation-consistency check of `Infer.iterate_infer` with `consistency_ssl` (infer_model.py:768-848) in ONE
+        device run: uint8 images (array or ragged list, at most batch_size) -> (detections, cons_iou [N, M] float64,
+        cons_cls [N, M] bool).
+
+        The device builds each image's left-right flip, 9x9 Gaussian blur and N(0, 0.5) noise variant and serves the 4N images
+        as one batch (`uda_run_consistency`); `detections` is exactly what `serve()` returns for the originals with the same
+        dropout seed.  cons_iou[n, k]: mean over the variants of the best IoU of detection k with any of the variant's M rows;
+        cons_cls[n, k]: the variants' classes at rank k have an integer mean (the reference's rank-wise test).  The handle then
+        holds all 4N images' results, originals first: `class_probs`, the calibrators and `preprocessed` take / return 4N
+        rows, and `last_consistency_variants` has the variants' own detections."""
+        if not self.params.get("consistency_ssl"):
+            raise ValueError("serve_consistency needs a driver created with model_params consistency_ssl=True "
+                             "(its handle is planned for the 3 variants of every image)")
+        mode = self._mode(post_mode)
+        n = self._feed(image_arrays)
+        self._next_seed()
+        self._run_id += 1
+        self._ck(self._lib.uda_run_consistency(self._h, mode), "uda_run_consistency")
+        self._last_n = 4 * n
+        det = self._collect(4 * n, mode)
+        iou = np.empty((n, self.M), np.float64)
+        agree = np.empty((n, self.M), np.uint8)
+        self._ck(self._lib.uda_get_consistency(self._h, _ptr(iou), _ptr(agree)), "uda_get_consistency")
+        self._cons_variants = {name: tuple(a[(v + 1) * n:(v + 2) * n].copy() for a in det)
+                               for v, name in enumerate(("flip", "blur", "noise"))}
+        return tuple(a[:n].copy() for a in det), iou, agree.astype(bool)
+
+    def last_consistency_variants(self):
+        """{"flip", "blur", "noise"}: the detection tuples (as `serve` returns them) of the last `serve_consistency`'s
+        variants; the flip's boxes are in the flipped image's coordinates."""
+        if not hasattr(self, "_cons_variants"):
+            raise ValueError("no serve_consistency run yet")
+        return self._cons_variants
+
+    def consistency_images(self, image_arrays):
+        """(flips, blurs): the device-built uint8 variants of the current consistency input, one [h, w, 3] array per image;
+        `image_arrays` is that input (for the raw sizes)."""
+        shapes = [np.shape(x) for x in image_arrays]
+        total = sum(int(np.prod(sh)) for sh in shapes)
+        buf = np.empty((2 * total,), np.uint8)
+        self._ck(self._lib.uda_get_augmented_u8(self._h, _ptr(buf), buf.size), "uda_get_augmented_u8")
+        out, off = [], 0
+        for _ in range(2):
+            imgs = []
+            for sh in shapes:
+                sz = int(np.prod(sh))
+                imgs.append(buf[off:off + sz].reshape(sh))
+                off += sz
+            out.append(imgs)
+        return out[0], out[1]
+
     def serve_resident(self, image_arrays, post_mode=None):
         """serve() without the download: the detections stay in the handle (`detections_device`, calibrators,
         `class_probs`) - what the multi-GPU layer runs before its device-resident gather.  Returns the image count."""
@@ -584,7 +639,7 @@ class ServingDriver:
 
     def preprocessed_scales(self, n):
         """(None, image scales [n]) of the last uint8 batch (host-side copy kept by the handle)."""
-        scales = np.empty((max(n, self._cap),), np.float32)
+        scales = np.empty((max(n, self._plan_images),), np.float32)
         self._ck(self._lib.uda_get_preprocessed(self._h, None, _ptr(scales)), "uda_get_preprocessed")
         return None, scales[:n]
 
@@ -842,6 +897,9 @@ class EnsembleDriver:
         s = np.ascontiguousarray(scales, dtype=np.float32)
         self.post._ck(lib.uda_postprocess_heads(self.post._h, n, _ptr(s), mode), "uda_postprocess_heads")
         return self.post._collect(n, mode)
+
+    def serve_consistency(self, image_arrays, post_mode=None):
+        raise NotImplementedError("the consistency check (consistency_ssl) is served by a single ServingDriver")
 
     def close(self):
         for d in self.members + [self.post]:

@@ -205,6 +205,8 @@ MODEL_PARAM_HANDLING = {
     "calibrate_classification": "consumed by calibration.py (above the driver)", "calib_method_class": "consumed by calibration.py",
     "calibrate_regression": "consumed by calibration.py", "calib_method_box": "consumed by calibration.py",
     "infer_draw_uncert": "consumed by visualize", "label_map": "consumed by infer_lib / writers",
+    "consistency_ssl": "consumed: infer_lib plans 4 x batch_size images for serve_consistency (flip / blur / noise "
+                       "variants, infer_model.py:768-848); writers.predict_to_file writes cons_iou / cons_cls",
     # --- training-only keys the shipped YAMLs set
     "assign_gt_box": "inert: validation matching above the driver", "early_stopping_patience": "inert: training",
     "count_classes": "inert: training", "boxloss_type": "inert: training", "save_freq": "inert: training",

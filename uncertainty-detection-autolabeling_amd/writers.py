@@ -40,13 +40,15 @@ def add_array_dict(data_dict, source_array, target_key, select_index):
 
 
 def prediction_records(unpacked, image_names, min_score, calibrated=None, calibrate_classification=True,
-                       calibrate_regression=True):
+                       calibrate_regression=True, consistency=None):
     """Records of `ServingDriver.serve_unpacked` output for a batch, in the reference's key order
     (infer_model.py:836-960).
 
     calibrated: optional dict name -> [N, M, ...] arrays written behind the uncalibrated column they refine:
     "<method>_probab" / "<method>_entropy" / "<method>_mcclass" (`ClassCalibrator`), "<method>_albox" /
-    "<method>_mcbox" (`BoxCalibrator`); a missing name is skipped like the reference's empty array."""
+    "<method>_mcbox" (`BoxCalibrator`); a missing name is skipped like the reference's empty array.
+    consistency: optional (cons_iou [N, M], cons_cls [N, M]) of `ServingDriver.serve_consistency`, written right after
+    "class" as the reference does under consistency_ssl (:842-844): a float64 and a python bool."""
     recs = []
     cal = calibrated or {}
     boxes, scores, classes = unpacked["boxes"], unpacked["scores"], unpacked["classes"]
@@ -64,6 +66,9 @@ def prediction_records(unpacked, image_names, min_score, calibrated=None, calibr
             d["det_score"] = _f32(scores[i][sel])
             d["bbox"] = _f32_list(boxes[i][sel])
             d["class"] = _f32(classes[i][sel])
+            if consistency is not None:
+                d["cons_iou"] = float(consistency[0][i][sel])
+                d["cons_cls"] = bool(consistency[1][i][sel])
             if unpacked.get("logits") is not None:
                 add_array_dict(d, unpacked["logits"][i], "logits", sel)
                 add_array_dict(d, unpacked["entropy"][i], "entropy", sel)
@@ -100,35 +105,43 @@ def predict_to_file(driver, batches, names, path, min_score, box_calibrator=None
     lists of images of different raw sizes): serve (feed of the next batch hidden under this one) -> unpack + softmax /
     entropy (device) -> calibrated box / class uncertainties (device, `calibration.BoxCalibrator` / `ClassCalibrator`)
     -> `prediction_data.txt` lines appended to `path`.  `names`: one list of image names per batch.  Returns the number
-    of records written."""
+    of records written.  With `driver.params["consistency_ssl"]` every batch goes through `serve_consistency` (one device
+    run of the images and their flip / blur / noise variants, not pipelined) and the records carry cons_iou / cons_cls
+    (infer_model.py:768-848)."""
     from . import postprocess as pp
     names = list(names)
     state = {"i": 0, "written": 0}
 
-    def per_batch(det):
+    def per_batch(det, consistency=None):
         n = det[0].shape[0]
+        rows = 4 * n if consistency is not None else n       # images the handle holds: the variants follow the originals
         probs = ent = None
         if driver.params["enable_softmax"]:
-            probs, ent = driver.class_probs(n)
+            probs, ent = (a[:n] for a in driver.class_probs(rows))
         un = pp.unpack_detections(driver.params, det, probs, ent)
         cal = {}
         if box_calibrator is not None:
             for m in box_methods:
                 for which in ("albox", "mcbox"):
                     if un.get(which) is not None:
-                        cal["%s_%s" % (m, which)] = box_calibrator.calibrate_boxuncert(n, which, m)
+                        cal["%s_%s" % (m, which)] = box_calibrator.calibrate_boxuncert(rows, which, m)[:n]
         if class_calibrator is not None and un.get("logits") is not None:
             for m in class_methods:
-                r = class_calibrator.perform_class_calib(n, m)
-                cal[m + "_entropy"], cal[m + "_probab"] = r[0], r[1]
+                r = class_calibrator.perform_class_calib(rows, m)
+                cal[m + "_entropy"], cal[m + "_probab"] = r[0][:n], r[1][:n]
                 if len(r) > 2:
-                    cal[m + "_mcclass"] = r[2]
-        recs = prediction_records(un, names[state["i"]], min_score, cal)
+                    cal[m + "_mcclass"] = r[2][:n]
+        recs = prediction_records(un, names[state["i"]], min_score, cal, consistency=consistency)
         write_prediction_data(path, recs)
         state["i"] += 1
         state["written"] += len(recs)
         return len(recs)
 
+    if driver.params.get("consistency_ssl"):
+        for batch in batches:
+            det, cons_iou, cons_cls = driver.serve_consistency(batch)
+            per_batch(det, (cons_iou, cons_cls))
+        return state["written"]
     for _ in driver.serve_stream(batches, while_resident=per_batch):
         pass
     return state["written"]
