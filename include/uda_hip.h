@@ -16,6 +16,8 @@
  *                            (infer_lib.py:345-350,450-457)
  *   uda_postprocess_heads <- ServingDriver._postprocess = postprocess_global on given head outputs
  *                            (infer_lib.py:263-267)
+ *   uda_assign_ground_truth <- the gt_box_assigner walk of the validate / calibrate modes over the ground-truth rows
+ *                            (utils_extra.py:44-64; validate_model.py:314-470, calibrate_model.py:133-190)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -290,6 +292,42 @@ int uda_detections_device(uda_ctx_t* ctx, int32_t rows, int32_t with_logits, voi
  * infer_model.py:585-600, utils_class.py:36-41), on the device: probs [n, M, num_classes] = stable softmax of the
  * selected rows' mean logits, entropy [n, M] = -sum p * log2(max(p, 1e-7)).  Global post-process only. */
 int uda_get_class_probs(uda_ctx_t* ctx, float* probs, float* entropy);
+
+/* Ground-truth assignment: what the reference's validate and calibrate modes do on the host right after serve() - give every
+ * ground-truth (GT) box the detection that belongs to it (utils_extra.gt_box_assigner, utils_extra.py:44-64; callers
+ * validate_model.py:314-339, calibrate_model.py:133-147) and keep that detection's row of every output column - done on the
+ * detections RESIDENT in the handle after a global post-process (uda_run / uda_collect, the originals and variants of
+ * uda_run_consistency, an ensemble's uda_postprocess_heads).
+ *   uda_set_ground_truth     boxes [n, G, 4] (y1, x1, y2, x2 in raw-image pixels, the coordinates of the detections) and classes
+ *                            [n, G], float32, padded with -1 rows (inspector.py:147-160); values must be finite (the Python
+ *                            layer checks).  The handle's GT buffers hold max_images x G rows and grow only when G grows.
+ *   uda_assign_ground_truth  method 0 "IoU": argmax_k calc_iou_np(gt, box_k) (utils_box.py:56-89; float32 differences, float64
+ *                            products) over all M rows, padded ones included; 1 "MSE": argmin_k mean((gt - box_k)^2) in float32,
+ *                            summed ((d0 + d1) + d2) + d3; 2: the GT row's own rank (the reference's else branch; a kept row
+ *                            >= M is an error).  Ties go to the lowest rank, as np.argmax / np.argmin do.
+ *                            keep 0 "validate": rows with class > 0 (validate_model.py:314); 1 "calibrate": rows < min(G, M) with
+ *                            class >= 0 (calibrate_model.py:133-135).  Forces the deferred fix-ups every reader of detections
+ *                            forces.  Refuses: no GT set, no global post-process yet, a per-class run, n different from the
+ *                            run's image count, a pipelined run still in flight.
+ *   uda_get_assignment       det_index [n, G] int32 (-1: row not kept), iou [n, G] float64 = calc_iou_np(gt, matched box) whatever
+ *                            the method (0: not kept), count [n] int32 kept rows per image; any pointer may be NULL.
+ *   uda_get_assigned_rows    the matched rows, K = sum(count) in (image, GT row) order - the order the reference appends in -
+ *                            as one float32 table [K, cols]: box columns (box_cols of uda_detection_cols) | score | class
+ *                            columns (cls_cols) | and with enable_softmax: logits (num_classes) | probab (num_classes) | entropy
+ *                            (the buffers of uda_get_class_probs).  Values are copied unchanged: np.nan_to_num of the
+ *                            uncertainty columns (validate_model.py:176-196) is the caller's (infer_lib does it).
+ *                            n_floats must equal K * cols.
+ *   uda_assigned_row_cols    cols of that table. */
+int uda_set_ground_truth(uda_ctx_t* ctx, const float* boxes, const float* classes, int32_t n, int32_t G);
+int uda_assign_ground_truth(uda_ctx_t* ctx, int32_t method, int32_t keep);
+int uda_get_assignment(uda_ctx_t* ctx, int32_t* det_index, double* iou, int32_t* count);
+int uda_get_assigned_rows(uda_ctx_t* ctx, float* rows, int64_t n_floats);
+int uda_assigned_row_cols(const uda_ctx_t* ctx, int32_t* cols);
+/* The same assignment without a handle, in the manner of uda_nms_np: host arrays det_boxes [n, M, 4], gt_boxes [n, G, 4],
+ * gt_classes [n, G] in, the same kernel, det_index / iou [n, G] and count [n] out - gt_box_assigner for callers that hold
+ * detections of their own.  M <= 4096, G <= 16384. */
+int uda_assign_gt_np(int32_t device, const float* det_boxes, const float* gt_boxes, const float* gt_classes, int32_t n,
+                     int32_t M, int32_t G, int32_t method, int32_t keep, int32_t* det_index, double* iou, int32_t* count);
 
 /* serve = set_images_u8 + run + get_detections */
 int uda_serve(uda_ctx_t* ctx, const uint8_t* images, int32_t n, int32_t h, int32_t w,

@@ -147,3 +147,33 @@ class ClassCalibrator:
             r = res[m]
             out += [r[1], r[2], r[0]] if with_unc else [r[1], r[0]]
         return tuple(out)
+
+
+def gather_detections(driver, batches, gts):
+    """`Calibrate.gather_detections` (calibrate_model.py:88-190) followed by the `ious > 0` filter of `calibrate_regclas`
+    (:196-211): serve every batch, give each ground-truth row < min(G, M) with class >= 0 its detection on the device
+    (`ServingDriver.assign_ground_truth(keep="calibrate")`, method model_params["assign_gt_box"]), keep the pairs that
+    overlap.  gts: per batch (gt_boxes [n, G, 4], gt_classes [n, G]).  Returns the arrays the reference's fits take:
+    gt_classes (class - 1, :137), logits, mcclass, gt_boxes, boxes, albox, mcbox (None where the configuration has none),
+    plus scores, classes and iou of the kept pairs.  Fitting the calibrators is not part of this package."""
+    gts = list(gts)
+    keys = ("gt_classes", "logits", "mcclass", "gt_boxes", "boxes", "albox", "mcbox", "scores", "classes")
+    acc = {k: [] for k in keys + ("iou",)}
+    state = {"i": 0}
+
+    def per_batch(det):
+        gb, gc = gts[state["i"]]
+        asg = driver.assign_ground_truth(gb, gc, keep="calibrate")
+        for k in keys:
+            if asg[k] is not None:
+                acc[k].append(asg[k])
+        acc["iou"].append(asg["iou"][asg["image"], asg["gt_row"]])
+        state["i"] += 1
+
+    for _ in driver.serve_stream(batches, while_resident=per_batch):
+        pass
+    if not acc["iou"]:
+        raise ValueError("gather_detections: no batches")
+    out = {k: (np.concatenate(v) if v else None) for k, v in acc.items()}
+    sel = out["iou"] > 0.0
+    return {k: (None if v is None else v[sel]) for k, v in out.items()}

@@ -25,6 +25,8 @@ DECODE_PLAIN, DECODE_LNORM, DECODE_FALSEDEC, DECODE_SAMPLE = 0, 1, 2, 3
 POST_GLOBAL, POST_PER_CLASS = 0, 1
 CALIB_TS_ALL, CALIB_TS_PERCOO, CALIB_ISO_ALL, CALIB_ISO_PERCOO, CALIB_ISO_PERCLSCOO = 0, 1, 2, 3, 4
 CLS_TS, CLS_ISO_ALL, CLS_ISO_PERCLS = 0, 1, 2
+ASSIGN_IOU, ASSIGN_MSE, ASSIGN_RANK = 0, 1, 2
+ASSIGN_KEEP_VALIDATE, ASSIGN_KEEP_CALIBRATE = 0, 1
 PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS = 16, 17, 18
 
 
@@ -103,6 +105,12 @@ _SIGNATURES = {
     "uda_detection_cols": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "uda_detections_device": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int32)]),
     "uda_get_class_probs": (C.c_int, [_P, _P, _P]),
+    "uda_set_ground_truth": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
+    "uda_assign_ground_truth": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "uda_get_assignment": (C.c_int, [_P, _P, _P, _P]),
+    "uda_get_assigned_rows": (C.c_int, [_P, _P, C.c_int64]),
+    "uda_assigned_row_cols": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "uda_assign_gt_np": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "uda_calibrate_box": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "uda_calibrate_class": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, _P]),
     "uda_serve": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),

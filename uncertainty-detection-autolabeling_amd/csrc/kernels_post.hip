@@ -8,6 +8,8 @@
 //   augment_u8_kernel  flip + 9x9 Gaussian blur of the staged uint8 images (consistency check, infer_model.py:775-783)
 //   consistency_kernel IoU / class agreement of the originals' detections with the variants' (infer_model.py:768-848,
 //                      utils_box.py:56-89)
+//   assign_gt_kernel   the detection that belongs to each ground-truth box (utils_extra.py:44-64, validate_model.py:314-339,
+//                      calibrate_model.py:133-147); gather_assigned_kernel packs the matched rows of every output column
 //   aggregate_kernel   MC mean / population std of the class logits, argmax + sigmoid,
 //                      per-sample anchor decode (plain f32 or variance-propagating f64),
 //                      mean / std over samples of the decoded corners, mean of decoded sigma
@@ -208,6 +210,138 @@ __global__ __launch_bounds__(128) void consistency_kernel(ConsArgs a) {
 
 void launch_consistency(const ConsArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(consistency_kernel, dim3((unsigned)a.n), dim3(128), 0, s, a);
+}
+
+// ------------------------------------------------------------------------------------ ground-truth assignment
+// gt_box_assigner (utils_extra.py:44-64) for every kept ground-truth row of every image.  One block per image; the image's M
+// detection boxes are staged in LDS once; a wave owns GT rows wave, wave + waves, ... and its lanes stride over the M ranks.
+//   IoU  argmax_k calc_iou_np(gt, box_k) (iou_np above), all M rows, padded ones included
+//   MSE  argmin_k np.mean(np.square(gt - box_k)) in float32: differences, squares, ((s0 + s1) + s2) + s3 (numpy's order for a
+//        4-element inner axis), times 0.25f (= / 4 exactly); no contraction in this file
+//   else rank i itself (the reference's else branch); a kept row i >= M raises *err
+// np.argmax / np.argmin return the first occurrence: a candidate replaces the best one only when its key is strictly better, or
+// equal with a lower rank - in the lane's own sweep and in every step of the wave reduction alike, so the winner is the
+// lexicographic best of (key, rank) however the ranks were dealt to lanes.  This decides real cases: padded slots carry row
+// 0's box, and a GT box that overlaps nothing has IoU 0 with every row.
+// Kept rows: ASSIGN_KEEP_VALIDATE class > 0 (validate_model.py:314); ASSIGN_KEEP_CALIBRATE row < min(G, M) and class >= 0
+// (calibrate_model.py:133-135).  Outputs: det_index (-1: not kept), iou = calc_iou_np(gt, matched box) whatever the method
+// (0: not kept), count = kept rows of the image.
+__device__ __forceinline__ bool gt_row_kept(float cls, int g, int M, int keep) {
+  return keep == ASSIGN_KEEP_CALIBRATE ? (g < M && cls >= 0.0f) : cls > 0.0f;
+}
+
+__device__ __forceinline__ float mse_np(const float* a, const float* b) {
+  const float d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2], d3 = a[3] - b[3];
+  return (((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3) * 0.25f;
+}
+
+__global__ __launch_bounds__(256) void assign_gt_kernel(AssignArgs a) {
+  extern __shared__ float det[];           // [M][4]
+  __shared__ int kept_rows;
+  const int i = blockIdx.x, M = a.M, G = a.G;
+  if (threadIdx.x == 0) kept_rows = 0;
+  for (int e = threadIdx.x; e < M * 4; e += blockDim.x) det[e] = a.det_boxes[((size_t)i * M + (e >> 2)) * a.det_stride + (e & 3)];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  int mine = 0;
+  for (int g = wave; g < G; g += waves) {                 // (wave-uniform: the shuffles below see all 64 lanes)
+    const size_t row = (size_t)i * G + g;
+    const float* gp = a.gt_boxes + row * 4;
+    const float gt[4] = {gp[0], gp[1], gp[2], gp[3]};
+    if (!gt_row_kept(a.gt_classes[row], g, M, a.keep)) {
+      if (lane == 0) { a.det_index[row] = -1; a.iou[row] = 0.0; }
+      continue;
+    }
+    int best = 0x7fffffff;
+    if (a.method == ASSIGN_IOU) {
+      double key = -1.0;                                   // below every IoU
+      for (int k = lane; k < M; k += 64) {
+        const double v = iou_np(gt, det + k * 4);
+        if (v > key) { key = v; best = k; }               // (k ascends: an equal key never replaces a lower rank)
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        const double ok = __shfl_xor(key, o);
+        const int ob = __shfl_xor(best, o);
+        if (ok > key || (ok == key && ob < best)) { key = ok; best = ob; }
+      }
+    } else if (a.method == ASSIGN_MSE) {
+      float key = __builtin_inff();
+      for (int k = lane; k < M; k += 64) {
+        const float v = mse_np(gt, det + k * 4);
+        if (v < key || best == 0x7fffffff) { key = v; best = k; }
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ok = __shfl_xor(key, o);
+        const int ob = __shfl_xor(best, o);
+        if (ob != 0x7fffffff && (best == 0x7fffffff || ok < key || (ok == key && ob < best))) { key = ok; best = ob; }
+      }
+    } else {
+      best = g;
+    }
+    if (lane == 0) {
+      if (best >= M) {                                     // rank branch beyond the detections (or M == 0)
+        if (a.method != ASSIGN_IOU && a.method != ASSIGN_MSE) *a.err = 1;
+        best = 0;
+      }
+      a.det_index[row] = best;
+      a.iou[row] = M > 0 ? iou_np(gt, det + best * 4) : 0.0;
+      ++mine;
+    }
+  }
+  if (lane == 0 && mine) atomicAdd(&kept_rows, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) a.count[i] = kept_rows;
+}
+
+void launch_assign_gt(const AssignArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(assign_gt_kernel, dim3((unsigned)a.n), dim3(256), (size_t)a.M * 4 * sizeof(float), s, a);
+}
+
+// The matched rows as one compact float32 table, K = sum(count) rows in (image, GT row) order - the order the reference
+// appends in (validate_model.py:314-470).  Row = the matched detection's box columns (box 4, then aleatoric / MC std as the
+// configuration has them) | score | class columns (id, then the MC std of the logits) | logits C | probab C | entropy (the
+// last three when the handle has logits).  The values are copied as they are: the reference's nan_to_num of the uncertainty
+// columns (validate_model.py:176-196) is done by the host that splits the table (infer_lib.split_assigned_rows).
+// One block per image: its row offset is the exclusive scan of count (n is at most a few dozen), the kept rows are ranked by
+// the first wave with ballots.
+__global__ __launch_bounds__(256) void gather_assigned_kernel(AssignRowsArgs a) {
+  extern __shared__ int src_g[];           // [G] GT row of the image's r-th kept row
+  __shared__ int row0;
+  const int i = blockIdx.x, G = a.G, M = a.M;
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int j = 0; j < i; ++j) s += a.count[j];
+    row0 = s;
+  }
+  if (threadIdx.x < 64) {
+    int run = 0;
+    for (int base = 0; base < G; base += 64) {            // (wave-uniform trip count)
+      const int g = base + (int)threadIdx.x;
+      const bool kept = g < G && a.det_index[(size_t)i * G + g] >= 0;
+      const unsigned long long m = __ballot(kept);
+      if (kept) src_g[run + __popcll(m & ((1ull << threadIdx.x) - 1ull))] = g;
+      run += __popcll(m);
+    }
+  }
+  __syncthreads();
+  const int cnt = a.count[i], W = a.cols;
+  const int sc0 = a.bc, cl0 = sc0 + 1, lg0 = cl0 + a.cc, pr0 = lg0 + a.C, en0 = pr0 + a.C;
+  for (int e = threadIdx.x; e < cnt * W; e += blockDim.x) {
+    const int r = e / W, col = e - r * W;
+    const size_t d = (size_t)i * M + a.det_index[(size_t)i * G + src_g[r]];
+    float v;
+    if (col < sc0) v = a.boxes[d * a.bc + col];
+    else if (col < cl0) v = a.scores[d];
+    else if (col < lg0) v = a.classes[d * a.cc + (col - cl0)];
+    else if (col < pr0) v = a.logits[d * a.C + (col - lg0)];
+    else if (col < en0) v = a.probs[d * a.C + (col - pr0)];
+    else v = a.entropy[d];
+    a.rows[((size_t)row0 + r) * W + col] = v;
+  }
+}
+
+void launch_gather_assigned(const AssignRowsArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(gather_assigned_kernel, dim3((unsigned)a.n), dim3(256), (size_t)(a.G > 0 ? a.G : 1) * sizeof(int), s, a);
 }
 
 // ------------------------------------------------------------------------------------ aggregate + decode

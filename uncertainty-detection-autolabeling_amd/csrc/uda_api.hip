@@ -185,6 +185,20 @@ struct uda_ctx {
   float *d_oprobs = nullptr, *d_oentropy = nullptr;   // stable softmax / entropy of the selected rows (lazy)
   float* d_opacked = nullptr;                        // packed detection records for the multi-GPU gather (lazy, uda_detections_device)
   int32_t* d_ovalid = nullptr;
+  // ground-truth assignment (uda_set_ground_truth / uda_assign_ground_truth): buffers for max_images x gt_cap GT rows, grown when a
+  // call brings more rows per image; nothing is allocated per call in the steady state
+  float *d_gt_boxes = nullptr, *d_gt_classes = nullptr, *h_gt = nullptr;   // h_gt: pinned staging [max_images, gt_cap, 5]
+  hipEvent_t gt_ev = nullptr;        // the upload out of h_gt has been consumed
+  // results of an assignment of n images x G rows, packed so that ONE copy brings them to the host:
+  // iou [n G] float64 | det_index [n G] int32 | count [n] int32 | error flag int32 (the four pointers point into d_asg_pack)
+  char* d_asg_pack = nullptr;
+  int32_t *d_asg_index = nullptr, *d_asg_count = nullptr, *d_asg_err = nullptr;
+  double* d_asg_iou = nullptr;
+  std::vector<char> h_asg;           // host copy of the pack (filled by the first reader of an assignment)
+  float* d_asg_rows = nullptr;       // [max_images * gt_cap, assigned_row_cols]
+  int gt_cap = 0, gt_n = 0, gt_G = 0; // rows per image the buffers hold; images / rows per image of the GT that is set (0: none)
+  int asg_n = 0, asg_G = 0;          // images / rows per image of the last assignment (0: none)
+  int64_t asg_rows = -1;             // sum(count) of the last assignment once the host has seen it
   int last_post_mode = 0;
   int last_n = 0;
   int last_chunk_i0 = 0, last_chunk_n = 0;
@@ -345,7 +359,10 @@ extern "C" void uda_destroy(uda_ctx_t* c) {
                   c->d_site_off, c->d_site_ch, c->d_site_rate, c->d_cboxes, c->d_cscores, c->d_clogits,
                   c->d_cclasses, c->d_ucls, c->d_ual, c->d_uep, c->d_clsmean, c->d_cand_flat, c->d_merge_keys,
                   c->d_oboxes, c->d_oscores, c->d_oclasses, c->d_ologits, c->d_ovalid, c->d_oprobs, c->d_oentropy,
-                  c->d_opacked, c->d_cons_iou, c->d_cons_agree};
+                  c->d_opacked, c->d_cons_iou, c->d_cons_agree, c->d_gt_boxes, c->d_gt_classes, c->d_asg_pack,
+                  c->d_asg_rows};
+  if (c->h_gt) hipHostFree(c->h_gt);
+  if (c->gt_ev) hipEventDestroy(c->gt_ev);
   for (void* p : ptrs)
     if (p) hipFree(p);
   free_prefix_ws(c->pfx);
@@ -2575,6 +2592,192 @@ extern "C" int uda_get_class_probs(uda_ctx_t* c, float* probs, float* entropy) {
   HIPC(c, hipGetLastError());
   HIPC(c, hipMemcpy(probs, c->d_oprobs, n * M * C * sizeof(float), hipMemcpyDeviceToHost));
   HIPC(c, hipMemcpy(entropy, c->d_oentropy, n * M * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- ground-truth assignment (reference utils_extra.py:44-64; validate_model.py:314-339, calibrate_model.py:133-147)
+// Width of a matched row: every column the global post-process produced, then what uda_get_class_probs adds.
+static int assigned_row_cols_of(const uda_model_t& m) {
+  return box_cols_of(m, UDA_POST_GLOBAL) + 1 + cls_cols_of(m, UDA_POST_GLOBAL) + (m.enable_softmax ? 2 * m.num_classes + 1 : 0);
+}
+// LDS of the two kernels: M boxes of 16 bytes, G row numbers of 4 bytes, each inside the 64 KiB a block may ask for
+static const int kAssignMaxM = 4096, kAssignMaxG = 16384;
+
+extern "C" int uda_assigned_row_cols(const uda_ctx_t* c, int32_t* cols) {
+  if (!c || !cols) return 1;
+  *cols = assigned_row_cols_of(c->model);
+  return 0;
+}
+
+extern "C" int uda_set_ground_truth(uda_ctx_t* c, const float* boxes, const float* classes, int32_t n, int32_t G) {
+  if (!c || !boxes || !classes) return c ? fail(c, "set_ground_truth: NULL argument") : 1;
+  const uda_model_t& m = c->model;
+  if (n < 1 || n > m.max_images) return fail(c, "set_ground_truth: %d images, the handle holds 1..%d", n, m.max_images);
+  if (G < 0 || G > kAssignMaxG) return fail(c, "set_ground_truth: %d ground-truth rows per image, at most %d", G, kAssignMaxG);
+  HIPC(c, hipSetDevice(c->device));
+  if (!c->gt_ev) HIPC(c, hipEventCreateWithFlags(&c->gt_ev, hipEventDisableTiming));
+  else HIPC(c, hipEventSynchronize(c->gt_ev));          // the previous upload has left the staging buffer
+  if (G > c->gt_cap || !c->d_gt_boxes) {
+    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffers)
+    void* old[] = {c->d_gt_boxes, c->d_gt_classes, c->d_asg_pack, c->d_asg_rows};
+    for (void* p : old)
+      if (p) hipFree(p);
+    if (c->h_gt) hipHostFree(c->h_gt);
+    c->d_gt_boxes = c->d_gt_classes = c->d_asg_rows = c->h_gt = nullptr; c->d_asg_pack = nullptr;
+    c->gt_cap = 0; c->asg_n = 0; c->asg_rows = -1;
+    const size_t cap = (size_t)std::max(G, 1), rows = (size_t)m.max_images * cap;
+    HIPC(c, dalloc(&c->d_gt_boxes, rows * 4));
+    HIPC(c, dalloc(&c->d_gt_classes, rows));
+    HIPC(c, dalloc(&c->d_asg_pack, rows * 12 + ((size_t)m.max_images + 1) * 4));
+    HIPC(c, dalloc(&c->d_asg_rows, rows * (size_t)assigned_row_cols_of(m)));
+    HIPC(c, hipHostMalloc((void**)&c->h_gt, rows * 5 * sizeof(float)));
+    c->gt_cap = (int)cap;
+  }
+  const size_t rows = (size_t)n * G;
+  if (rows) {
+    memcpy(c->h_gt, boxes, rows * 4 * sizeof(float));
+    memcpy(c->h_gt + rows * 4, classes, rows * sizeof(float));
+    HIPC(c, hipMemcpyAsync(c->d_gt_boxes, c->h_gt, rows * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->d_gt_classes, c->h_gt + rows * 4, rows * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPC(c, hipEventRecord(c->gt_ev, c->stream));
+  c->gt_n = n; c->gt_G = G;
+  return 0;
+}
+
+extern "C" int uda_assign_ground_truth(uda_ctx_t* c, int32_t method, int32_t keep) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  if (method < ASSIGN_IOU || method > ASSIGN_RANK) return fail(c, "assign_ground_truth: unknown method %d", method);
+  if (keep != ASSIGN_KEEP_VALIDATE && keep != ASSIGN_KEEP_CALIBRATE) return fail(c, "assign_ground_truth: unknown keep rule %d", keep);
+  if (c->gt_n < 1) return fail(c, "assign_ground_truth: no ground truth is set (uda_set_ground_truth)");
+  if (c->as[0].open || c->as[1].open)
+    return fail(c, "assign_ground_truth: a pipelined run (uda_run_async) is in flight - uda_collect it first");
+  if (c->last_n < 1) return fail(c, "assign_ground_truth: no global post-process has run yet");
+  if (c->last_post_mode != UDA_POST_GLOBAL)
+    return fail(c, "assign_ground_truth: the last post-process ran per class; the assignment reads the global post-process");
+  // after a consistency run the handle holds 4n images, the n originals first: the ground truth belongs to those
+  const bool cons = c->noise_from >= 0 && c->cons_n > 0 && c->last_n == 4 * c->cons_n;
+  if (c->gt_n != (cons ? c->cons_n : c->last_n))
+    return fail(c, "assign_ground_truth: ground truth of %d images, the last post-process holds %d", c->gt_n, cons ? c->cons_n : c->last_n);
+  if (m.max_output_size > kAssignMaxM) return fail(c, "assign_ground_truth: max_output_size %d above %d", m.max_output_size, kAssignMaxM);
+  HIPC(c, hipSetDevice(c->device));
+  if (int rc = finish_post(c)) return rc;      // range replay / prefix redo / NMS fallback: the assignment reads final detections
+  const int n = c->gt_n, M = m.max_output_size, G = c->gt_G, C = m.enable_softmax ? m.num_classes : 0;
+  if (C) {
+    if (!c->d_oprobs) {
+      const size_t N = (size_t)m.max_images;
+      HIPC(c, dalloc(&c->d_oprobs, N * M * C));
+      HIPC(c, dalloc(&c->d_oentropy, N * M));
+    }
+    launch_probs(c->d_ologits, c->d_oprobs, c->d_oentropy, n * M, C, c->stream);
+  }
+  const size_t ng = (size_t)n * G;
+  c->d_asg_iou = (double*)c->d_asg_pack;
+  c->d_asg_index = (int32_t*)(c->d_asg_pack + ng * sizeof(double));
+  c->d_asg_count = c->d_asg_index + ng;
+  c->d_asg_err = c->d_asg_count + n;
+  HIPC(c, hipMemsetAsync(c->d_asg_err, 0, sizeof(int32_t), c->stream));
+  AssignArgs a{};
+  a.det_boxes = c->d_oboxes; a.det_stride = box_cols_of(m, UDA_POST_GLOBAL);
+  a.gt_boxes = c->d_gt_boxes; a.gt_classes = c->d_gt_classes;
+  a.det_index = c->d_asg_index; a.iou = c->d_asg_iou; a.count = c->d_asg_count; a.err = c->d_asg_err;
+  a.n = n; a.M = M; a.G = G; a.method = method; a.keep = keep;
+  launch_assign_gt(a, c->stream);
+  AssignRowsArgs r{};
+  r.det_index = c->d_asg_index; r.count = c->d_asg_count;
+  r.boxes = c->d_oboxes; r.scores = c->d_oscores; r.classes = c->d_oclasses;
+  r.logits = c->d_ologits; r.probs = c->d_oprobs; r.entropy = c->d_oentropy;
+  r.rows = c->d_asg_rows;
+  r.n = n; r.M = M; r.G = G; r.bc = a.det_stride; r.cc = cls_cols_of(m, UDA_POST_GLOBAL); r.C = C; r.cols = assigned_row_cols_of(m);
+  launch_gather_assigned(r, c->stream);
+  HIPC(c, hipGetLastError());
+  c->asg_n = n; c->asg_G = G; c->asg_rows = -1;
+  return 0;
+}
+
+// The first reader of an assignment waits for it and brings the packed results over in one copy.
+static int fetch_assignment(uda_ctx* c) {
+  if (c->asg_rows >= 0) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  const size_t ng = (size_t)c->asg_n * c->asg_G;
+  c->h_asg.resize(ng * 12 + ((size_t)c->asg_n + 1) * 4);
+  HIPC(c, hipMemcpy(c->h_asg.data(), c->d_asg_pack, c->h_asg.size(), hipMemcpyDeviceToHost));
+  const int32_t* cnt = (const int32_t*)(c->h_asg.data() + ng * 12);
+  if (cnt[c->asg_n]) return fail(c, "assign_ground_truth: the rank method met a kept ground-truth row beyond the %d detections", c->model.max_output_size);
+  int64_t rows = 0;
+  for (int i = 0; i < c->asg_n; ++i) rows += cnt[i];
+  c->asg_rows = rows;
+  return 0;
+}
+
+extern "C" int uda_get_assignment(uda_ctx_t* c, int32_t* det_index, double* iou, int32_t* count) {
+  if (!c) return 1;
+  if (c->asg_n < 1) return fail(c, "get_assignment: no assignment (uda_assign_ground_truth)");
+  if (int rc = fetch_assignment(c)) return rc;
+  const size_t ng = (size_t)c->asg_n * c->asg_G;
+  const char* h = c->h_asg.data();
+  if (iou && ng) memcpy(iou, h, ng * sizeof(double));
+  if (det_index && ng) memcpy(det_index, h + ng * 8, ng * sizeof(int32_t));
+  if (count) memcpy(count, h + ng * 12, (size_t)c->asg_n * sizeof(int32_t));
+  return 0;
+}
+
+extern "C" int uda_get_assigned_rows(uda_ctx_t* c, float* rows, int64_t n_floats) {
+  if (!c) return 1;
+  if (c->asg_n < 1) return fail(c, "get_assigned_rows: no assignment (uda_assign_ground_truth)");
+  if (int rc = fetch_assignment(c)) return rc;
+  const int64_t want = c->asg_rows * assigned_row_cols_of(c->model);
+  if (n_floats != want) return fail(c, "get_assigned_rows: the %lld matched rows take %lld floats, not %lld", (long long)c->asg_rows, (long long)want, (long long)n_floats);
+  if (want && !rows) return fail(c, "get_assigned_rows: NULL output");
+  HIPC(c, hipSetDevice(c->device));
+  if (want) HIPC(c, hipMemcpy(rows, c->d_asg_rows, (size_t)want * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// gt_box_assigner for callers that hold detections of their own: host arrays in, the same kernel, host arrays out
+extern "C" int uda_assign_gt_np(int32_t device, const float* det_boxes, const float* gt_boxes, const float* gt_classes, int32_t n,
+                                int32_t M, int32_t G, int32_t method, int32_t keep, int32_t* det_index, double* iou, int32_t* count) {
+  if (n < 0 || M < 0 || G < 0 || M > kAssignMaxM || G > kAssignMaxG || method < ASSIGN_IOU || method > ASSIGN_RANK ||
+      (keep != ASSIGN_KEEP_VALIDATE && keep != ASSIGN_KEEP_CALIBRATE) || !count ||
+      ((size_t)n * G && (!gt_boxes || !gt_classes || !det_index || !iou)) || ((size_t)n * M && !det_boxes))
+    return fail(nullptr, "uda_assign_gt_np: bad argument");
+  if (n == 0) return 0;
+  float *d_det = nullptr, *d_gb = nullptr, *d_gc = nullptr;
+  int32_t *d_idx = nullptr, *d_cnt = nullptr;
+  double* d_iou = nullptr;
+  const size_t nm = (size_t)n * M, ng = (size_t)n * G;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = dalloc(&d_det, nm * 4);
+  if (e == hipSuccess) e = dalloc(&d_gb, ng * 4);
+  if (e == hipSuccess) e = dalloc(&d_gc, ng);
+  if (e == hipSuccess) e = dalloc(&d_idx, ng);
+  if (e == hipSuccess) e = dalloc(&d_iou, ng);
+  if (e == hipSuccess) e = dalloc(&d_cnt, (size_t)n + 1);
+  if (e == hipSuccess && nm) e = hipMemcpy(d_det, det_boxes, nm * 4 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && ng) e = hipMemcpy(d_gb, gt_boxes, ng * 4 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && ng) e = hipMemcpy(d_gc, gt_classes, ng * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_cnt, 0, ((size_t)n + 1) * sizeof(int32_t));
+  int32_t err = 0;
+  if (e == hipSuccess) {
+    AssignArgs a{};
+    a.det_boxes = d_det; a.det_stride = 4; a.gt_boxes = d_gb; a.gt_classes = d_gc;
+    a.det_index = d_idx; a.iou = d_iou; a.count = d_cnt; a.err = d_cnt + n;
+    a.n = n; a.M = M; a.G = G; a.method = method; a.keep = keep;
+    launch_assign_gt(a, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(count, d_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&err, d_cnt + n, sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && ng) e = hipMemcpy(det_index, d_idx, ng * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && ng) e = hipMemcpy(iou, d_iou, ng * sizeof(double), hipMemcpyDeviceToHost);
+  void* ptrs[] = {d_det, d_gb, d_gc, d_idx, d_iou, d_cnt};
+  for (void* p : ptrs)
+    if (p) hipFree(p);
+  if (e != hipSuccess) return fail(nullptr, "uda_assign_gt_np: %s", hipGetErrorString(e));
+  if (err) return fail(nullptr, "uda_assign_gt_np: the rank method met a kept ground-truth row beyond the %d detections", M);
   return 0;
 }
 

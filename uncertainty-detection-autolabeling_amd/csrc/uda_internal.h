@@ -371,6 +371,29 @@ struct ConsArgs {
 };
 void launch_consistency(const ConsArgs& a, hipStream_t s);
 
+// ground-truth assignment (reference utils_extra.py:44-64; validate_model.py:314-339, calibrate_model.py:133-147)
+enum { ASSIGN_IOU = 0, ASSIGN_MSE = 1, ASSIGN_RANK = 2 };
+enum { ASSIGN_KEEP_VALIDATE = 0, ASSIGN_KEEP_CALIBRATE = 1 };
+struct AssignArgs {
+  const float* det_boxes;   // [n, M, det_stride] y1 x1 y2 x2 in the first four columns
+  const float* gt_boxes;    // [n, G, 4]
+  const float* gt_classes;  // [n, G] (-1 rows: padding)
+  int32_t* det_index;       // [n, G] matched rank, -1 = row not kept
+  double* iou;              // [n, G] calc_iou_np(gt, matched box), 0 = row not kept
+  int32_t* count;           // [n] kept rows
+  int32_t* err;             // set to 1 when the rank method meets a kept row >= M
+  int n, M, G, det_stride, method, keep;
+};
+void launch_assign_gt(const AssignArgs& a, hipStream_t s);
+struct AssignRowsArgs {
+  const int32_t* det_index; // [n, G]
+  const int32_t* count;     // [n]
+  const float *boxes, *scores, *classes, *logits, *probs, *entropy;   // the detection outputs (logits / probs / entropy: C > 0)
+  float* rows;              // [sum(count), cols]
+  int n, M, G, bc, cc, C, cols;   // cols = bc + 1 + cc + (C ? 2 C + 1 : 0)
+};
+void launch_gather_assigned(const AssignRowsArgs& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

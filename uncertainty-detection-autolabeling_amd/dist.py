@@ -282,6 +282,15 @@ class SampleShardedDriver:
     def serve_consistency(self, images, *args, **kwargs):
         raise NotImplementedError("the consistency check (consistency_ssl) is served by a single ServingDriver")
 
+    def assign_ground_truth(self, gt_boxes, gt_classes, method=None, keep="validate"):
+        """After the gather every rank holds ALL detections on the host, while its post-processing handle holds its own image
+        shard only: no single handle has the batch, so the resident assignment does not apply."""
+        raise ValueError("a sample-sharded serve leaves no handle that holds the whole batch's detections: run "
+                         "utils_extra.assign_gt_boxes(method, gt_boxes, gt_classes, boxes) on the gathered detections")
+
+    def serve_validate(self, images, gt_boxes, gt_classes, method=None, keep="validate"):
+        return self.assign_ground_truth(gt_boxes, gt_classes, method, keep)
+
     def close(self):
         self.net.close()
         self.post.close()

@@ -39,6 +39,32 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def split_assigned_rows(params, table, box_cols, cls_cols, num_classes):
+    """The matched-rows table of `uda_get_assigned_rows` [K, cols] -> the columns `writers.validate_records` reads.  Row layout:
+    box columns | score | class columns | logits | probab | entropy (the last three with enable_softmax).  The device copies
+    the values unchanged; the reference's np.nan_to_num of the uncertainty columns (validate_model.py:176-196) happens here,
+    in `postprocess.unpack_detections` - the same split `serve_unpacked` makes of whole detections."""
+    from . import postprocess as pp
+    table = np.asarray(table, np.float32)
+    with_logits = bool(params["enable_softmax"])
+    want = box_cols + 1 + cls_cols + ((2 * num_classes + 1) if with_logits else 0)
+    if table.ndim != 2 or table.shape[1] != want:
+        raise ValueError("matched rows must be [K, %d], got %s" % (want, table.shape))
+    o = 0
+    boxes = table[:, o:o + box_cols]; o += box_cols
+    scores = table[:, o]; o += 1
+    classes = table[:, o:o + cls_cols] if cls_cols > 1 else table[:, o]; o += cls_cols
+    det = [boxes[None], scores[None], classes[None], None]
+    probab = entropy = None
+    if with_logits:
+        det.append(table[None, :, o:o + num_classes]); o += num_classes
+        probab = table[None, :, o:o + num_classes]; o += num_classes
+        entropy = table[None, :, o]
+    un = pp.unpack_detections(params, tuple(det), probab, entropy)
+    keys = ("scores", "boxes", "classes", "logits", "probab", "entropy", "mcclass", "mcbox", "albox")
+    return {k: (None if un[k] is None else np.ascontiguousarray(un[k][0])) for k in keys}
+
+
 class ServingDriver:
     """One GPU, one handle, synchronous calls (same threading contract as the reference).
 
@@ -421,6 +447,75 @@ class ServingDriver:
                 off += sz
             out.append(imgs)
         return out[0], out[1]
+
+    # ------------------------------------------------------------------ validate / calibrate: ground-truth assignment
+    def _queue_assignment(self, gb, gc, method, keep):
+        from . import utils_extra
+        method = self.params.get("assign_gt_box") if method is None else method
+        kc = utils_extra.keep_code(keep)
+        utils_extra.check_rank_rows(method, gc, self.M, keep)
+        self._ck(self._lib.uda_set_ground_truth(self._h, _ptr(gb), _ptr(gc), gb.shape[0], gb.shape[1]), "uda_set_ground_truth")
+        return utils_extra.assign_method_code(method), kc
+
+    def _fetch_assignment(self, gb, gc, keep):
+        n, G = gc.shape
+        idx = np.full((n, G), -1, np.int32)
+        iou = np.zeros((n, G), np.float64)
+        count = np.zeros((n,), np.int32)
+        self._ck(self._lib.uda_get_assignment(self._h, _ptr(idx), _ptr(iou), _ptr(count)), "uda_get_assignment")
+        cols = C.c_int32()
+        self._ck(self._lib.uda_assigned_row_cols(self._h, C.byref(cols)), "uda_assigned_row_cols")
+        table = np.empty((int(count.sum()), cols.value), np.float32)
+        self._ck(self._lib.uda_get_assigned_rows(self._h, _ptr(table), table.size), "uda_get_assigned_rows")
+        bc, cc = C.c_int32(), C.c_int32()
+        self._ck(self._lib.uda_detection_cols(self._h, capi.POST_GLOBAL, C.byref(bc), C.byref(cc)), "uda_detection_cols")
+        out = dict(det_index=idx, iou=iou, count=count)
+        out.update(split_assigned_rows(self.params, table, bc.value, cc.value, self.num_classes))
+        image, row = np.nonzero(idx >= 0)                # row-major = (image, GT row): the order of the table
+        out["gt_boxes"] = gb[image, row]
+        out["gt_classes"] = gc[image, row] - np.float32(1) if keep == "calibrate" else gc[image, row]   # calibrate_model.py:137
+        out["image"], out["gt_row"] = image.astype(np.int32), row.astype(np.int32)
+        return out
+
+    def assign_ground_truth(self, gt_boxes, gt_classes, method=None, keep="validate"):
+        """What the reference's validate and calibrate modes do on the host right after `serve` (validate_model.py:314-470,
+        calibrate_model.py:133-190), on the detections resident in the handle: every kept ground-truth (GT) row gets the
+        detection that belongs to it (`utils_extra.gt_box_assigner`, :44-64) and that detection's row of every output
+        column comes back as one compact table.
+
+        gt_boxes [n, G, 4] (y1, x1, y2, x2 in raw-image pixels, like the boxes `serve` returns), gt_classes [n, G], padded
+        with -1 rows (inspector.py:147-160); cast to float32; non-finite values raise ValueError.  method: "IoU" | "MSE" |
+        anything else = the GT row's own rank; None = model_params["assign_gt_box"].  keep="validate": rows with class > 0;
+        "calibrate": rows < min(G, M) with class >= 0, reported class = class - 1.
+
+        Returns a dict: det_index [n, G] int32 (-1: not kept), iou [n, G] float64 (GT box against its detection), count
+        [n]; and for the K = sum(count) matched rows in (image, GT row) order the columns `writers.validate_records` reads -
+        scores, boxes [K, 4], classes, logits, probab, entropy, mcclass, mcbox, albox (None where the configuration has
+        none; the uncertainty columns through np.nan_to_num, done here on the host) - plus gt_boxes, gt_classes, image, gt_row.
+        It reads the last run (serve, serve_resident, serve_consistency's originals, inside serve_stream(while_resident=))."""
+        from . import utils_extra
+        gb, gc = utils_extra.check_ground_truth(gt_boxes, gt_classes)
+        mc, kc = self._queue_assignment(gb, gc, method, keep)
+        self._ck(self._lib.uda_assign_ground_truth(self._h, mc, kc), "uda_assign_ground_truth")
+        return self._fetch_assignment(gb, gc, keep)
+
+    def serve_validate(self, image_arrays, gt_boxes, gt_classes, method=None, keep="validate"):
+        """serve + `assign_ground_truth` as one device pass -> (detections, assignment): the GT upload is queued before the
+        network, the assignment behind the post-process, and the host waits once.  `detections` is exactly what `serve()`
+        returns with the same dropout seed (global post-process)."""
+        from . import utils_extra
+        gb, gc = utils_extra.check_ground_truth(gt_boxes, gt_classes)
+        n = self._feed(image_arrays)
+        if gb.shape[0] != n:
+            raise ValueError("ground truth of %d images for a batch of %d" % (gb.shape[0], n))
+        mc, kc = self._queue_assignment(gb, gc, method, keep)
+        self._next_seed()
+        self._run_id += 1
+        self._ck(self._lib.uda_run(self._h, capi.POST_GLOBAL, 1), "uda_run")
+        self._last_n = n
+        self._ck(self._lib.uda_assign_ground_truth(self._h, mc, kc), "uda_assign_ground_truth")
+        det = self._collect(n, capi.POST_GLOBAL)
+        return det, self._fetch_assignment(gb, gc, keep)
 
     def serve_resident(self, image_arrays, post_mode=None):
         """serve() without the download: the detections stay in the handle (`detections_device`, calibrators,
@@ -900,6 +995,14 @@ class EnsembleDriver:
 
     def serve_consistency(self, image_arrays, post_mode=None):
         raise NotImplementedError("the consistency check (consistency_ssl) is served by a single ServingDriver")
+
+    def assign_ground_truth(self, gt_boxes, gt_classes, method=None, keep="validate"):
+        """The ensemble's detections live in its aggregating handle: the assignment is that handle's."""
+        return self.post.assign_ground_truth(gt_boxes, gt_classes, method=method, keep=keep)
+
+    def serve_validate(self, image_arrays, gt_boxes, gt_classes, method=None, keep="validate"):
+        det = self.serve(image_arrays)
+        return det, self.assign_ground_truth(gt_boxes, gt_classes, method=method, keep=keep)
 
     def close(self):
         for d in self.members + [self.post]:

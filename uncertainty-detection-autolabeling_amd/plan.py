@@ -207,8 +207,10 @@ MODEL_PARAM_HANDLING = {
     "infer_draw_uncert": "consumed by visualize", "label_map": "consumed by infer_lib / writers",
     "consistency_ssl": "consumed: infer_lib plans 4 x batch_size images for serve_consistency (flip / blur / noise "
                        "variants, infer_model.py:768-848); writers.predict_to_file writes cons_iou / cons_cls",
+    "assign_gt_box": "consumed: default method of ServingDriver.assign_ground_truth / serve_validate (IoU | MSE | else the GT "
+                     "row's own rank; utils_extra.py:44-64, validate_model.py:337, calibrate_model.py:140)",
     # --- training-only keys the shipped YAMLs set
-    "assign_gt_box": "inert: validation matching above the driver", "early_stopping_patience": "inert: training",
+    "early_stopping_patience": "inert: training",
     "count_classes": "inert: training", "boxloss_type": "inert: training", "save_freq": "inert: training",
     "sample_images": "inert: training", "sample_images_freq": "inert: training", "save_train_images": "inert: training",
     "autoaugment_policy": "inert: training", "map_freq": "inert: training", "box_loss_weight": "inert: training",

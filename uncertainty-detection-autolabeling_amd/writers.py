@@ -4,7 +4,8 @@
                         writes it (reference src/infer_model.py:836-960, `add_array_dict` utils_extra.py:67-81)
   validate_results.txt  one dict per detection matched to a ground-truth box, as `Validate.launch_val` writes it
                         (src/validate_model.py:524-681), plus the runtime summary of validationstep_runtime.txt
-                        (:685-704)
+                        (:685-704), average_score.txt (:683-684) and model_performance.txt (:706-735):
+                        `validate_to_file` is that whole loop
 
 Both are read back with `ast.literal_eval(line.replace("inf", "2e308"))` (active_learning_loop.py:532,
 SSL_stac.py:345, uncertainty_analysis.py).  The reference prints numpy-1 float32 scalars, whose repr is the shortest
@@ -219,3 +220,97 @@ def summarize_runtimes(seconds):
     kept = [x for x in t if x <= q3 + 50 * iqr]
     return ["Mean time in ms: {:.3f}\n".format(np.mean(kept) * 1000), "STD time in ms: {:.3f}\n".format(np.std(kept) * 1000),
             "Median time in ms: {:.3f}\n".format(np.median(kept) * 1000)]
+
+
+def model_performance(filtered):
+    """The three lines of model_performance.txt (validate_model.py:706-735) from the matched rows: share of rows whose
+    class differs from the ground truth's, mean IoU (`filtered["iou"]`: calc_iou_np of each GT box with its detection), and
+    RMSE over the box ELEMENTS where the ground truth is not 0 (utils_box.py:92-103).  The reference takes the RMSE as a
+    TensorFlow float32 reduce_mean whose summation order is not pinned; here it is a float64 mean."""
+    gt_cls, cls = np.asarray(filtered["gt_classes"]), np.asarray(filtered["classes"])
+    gt, b = np.asarray(filtered["gt_boxes"], np.float32), np.asarray(filtered["boxes"], np.float32)
+    mis = len(np.where(gt_cls != cls)[0]) / len(gt_cls)
+    sq = np.square(b.astype(np.float64) - gt.astype(np.float64))[gt != 0.0]
+    return ["Misclassification rate: {}\n".format(mis), "mIoU: {}\n".format(float(np.mean(filtered["iou"]))),
+            "RMSE: {}\n".format(float(np.sqrt(np.mean(sq))))]
+
+
+def validate_to_file(driver, batches, gts, names, out_dir, box_calibrator=None, class_calibrator=None, occlusions=None,
+                     truncations=None):
+    """The loop of `Validate.launch_val` (validate_model.py:472-735) without its `infer_augment` branches, over batches
+    of images: serve (feed of the next batch hidden under this one, as in `predict_to_file`) -> ground-truth assignment on
+    the resident detections (`ServingDriver.assign_ground_truth`, method model_params["assign_gt_box"]) -> calibrated
+    columns of every method the calibrators hold a model for, gathered on the host with `det_index` -> files in `out_dir`:
+
+      validate_results.txt          `validate_records` / `write_validate_results`
+      average_score.txt             mean matched score (:683-684; the reference accumulates the scores in float64)
+      validationstep_runtime.txt    `summarize_runtimes` of the per-image serve time (batch time / images, the assignment
+                                    and the writing excluded, as the reference times serve() alone, :154-158)
+      model_performance.txt         only without box uncertainty (no MC box dropout, no loss attenuation), as the reference
+                                    (:706-735); `model_performance`
+
+    gts: per batch (gt_boxes [n, G, 4], gt_classes [n, G]); names: per batch the n image file names; occlusions /
+    truncations: per batch [n, G] label fields (None: written as 0).  Returns the matched-row arrays (`filtered`)."""
+    import os
+    import time
+    p = driver.params
+    gts, names = list(gts), list(names)
+    keys = ("scores", "boxes", "classes", "logits", "probab", "entropy", "mcclass", "mcbox", "albox", "gt_boxes", "gt_classes")
+    acc = {k: [] for k in keys + ("names", "occlusions", "truncations", "iou")}
+    cal_acc = {}
+    state = {"i": 0, "inside": 0.0}
+    seconds = []
+
+    def per_batch(det):
+        t0 = time.time()
+        b = state["i"]
+        n = det[0].shape[0]
+        asg = driver.assign_ground_truth(gts[b][0], gts[b][1], keep="validate")
+        im, row, k = asg["image"], asg["gt_row"], asg["det_index"][asg["image"], asg["gt_row"]]
+        for key in keys:
+            if asg[key] is not None:
+                acc[key].append(asg[key])
+        acc["iou"].append(asg["iou"][im, row])
+        acc["names"] += [names[b][i] for i in im]
+        for key, src in (("occlusions", occlusions), ("truncations", truncations)):
+            acc[key].append(np.zeros(len(im), np.int64) if src is None else np.asarray(src[b])[im, row])
+        if box_calibrator is not None and p.get("calibrate_regression"):
+            for which in ("albox", "mcbox"):
+                if asg[which] is not None:
+                    for m in box_calibrator.models:
+                        cal_acc.setdefault("%s_%s" % (m, which), []).append(box_calibrator.calibrate_boxuncert(n, which, m)[im, k])
+        if class_calibrator is not None and p.get("calibrate_classification") and asg["logits"] is not None:
+            for m in class_calibrator.models:
+                r = class_calibrator.perform_class_calib(n, m)
+                cal_acc.setdefault(m + "_entropy", []).append(r[0][im, k])
+                cal_acc.setdefault(m + "_probab", []).append(r[1][im, k])
+                if len(r) > 2:
+                    cal_acc.setdefault(m + "_mcclass", []).append(r[2][im, k])
+        state["i"] += 1
+        state["inside"] = time.time() - t0
+        return n
+
+    it = driver.serve_stream(batches, while_resident=per_batch)
+    while True:
+        t0 = time.time()
+        n = next(it, None)
+        if n is None:
+            break
+        seconds += [(time.time() - t0 - state["inside"]) / n] * n
+
+    filtered = {k: (np.concatenate(v) if v else None) for k, v in acc.items() if k != "names"}
+    filtered["names"] = acc["names"]
+    cal = {k: np.concatenate(v) for k, v in cal_acc.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    if filtered["boxes"] is None:
+        raise ValueError("validate_to_file: no batches")
+    write_validate_results(os.path.join(out_dir, "validate_results.txt"), validate_records(filtered, p, cal))
+    with open(os.path.join(out_dir, "average_score.txt"), "w") as f:
+        f.write(str(np.mean(filtered["scores"].astype(np.float64))))
+    with open(os.path.join(out_dir, "validationstep_runtime.txt"), "w") as f:
+        f.writelines(summarize_runtimes(seconds))
+    if not (p.get("mc_boxheadrate") or p.get("mc_dropoutrate")) and not p.get("loss_attenuation"):
+        with open(os.path.join(out_dir, "model_performance.txt"), "w") as f:
+            f.writelines(model_performance(filtered))
+    filtered["calibrated"] = cal
+    return filtered
