@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define UDA_ABI_VERSION 4
+#define UDA_ABI_VERSION 5
 #define UDA_MAX_LEVELS 8
 #define UDA_MAX_FUSE_INPUTS 3
 
@@ -117,6 +117,14 @@ typedef struct uda_drop_site {
 enum uda_decode { UDA_DECODE_PLAIN = 0, UDA_DECODE_LNORM = 1, UDA_DECODE_FALSEDEC = 2,
                   UDA_DECODE_SAMPLE = 3 /* utils_box.py:162-184: moments of decode_nsamples decoded Normal draws (Philox stream) */ };
 enum uda_post_mode { UDA_POST_GLOBAL = 0, UDA_POST_PER_CLASS = 1 };
+/* split-precision scheme of the 1x1 contractions (plan.PW_SCHEMES; the values are kernel template arguments) */
+enum uda_pw_scheme {
+  UDA_SPLIT_NONE = 0,     /* "f32": exact f32-input MFMA kernels, unfused */
+  UDA_SPLIT_BF16X2 = 2,   /* "bf16x2": two bf16 pieces per operand, three cross terms (~2^-17 per product) */
+  UDA_SPLIT_BF16X3 = 3,   /* "bf16x3": three bf16 pieces, six cross terms (~2^-24) */
+  UDA_SPLIT_F16X2 = 4,    /* "f16x2": two fp16 pieces, three cross terms (~2^-22; operands must stay below 65504) */
+  UDA_SPLIT_F16X1 = 5     /* "f16": one fp16 piece, one product (~2^-11: Keras mixed_float16 operands; same range limit) */
+};
 
 typedef struct uda_model {
   int32_t abi_version;
@@ -144,6 +152,7 @@ typedef struct uda_model {
   int64_t arena_floats;             /* per-chunk arena size */
   int32_t n_drop_sites;
   int32_t decode_nsamples;          /* UDA_DECODE_SAMPLE: draws per (anchor, MC sample); config `decode_nsamples` (100) */
+  int32_t pw_scheme;                /* uda_pw_scheme of the handle (plan.Plan.pw_scheme); anything else fails uda_create */
 } uda_model_t;
 
 typedef struct uda_ctx uda_ctx_t;

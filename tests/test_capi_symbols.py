@@ -42,15 +42,16 @@ def test_library_exports_every_declared_symbol(lib_path):
 def test_struct_layouts_match_c(tmp_path):
     csrc = tmp_path / "sz.c"
     csrc.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "uda_hip.h"\n'
-                    'int main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(uda_buf_desc_t), sizeof(uda_op_t),'
+                    'int main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(uda_buf_desc_t), sizeof(uda_op_t),'
                     'sizeof(uda_drop_site_t), sizeof(uda_model_t), offsetof(uda_op_t, w_off), offsetof(uda_op_t, fuse_w),'
-                    'offsetof(uda_model_t, arena_floats), offsetof(uda_model_t, nms_soft_sigma));return 0;}\n')
+                    'offsetof(uda_model_t, arena_floats), offsetof(uda_model_t, nms_soft_sigma), offsetof(uda_model_t, pw_scheme));return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(csrc), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
     want = [ctypes.sizeof(capi.BufDesc), ctypes.sizeof(capi.Op), ctypes.sizeof(capi.DropSite),
             ctypes.sizeof(capi.Model), capi.Op.w_off.offset, capi.Op.fuse_w.offset,
-            capi.Model.arena_floats.offset, capi.Model.nms_soft_sigma.offset]
+            capi.Model.arena_floats.offset, capi.Model.nms_soft_sigma.offset, capi.Model.pw_scheme.offset]
+    assert got[6:8] == [176, 140]       # the fields of ABI 4 keep their places: pw_scheme is appended
     assert got == want
 
 

@@ -64,39 +64,83 @@ def test_exactly_the_fused_front_halves_outputs_are_fp16(scheme_env, mc):
     assert all(b.storage == "f32" for b in _plan(p, w).bufs)
 
 
-def test_support_mirrors_with_one_piece(scheme_env):
+def test_support_mirrors_with_one_piece():
     from uda_amd import plan
-    scheme_env("f16")
     # the deferred-input mode at the heads' widths (D0 64, D2 112): the A region is widened to hold the epilogue staging
     for c in (64, 112):
         for cout in (c, 36, 63, 72):
-            assert plan.sep_tin_supported(c, cout) == plan.sep_tin_supported(c, cout, "f16x2"), (c, cout)
-    assert plan.sepf_supported(64, 64) and plan.sepf_supported(112, 112)
+            assert plan.sep_tin_supported(c, cout, "f16") == plan.sep_tin_supported(c, cout, "f16x2"), (c, cout)
+    assert plan.sepf_supported(64, 64, "f16") and plan.sepf_supported(112, 112, "f16")
+
+
+def _fake_library(monkeypatch, seen):
+    """capi.load() -> a stand-in whose uda_create records the environment and the model struct it is handed (a real handle
+    needs a GPU) and leaves the handle NULL."""
+    from uda_amd import capi
+
+    class Lib:
+        def uda_create(self, model, *rest):
+            seen.append((os.environ.get("UDA_PW_SCHEME"), os.environ.get("UDA_PW_TERMS"), model._obj.pw_scheme))
+            return 0
+    monkeypatch.setattr(capi, "load", lambda: Lib())
 
 
 def test_driver_accepts_f16(monkeypatch):
-    """The driver's validation of `uda_pw_scheme` accepts "f16" and hands it to the handle's creation (stubbed: the handle
-    itself needs a GPU), where the planner reads it; an unknown value is refused."""
-    from uda_amd import plan
-    from uda_amd.infer_lib import ServingDriver, KerasDriver
+    """`uda_pw_scheme = "f16"` reaches the handle's creation in the model struct (code 5), not through the environment, which
+    is untouched while the handle is created; the driver's and the plan's scheme say f16; an unknown value is refused."""
+    from uda_amd.infer_lib import KerasDriver
     seen = []
-
-    class Created(Exception):
-        pass
-
-    def create(self, *a, **k):
-        seen.append((self.pw_scheme, plan.pw_scheme()))
-        raise Created          # (stop here: what follows needs the handle)
-    monkeypatch.setattr(ServingDriver, "_create", create)
+    _fake_library(monkeypatch, seen)
     monkeypatch.delenv("UDA_PW_SCHEME", raising=False)
+    monkeypatch.delenv("UDA_PW_TERMS", raising=False)
     p = make_params(**FULL_MC)
     w = make_weights(p)
-    with pytest.raises(Created):
-        KerasDriver("_", False, p["name"], 1, False, dict(p, uda_pw_scheme="f16"), weights=w)
-    assert seen == [("f16", "f16")]
-    assert "UDA_PW_SCHEME" not in os.environ          # (set for the creation only)
+    d = KerasDriver("_", False, p["name"], 1, False, dict(p, uda_pw_scheme="f16"), weights=w)
+    assert seen == [(None, None, 5)]
+    assert d.pw_scheme == "f16" and d.plan.pw_scheme == "f16" and d.plan.to_c()[0].pw_scheme == 5
+    assert "UDA_PW_SCHEME" not in os.environ and "UDA_PW_TERMS" not in os.environ
     with pytest.raises(ValueError, match="uda_pw_scheme"):
         KerasDriver("_", False, p["name"], 1, False, dict(p, uda_pw_scheme="f8"), weights=w)
+    assert len(seen) == 1           # (refused before anything was created)
+
+
+def test_params_win_over_the_environment(monkeypatch):
+    """UDA_PW_SCHEME is the default only: a handle whose params name a scheme plans with that one, whatever the environment says."""
+    from uda_amd import plan
+    from uda_amd.infer_lib import KerasDriver
+    seen = []
+    _fake_library(monkeypatch, seen)
+    monkeypatch.delenv("UDA_PW_TERMS", raising=False)
+    monkeypatch.setenv("UDA_PW_SCHEME", "bf16x3")
+    p = make_params(**FULL_MC)
+    w = make_weights(p)
+    assert _plan(dict(p, uda_pw_scheme="f16"), w).pw_scheme == "f16"
+    assert _plan(p, w).pw_scheme == "bf16x3" and _plan(p, w).to_c()[0].pw_scheme == 3
+    a = KerasDriver("_", False, p["name"], 1, False, dict(p, uda_pw_scheme="f16"), weights=w)
+    b = KerasDriver("_", False, p["name"], 1, False, p, weights=w)
+    assert (a.pw_scheme, b.pw_scheme) == ("f16", "bf16x3")
+    assert seen == [("bf16x3", None, 5), ("bf16x3", None, 3)]
+    assert {s: plan.PW_SCHEME_CODES[s] for s in plan.PW_SCHEMES} == {"f32": 0, "bf16x2": 2, "bf16x3": 3, "f16x2": 4, "f16": 5}
+
+
+def _plan_state(pl):
+    bufs = [(b.H, b.W, b.C, b.per_sample, b.kind, b.level, b.offset, b.name, b.storage) for b in pl.bufs]
+    return bufs, pl.ops, pl.sites, pl.arena_floats
+
+
+@pytest.mark.parametrize("mc", ["full", "head"])
+def test_plans_of_two_schemes_do_not_disturb_each_other(monkeypatch, mc):
+    """Two Plans with different schemes built alternately in one process equal the plans built alone: nothing a Plan decides
+    depends on what another one was given (f32 against f16: unfused against fused with fp16 storage, the widest difference)."""
+    monkeypatch.delenv("UDA_PW_SCHEME", raising=False)
+    monkeypatch.delenv("UDA_PW_TERMS", raising=False)
+    p = make_params(**(FULL_MC if mc == "full" else HEAD_MC))
+    w = make_weights(p, seed=1)
+    alone = {s: _plan_state(_plan(dict(p, uda_pw_scheme=s), w)) for s in ("f32", "f16", "bf16x3")}
+    assert alone["f32"] != alone["f16"]
+    for s in ("f16", "f32", "bf16x3", "f32", "f16", "bf16x3"):
+        assert _plan_state(_plan(dict(p, uda_pw_scheme=s), w)) == alone[s], s
+    assert _plan_state(_plan(p, w)) == _plan_state(_plan(dict(p, uda_pw_scheme="f16x2"), w))      # the default, either way
 
 
 def test_isa_lint_covers_the_one_piece_kernels():

@@ -252,9 +252,21 @@ if sys.argv[2] == "after_f16":
 d = KerasDriver("_", False, p["name"], 2, False, dict(p, uda_pw_scheme="f16x2"), weights=w)
 assert d.pw_scheme == "f16x2"
 d.set_dropout_seed(4)
+if sys.argv[2] == "beside_f16":
+    # UDA_PW_SCHEME=bf16x3 in this process's environment; an f16 handle alive at the same time, served alternately
+    import os
+    assert os.environ["UDA_PW_SCHEME"] == "bf16x3"
+    other = KerasDriver("_", False, p["name"], 2, False, dict(p, uda_pw_scheme="f16"), weights=w)
+    assert other.pw_scheme == "f16" and d.pw_scheme == "f16x2"
+    other.set_dropout_seed(4)
+    for _ in range(2):
+        d.serve(imgs)
+        other.serve(imgs)
 det = d.serve(imgs)
 cls, box = d.head_outputs(2)
 d.close()
+if sys.argv[2] == "beside_f16":
+    other.close()
 np.savez(sys.argv[1], *(list(det) + list(cls) + list(box)))
 print("saved")
 """
@@ -262,17 +274,21 @@ print("saved")
 
 def test_f16x2_handle_after_an_f16_handle_is_unchanged(tmp_path):
     """The scheme is per handle: an f16x2 handle created after an f16 one in the same process computes bit for bit what one
-    in a fresh process computes."""
+    in a fresh process computes - and so does one that lives beside an f16 handle, served alternately with it, in a process whose
+    environment names a third scheme (the scheme travels in the model description, the environment gives the default only)."""
     outs = []
-    for tag in ("fresh", "after_f16"):
+    for tag in ("fresh", "after_f16", "beside_f16"):
         out = str(tmp_path / (tag + ".npz"))
         e = dict(os.environ)
         e.pop("UDA_PW_SCHEME", None)
         e.pop("UDA_PW_TERMS", None)
+        if tag == "beside_f16":
+            e["UDA_PW_SCHEME"] = "bf16x3"
         r = subprocess.run([sys.executable, "-c", ORDER_WORKER % {"root": ROOT}, out, tag], cwd=ROOT, env=e,
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0 and "saved" in r.stdout, (tag, r.stdout[-1500:], r.stderr[-2500:])
         outs.append(np.load(out))
-    assert len(outs[0].files) == len(outs[1].files) > 5
+    assert len(outs[0].files) == len(outs[1].files) == len(outs[2].files) > 5
     for k in outs[0].files:
         np.testing.assert_array_equal(outs[0][k], outs[1][k], err_msg=k)
+        np.testing.assert_array_equal(outs[0][k], outs[2][k], err_msg="beside_f16 " + k)

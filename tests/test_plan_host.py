@@ -100,16 +100,17 @@ def test_op_list_shape_d0():
     pl, _ = _plan(FULL_MC, chunk_images=2, max_images=4)
     kinds = [o["kind"] for o in pl.ops]
     fused = kinds.count(capi.OP_MBX)           # expand+depthwise as one op: blocks 1-5 (Cin <= 48) and the deep
-    shallow = 5 if plan_mod.mbx_supported(16, 96, 3, 2) else 0      # stride-1 blocks 6-10, 12-15; block 11 (5x5 stride 2): round 3
-    deep = 9 if plan_mod.mbx_supported(112, 672, 5, 1) else 0
-    deep += 1 if plan_mod.mbx_supported(112, 672, 5, 2) else 0
+    sch = pl.pw_scheme
+    shallow = 5 if plan_mod.mbx_supported(16, 96, 3, 2, sch) else 0      # stride-1 blocks 6-10, 12-15; block 11 (5x5 stride 2): round 3
+    deep = 9 if plan_mod.mbx_supported(112, 672, 5, 1, sch) else 0
+    deep += 1 if plan_mod.mbx_supported(112, 672, 5, 2, sch) else 0
     assert fused == shallow + deep and fused == 15
     sep = kinds.count(capi.OP_SEP)             # 24 BiFPN nodes + 2 heads x 5 levels x (3 + 1) separable convs
     assert sep == (64 if pl.fuse_sep else 0)
     proj = sum(1 for o in pl.ops if o["kind"] == capi.OP_MBX and o["se_scale"] >= 0)   # block 0's projection inside block 1's op
     assert proj == (1 if pl.fuse_proj and shallow else 0)
     fin = sum(1 for o in pl.ops if o.get("fuse_in"))      # BiFPN fusions computed inside the node's separable conv (round 4)
-    assert fin == (24 if pl.fuse_sep and plan_mod.sepf_supported(64, 64) else 0)
+    assert fin == (24 if pl.fuse_in and plan_mod.sepf_supported(64, 64, sch) else 0)
     assert all(o["kind"] == capi.OP_SEP and len(o["ins"]) in (2, 3) for o in pl.ops if o.get("fuse_in"))
     assert len(pl.ops) == 224 - fused - sep - proj - fin
     assert kinds.count(capi.OP_STEM) == 1 and kinds.count(capi.OP_SE) == 16 and kinds.count(capi.OP_FUSE) == 24 - fin
@@ -138,7 +139,7 @@ def test_sample_axis_propagation():
     assert any(o["kind"] == capi.OP_SEP and head.bufs[o["out"]].name == "class-0-3" for o in head.ops)
     # the first head layer reads a per-image tensor: its dropout site is deferred into the layer behind it (round 5) - its own
     # output stays per image, the second layer applies the site to its input channels and opens the sample axis
-    deferred = head.fuse_sep and plan_mod.sep_tin_supported(64, 64)
+    deferred = head.defer_head and plan_mod.sep_tin_supported(64, 64, head.pw_scheme)
     assert head.bufs[hb["class-0-3"]].per_sample == (not deferred) and head.bufs[hb["box-predict-7"]].per_sample
     l0 = [o for o in head.ops if head.bufs[o["out"]].name == "class-0-3"][0]
     l1 = [o for o in head.ops if head.bufs[o["out"]].name == "class-1-3"][0]
@@ -294,7 +295,7 @@ def test_reference_block_kats_structure():
 
 def test_pw_scheme_switches(monkeypatch):
     """UDA_PW_SCHEME names the split scheme of the 1x1 contractions (default: two fp16 pieces); the older UDA_PW_TERMS is
-    honoured when the newer switch is silent; anything else is refused (mirror of parse_pw_scheme in csrc/uda_api.hip)."""
+    honoured when the newer switch is silent; anything else is refused.  It is the default of a Plan whose params name no scheme."""
     from uda_amd import plan
     monkeypatch.delenv("UDA_PW_SCHEME", raising=False)
     monkeypatch.delenv("UDA_PW_TERMS", raising=False)
@@ -313,9 +314,9 @@ def test_pw_scheme_switches(monkeypatch):
         plan.pw_scheme()
     # the exact-f32 scheme switches the fusions off in the planner, the split schemes keep them
     monkeypatch.setenv("UDA_PW_TERMS", "0")
-    assert not plan.mbx_supported(192, 1152, 5, 1)
+    assert not plan.mbx_supported(192, 1152, 5, 1, plan.pw_scheme())
     monkeypatch.delenv("UDA_PW_TERMS")
-    assert plan.mbx_supported(192, 1152, 5, 1)
+    assert plan.mbx_supported(192, 1152, 5, 1, plan.pw_scheme())
 
 
 def test_bifpn_fusion_folds_into_the_separable_conv(monkeypatch):

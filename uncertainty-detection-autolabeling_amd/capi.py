@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("UDA_LIB") or os.path.join(CSRC, "libuda_hip.so")   # UDA_LIB: an alternative build for A/B runs
 HEADER = os.path.join(os.path.dirname(HERE), "include", "uda_hip.h")
 
-UDA_ABI_VERSION = 4
+UDA_ABI_VERSION = 5
 MAX_LEVELS = 8
 MAX_FUSE = 3
 
@@ -64,7 +64,8 @@ class Model(C.Structure):
                 ("nms_iou_thresh", C.c_float), ("nms_score_thresh", C.c_float),
                 ("max_output_size", C.c_int32), ("max_nms_inputs", C.c_int32),
                 ("post_mode", C.c_int32), ("chunk_images", C.c_int32), ("max_images", C.c_int32),
-                ("arena_floats", C.c_int64), ("n_drop_sites", C.c_int32), ("decode_nsamples", C.c_int32)]
+                ("arena_floats", C.c_int64), ("n_drop_sites", C.c_int32), ("decode_nsamples", C.c_int32),
+                ("pw_scheme", C.c_int32)]
 
 
 _P = C.c_void_p

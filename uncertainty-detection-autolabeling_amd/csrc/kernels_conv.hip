@@ -254,8 +254,7 @@ void launch_stem(const StemArgs& a, hipStream_t s) {
     }
     return;
   }
-  static int wide = -1;
-  if (wide < 0) { const char* e = getenv("UDA_STEM16"); wide = e ? atoi(e) : 1; }
+  static const int wide = uda_env_int("UDA_STEM16", 1);
   if (wide && (a.Co & 15) == 0 && a.act == UDA_ACT_SWISH) {     // (stem16 / stem_u8 are swish kernels; the executor keeps other activations off the uint8 route)
     const int64_t total = (int64_t)a.rows * a.Ho * a.Wo * (a.Co >> 4);
     hipLaunchKernelGGL(stem16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 27 * a.Co * sizeof(float), s, a);
@@ -505,8 +504,7 @@ void launch_pw(const PwArgs& a, int rows, hipStream_t s) {
   const int per = (a.Cout + passes - 1) / passes;
   int nt = (per + 31) / 32;
   if (nt > 4) nt = 4;
-  static int big = -1;
-  if (big < 0) { const char* e = getenv("UDA_PW_BIG"); big = e ? atoi(e) : 0; }
+  static const int big = uda_env_int("UDA_PW_BIG", 0);
   // 256-pixel blocks (8 waves) halve the weight-tile traffic per pixel; measured 6 % slower on the deep layers (off)
   if (big && a.Cin >= 80 && a.HW >= 256) launch_pw_nw<8>(a, rows, nt, s);
   else launch_pw_nw<4>(a, rows, nt, s);
@@ -1065,9 +1063,7 @@ __global__ __launch_bounds__(NW * 64) void mbx_kernel(MbxArgs a) {
 }
 
 bool mbx_supported(int Cin, int Cmid, int k, int stride) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("UDA_FUSE_MBX"); on = e ? atoi(e) : 1; }
-  return on && Cin % 8 == 0 && Cin >= 16 && Cin <= 48 && Cmid % 4 == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2);
+  return Cin % 8 == 0 && Cin >= 16 && Cin <= 48 && Cmid % 4 == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2);
 }
 
 int mbx_tiles(int Ho, int Wo, int k, int stride) {
@@ -1103,8 +1099,7 @@ static void launch_mbx_nw(const MbxArgs& a, int rows, hipStream_t s) {
 
 template <int K, int S>
 static void launch_mbx_ks(const MbxArgs& a, int rows, hipStream_t s) {
-  static int nw = -1;
-  if (nw < 0) { const char* e = getenv("UDA_MBX_WAVES"); nw = e ? atoi(e) : 4; }
+  static const int nw = uda_env_int("UDA_MBX_WAVES", 4);
   if (nw == 4) launch_mbx_nw<K, S, 4>(a, rows, s);
   else launch_mbx_nw<K, S, 8>(a, rows, s);
 }
@@ -1112,8 +1107,7 @@ static void launch_mbx_ks(const MbxArgs& a, int rows, hipStream_t s) {
 void launch_mbx(const MbxArgs& a0, int rows, int k, int stride, hipStream_t s) {
   MbxArgs a = a0;
   static unsigned long long* d_stamps = nullptr;
-  static int want = -1;
-  if (want < 0) { const char* e = getenv("UDA_MBX_STAMPS"); want = e ? atoi(e) : 0; }
+  static const int want = uda_env_int("UDA_MBX_STAMPS", 0);
   if (want) {   // diagnostic: dump the stamps of the previous launch, then arm this one
     static unsigned long long h[8 * 2 * 64];
     if (!d_stamps) { hipMalloc((void**)&d_stamps, sizeof(h)); hipMemset(d_stamps, 0, sizeof(h)); }

@@ -804,8 +804,7 @@ __global__ __launch_bounds__(128) void aggregate_reg2_kernel(AggArgs a) {
 
 void launch_aggregate(const AggArgs& a0, hipStream_t s) {
   AggArgs a = a0;
-  static int regs = -1;
-  if (regs < 0) { const char* e = getenv("UDA_AGG_REG"); regs = e ? atoi(e) : 1; }
+  static const int regs = uda_env_int("UDA_AGG_REG", 1);
   const bool sample = a.loss_att && a.decode == UDA_DECODE_SAMPLE;      // the (slow, optional) sampling decode: LDS-parking kernel only
   if (regs && !sample && a.Tc == a.Tb && (a.Tc == 10 || a.Tc == 20)) {
     const int64_t tot = (int64_t)a.n_img * a.K;
@@ -1095,8 +1094,7 @@ size_t topk_workspace_bytes(int n_img, int k) {
 }
 
 void launch_topk(const float* vals, int n_img, int L, int k, int32_t* out_idx, void* ws, hipStream_t s) {
-  static int multi = -1;
-  if (multi < 0) { const char* e = getenv("UDA_TOPK_MULTI"); multi = e ? atoi(e) : 1; }
+  static const int multi = uda_env_int("UDA_TOPK_MULTI", 1);
   // few images per launch and a long value list: spread each image over the device; many images: one block each is enough
   // (UDA_TOPK_MULTI=2: also for short lists - test hook; 0: never)
   if (!multi || !ws || L > (1 << 21) || (L < (1 << 16) && multi != 2) || n_img > 64 || k > TOPK_MAX) {
@@ -2736,8 +2734,7 @@ int launch_nms_coop(const NmsArgs& a, const float* scores, unsigned long long* s
   // so a small batch is spread over more, shorter blocks: the smallest IPT with which every block of the launch still has
   // a CU to itself; a batch that fills the device anyway takes 32 (fewest blocks per problem, most problems per launch).
   // UDA_NMS_COOP_IPT = 4 | 8 | 16 | 24 | 32 forces one.
-  static int force = -1;
-  if (force < 0) { const char* e = getenv("UDA_NMS_COOP_IPT"); force = e ? atoi(e) : 0; }
+  static const int force = uda_env_int("UDA_NMS_COOP_IPT", 0);
   const int ipts[5] = {4, 8, 16, 24, 32};
   int ipt = 0, bpi = 0, capacity = 0;
   for (int i = 0; i < 5 && !ipt; ++i) {
@@ -2765,8 +2762,7 @@ int launch_nms_coop(const NmsArgs& a, const float* scores, unsigned long long* s
   // the runners-up sit next to the maximum) and on every clustered score map, so extra winners are rarely certified while
   // the looser bound (the W-th largest of the blocks' offers) has every block evaluate more: 3.47 ms (1) / 3.66 (2) / 4.3 (4) /
   // 32 ms (8 of 8 blocks: the bound of the weakest block) per 32-image step
-  static int wenv = -1;
-  if (wenv < 0) { const char* e = getenv("UDA_NMS_WINNERS"); wenv = e ? atoi(e) : 0; }
+  static const int wenv = uda_env_int("UDA_NMS_WINNERS", 0);
   int wcfg = wenv > 0 ? wenv : 1;
   if (wcfg > COOP_W) wcfg = COOP_W;
   if (wcfg < 1) wcfg = 1;

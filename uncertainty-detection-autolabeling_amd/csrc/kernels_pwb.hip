@@ -589,7 +589,7 @@ static void launch_pwb_cfg(const PwArgs& a, int rows, hipStream_t s) {
   }
   else if (a.wparts == UDA_SPLIT_F16X2) {
     // (K-heavy projections on the big tiles - two blocks per CU by registers anyway: two chunks in flight per block)
-    static const bool deep_on = !(getenv("UDA_PWB_DEEP") && atoi(getenv("UDA_PWB_DEEP")) == 0);
+    static const bool deep_on = (uda_env_int("UDA_PWB_DEEP", 1) != 0);
     if constexpr (MT * NT > 4) {
       if (deep_on && a.Cin >= 384 && a.Cin % PWB_BK == 0 && a.Cout % BN == 0 && (2 * NT * WN * 2 * 64) % 256 == 0) { hipLaunchKernelGGL((pwb_kernel<MT, NT, WM, WN, 4, 2, true>), grid, block, 0, s, a); return; }
     }
@@ -601,18 +601,15 @@ static void launch_pwb_cfg(const PwArgs& a, int rows, hipStream_t s) {
 // tile = 128 pixels x {32, 64, 96, 128, 160, 192} channels (four waves stacked along the pixels for narrow outputs and
 // for 160, 2 x 2 waves of 64 x 64 / 64 x 96 for 128 / 192)
 void launch_pwb(const PwArgs& a, int rows, hipStream_t s) {
-  static int shared = -1;
-  if (shared < 0) { const char* e = getenv("UDA_PW_SHARED"); shared = e ? atoi(e) : 1; }
+  static const int shared = uda_env_int("UDA_PW_SHARED", 1);
   if (shared && a.in_div > 1 && a.Cin <= 32 && a.Cout <= 32 && (a.Cout & 3) == 0 && a.wparts == 2 && rows % a.in_div == 0) {
     const dim3 grid((a.HW + 127) / 128, 1, rows / a.in_div);
     hipLaunchKernelGGL(pwb_shared_kernel, grid, dim3(256), 0, s, a);
     return;
   }
   if (launch_pws(a, rows, s)) return;
-  static int force = -1;
-  if (force < 0) { const char* e = getenv("UDA_PWB_CFG"); force = e ? atoi(e) : 0; }
-  static int wide = -1;
-  if (wide < 0) { const char* e = getenv("UDA_PWB_WIDE"); wide = e ? atoi(e) : 1; }
+  static const int force = uda_env_int("UDA_PWB_CFG", 0);
+  static const int wide = uda_env_int("UDA_PWB_WIDE", 1);
   int cfg = force;
   if (cfg == 0) {
     cfg = a.Cout <= 32 ? 1 : (a.Cout <= 64 ? 2 : (a.Cout <= 96 ? 3 : 4));
@@ -701,10 +698,7 @@ __host__ __device__ constexpr MbxCfgB mbxb_cfg(int k, int s) {
   // input tile (with halo) = 8 slices of 32 pixels, two per wave: 3x3 s1 12x16 (14x18 = 252), 3x3 s2 7x8
   // (15x17 = 255: 224 of the 256 expanded pixels belong to the tile proper; 4x12 -> 9x25 = 225 had 192), 5x5 s2 4x10
   // (11x23 = 253), 5x5 s1 8x16 (12x20 = 240)
-#ifndef UDA_MBXB_S2_TILE
-#define UDA_MBXB_S2_TILE 78
-#endif
-  return s == 1 ? (k == 3 ? MbxCfgB{12, 16} : MbxCfgB{8, 16}) : (k == 3 ? (UDA_MBXB_S2_TILE == 78 ? MbxCfgB{7, 8} : MbxCfgB{4, 12}) : MbxCfgB{4, 10});
+  return s == 1 ? (k == 3 ? MbxCfgB{12, 16} : MbxCfgB{8, 16}) : (k == 3 ? MbxCfgB{7, 8} : MbxCfgB{4, 10});
 }
 }  // namespace
 
@@ -1151,8 +1145,7 @@ static void launch_mbxb_t(const MbxArgs& a, int rows, hipStream_t s) {
                      (size_t)KSF * split_np(PARTS) * 64 * sizeof(uint4);
   dim3 grid((a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH, rows);
   MbxArgs b = a;
-  static int remap = -1;
-  if (remap < 0) { const char* e = getenv("UDA_MBX_REMAP"); remap = e ? atoi(e) : 1; }
+  static const int remap = uda_env_int("UDA_MBX_REMAP", 1);
   b.remap_T = 0;
   if (remap && a.in_div > 1 && rows % a.in_div == 0) {      // input shared by the samples of an image: XCD-grouped 1-D grid
     const long long nt = (long long)grid.x * grid.y, ntp = (nt + 7) / 8 * 8;
@@ -1228,9 +1221,7 @@ __host__ __device__ constexpr long long mbxd_slots(int Ho, int Wo, int k, bool w
          ((Wo + mbxd_cfg(k, 1, wide).tw - 1) / mbxd_cfg(k, 1, wide).tw) * mbxd_cfg(k, 1, wide).tw;
 }
 bool mbxd_wide(int Ho, int Wo, int k, int stride) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("UDA_MBXD_WIDE"); on = e ? atoi(e) : 1; }
-  return on && stride == 1 && mbxd_slots(Ho, Wo, k, true) < mbxd_slots(Ho, Wo, k, false);
+  return stride == 1 && mbxd_slots(Ho, Wo, k, true) < mbxd_slots(Ho, Wo, k, false);
 }
 
 // One fp16 piece (PARTS = UDA_SPLIT_F16X1): the operand fragments of 13-14 k-steps are 56 registers instead of 112, so the deep
@@ -1919,8 +1910,7 @@ size_t mbx_lds_bytes(int Cin, int Cmid, int k, int stride, int scheme, int Ho, i
     const int etw = mbx_et_w(k, stride);
     return ((etw ? (size_t)32 * mbx_et_pitch(etw) : (size_t)npp * 32) + 8 * 32 + 2 * par) * sizeof(float) + (size_t)ksf * npc * 64 * sizeof(uint4);
   }
-  static int pipe = -1;
-  if (pipe < 0) { const char* e = getenv("UDA_MBXP"); pipe = e ? atoi(e) : 1; }
+  static const int pipe = uda_env_int("UDA_MBXP", 1);
   const bool wide = mbxd_wide(Ho, Wo, k, stride);
   const bool p2 = pipe && stride == 1 && ksf >= 13 && npc == 2 && !(scheme == UDA_SPLIT_F16X2 && k == 3 && !wide);      // mbxp_kernel
   if (p2) return ((size_t)2 * 256 * 33 + 2 * 16 * 32 + 3 * par + 2 * 32 * nch) * sizeof(float) + (size_t)2 * ksf * 2 * 64 * sizeof(uint4);
@@ -1928,15 +1918,9 @@ size_t mbx_lds_bytes(int Cin, int Cmid, int k, int stride, int scheme, int Ho, i
 }
 
 bool mbxd_supported(int Cin, int Cmid, int k, int stride) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("UDA_FUSE_MBXD"); on = e ? atoi(e) : 1; }
-  static int s2 = -1;            // UDA_FUSE_MBXD_S2=0: stride-2 deep blocks run unfused (1x1 expand + depthwise), as before round 3
-  if (s2 < 0) { const char* e = getenv("UDA_FUSE_MBXD_S2"); s2 = e ? atoi(e) : 1; }
   const int ksf = (Cin + 1 + 15) / 16;
-  static int maxksf = -1;
-  if (maxksf < 0) { const char* e = getenv("UDA_MBXD_MAXKSF"); maxksf = e ? atoi(e) : 14; }
-  return on && (stride == 1 || (stride == 2 && s2)) && (k == 3 || k == 5) && Cin % 8 == 0 && Cin > 48 &&
-         (ksf == 6 || ksf == 8 || ksf == 13 || ksf == 14) && ksf <= maxksf && Cmid % 4 == 0;
+  return (stride == 1 || stride == 2) && (k == 3 || k == 5) && Cin % 8 == 0 && Cin > 48 &&
+         (ksf == 6 || ksf == 8 || ksf == 13 || ksf == 14) && Cmid % 4 == 0;
 }
 
 int mbxd_tiles(int Ho, int Wo, int k, int stride) {
@@ -2002,8 +1986,7 @@ void launch_mbxd(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
     else launch_mbxd_p<2, 2>(a, rows, k, ksf, s);
     return;
   }
-  static int pipe = -1;
-  if (pipe < 0) { const char* e = getenv("UDA_MBXP"); pipe = e ? atoi(e) : 1; }
+  static const int pipe = uda_env_int("UDA_MBXP", 1);
   if (a.wparts == UDA_SPLIT_BF16X3) {     // six cross terms: three pieces per operand, the two-phase kernel
     launch_mbxd_p<3, 1>(a, rows, k, ksf, s);
     return;

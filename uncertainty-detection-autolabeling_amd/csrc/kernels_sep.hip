@@ -713,8 +713,7 @@ __global__ __launch_bounds__(256, (PC == 16 && NT <= 2) ? 3 : 2) void sepf_kerne
 // 2x larger map, where 64-byte pieces of a pixel doubled the traffic (half-used 128-byte lines): 32-channel passes.
 // UDA_SEPF_PC = 16 | 32 forces one (A/B).
 static int sepf_pc(int sig) {
-  static int epc = -1;
-  if (epc < 0) { const char* e = getenv("UDA_SEPF_PC"); epc = e ? atoi(e) : 0; }
+  static const int epc = uda_env_int("UDA_SEPF_PC", 0);
   return epc == 16 || epc == 32 ? epc : ((sig == SF_SIG_PLAIN || sig == SF_SIG_NU) ? 16 : 32);
 }
 
@@ -814,7 +813,7 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
   if (lds < stg) lds = stg;
   SepMulti mm = m;
   mm.tiles = m.n_lv > 0 ? m.tile0[m.n_lv] : sep_tiles(a.H, a.W);
-  static const bool remap = !(getenv("UDA_SEP_REMAP") && atoi(getenv("UDA_SEP_REMAP")) == 0);     // (0: plain block order, A/B)
+  static const bool remap = (uda_env_int("UDA_SEP_REMAP", 1) != 0);     // (0: plain block order, A/B)
   if (tin) rows /= a.in_div;
   mm.rows = remap ? rows : 0;
   const dim3 grid(mm.tiles * rows, gy);
@@ -826,8 +825,7 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
     }
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, mm);
   };
-  static int occ = -1;
-  if (occ < 0) { const char* e = getenv("UDA_SEP_OCC"); occ = e ? atoi(e) : 3; }   // 3 blocks per CU: measured 14 % faster than 2
+  static const int occ = uda_env_int("UDA_SEP_OCC", 3);   // 3 blocks per CU: measured 14 % faster than 2
   if (tin) {
     // (head layers: C = F, Cout = F | 9 C | 36 / 72: two to four column tiles; 32 / 64 more registers than the plain kernel)
     if constexpr (NT >= 2) {

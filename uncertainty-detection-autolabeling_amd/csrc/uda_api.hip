@@ -39,7 +39,7 @@ struct uda_ctx {
   uint16_t* d_wsplit = nullptr;
   std::vector<int64_t> wsplit_off;
   std::vector<int64_t> wpar_off;   // MBX: offset (uint16 units) of the per-slab depthwise operand block inside d_wsplit
-  int pw_parts = UDA_SPLIT_F16X2;  // requested split scheme of the 1x1 contractions (UDA_PW_SCHEME / UDA_PW_TERMS, parse_pw_scheme)
+  int pw_parts = UDA_SPLIT_F16X2;  // requested split scheme of the 1x1 contractions (uda_model_t.pw_scheme)
   std::vector<int> wscheme;        // per op: the scheme its packed weights use (an op whose weights do not suit fp16 pieces keeps bf16 x3)
   std::vector<float> wunscale;     // per op: 1 / (power-of-two factor folded into the packed weights); 1 unless fp16 pieces
   std::vector<float> wascale;      // per op: factor on the A operand (fp16 separable conv: pre-scaled depthwise taps); part of wunscale
@@ -256,28 +256,6 @@ static hipError_t dalloc(T** p, size_t n) {
   return hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
 }
 
-// UDA_PW_SCHEME = f16x2 | bf16x3 | bf16x2 | f32 | f16 (mirror: plan.pw_scheme); the older UDA_PW_TERMS = 6 | 3 | 0 names three of them
-static int parse_pw_scheme(std::string* err) {
-  const char* v = getenv("UDA_PW_SCHEME");
-  if (v && *v) {
-    if (!strcmp(v, "f16x2")) return UDA_SPLIT_F16X2;
-    if (!strcmp(v, "bf16x3")) return UDA_SPLIT_BF16X3;
-    if (!strcmp(v, "bf16x2")) return UDA_SPLIT_BF16X2;
-    if (!strcmp(v, "f32")) return UDA_SPLIT_NONE;
-    if (!strcmp(v, "f16")) return UDA_SPLIT_F16X1;
-    if (err) *err = std::string("UDA_PW_SCHEME=") + v + ": expected f16x2, bf16x3, bf16x2, f32 or f16";
-    return -1;
-  }
-  const char* t = getenv("UDA_PW_TERMS");
-  if (!t || !*t) return UDA_SPLIT_F16X2;
-  const int terms = atoi(t);
-  if (terms == 0) return UDA_SPLIT_NONE;
-  if (terms == 6) return UDA_SPLIT_BF16X3;
-  if (terms == 3) return UDA_SPLIT_BF16X2;
-  if (err) *err = std::string("UDA_PW_TERMS=") + t + ": expected 6, 3 or 0";
-  return -1;
-}
-
 static inline int same_pad_before(int in, int out, int k, int s) {
   int total = (out - 1) * s + k - in;
   if (total < 0) total = 0;
@@ -420,8 +398,7 @@ static hipError_t alloc_nms_ws(uda_ctx::NmsWs& w, size_t problems, size_t K, siz
 
 // UDA_NMS_SOLO = candidates per problem up to which the single-launch NMS kernel is used directly (0 = never)
 static int solo_limit() {
-  static int solo = -1;
-  if (solo < 0) { const char* e = getenv("UDA_NMS_SOLO"); solo = e ? atoi(e) : 8192; }
+  static const int solo = uda_env_int("UDA_NMS_SOLO", 8192);
   return solo;
 }
 
@@ -484,6 +461,9 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
     return fail(nullptr, "uda_create: chunk_images/max_images/mc_samples must be >= 1");
   if (model->decode_method == UDA_DECODE_SAMPLE && (model->decode_nsamples < 1 || model->decode_nsamples > 4096))
     return fail(nullptr, "uda_create: decode_nsamples %d outside [1, 4096]", model->decode_nsamples);
+  if (model->pw_scheme != UDA_SPLIT_NONE && model->pw_scheme != UDA_SPLIT_BF16X2 && model->pw_scheme != UDA_SPLIT_BF16X3 &&
+      model->pw_scheme != UDA_SPLIT_F16X2 && model->pw_scheme != UDA_SPLIT_F16X1)
+    return fail(nullptr, "uda_create: pw_scheme %d is not a uda_pw_scheme (0 f32, 2 bf16x2, 3 bf16x3, 4 f16x2, 5 f16)", model->pw_scheme);
   if (model->mc_samples > 96)      // the aggregate kernel parks T logits + 4 T box corners per candidate in LDS
     return fail(nullptr, "uda_create: mc_samples %d > 96 unsupported", model->mc_samples);
   int ndev = 0;
@@ -606,9 +586,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
   CK(hipMemcpy(c->d_weights, weights, (size_t)n_weights * sizeof(float), hipMemcpyHostToDevice));
   {
     // split-precision copies of every 1x1 kernel, packed once (host) in B-fragment order
-    std::string perr;
-    c->pw_parts = parse_pw_scheme(&perr);
-    if (c->pw_parts < 0) { fail(nullptr, "uda_create: %s", perr.c_str()); uda_destroy(c); return 1; }
+    c->pw_parts = m.pw_scheme;
     c->wsplit_off.assign(n_ops, -1);
     c->wpar_off.assign(n_ops, -1);
     c->wscheme.assign(n_ops, c->pw_parts);
@@ -621,8 +599,6 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
     c->wovr.assign(n_ops, nullptr);
     c->wovr_par.assign(n_ops, -1);
     c->h_weights.assign(weights, weights + n_weights);
-    const char* em = getenv("UDA_MBX_BF16");
-    const bool mbx_bf16 = em ? atoi(em) != 0 : true;
     if (c->pw_parts) {
       std::vector<uint16_t> packed;
       for (int i = 0; i < n_ops; ++i) {
@@ -656,7 +632,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
           size_t dw_fl = 0;
           float ascale = 1.0f;
           if (o.kind == UDA_OP_SEP && uda_split_f16(sch) && o.w2_off >= 0) {
-            static const int shift = getenv("UDA_F16_SEP_SHIFT") ? atoi(getenv("UDA_F16_SEP_SHIFT")) : 6;
+            static const int shift = uda_env_int("UDA_F16_SEP_SHIFT", 6);
             ascale = ldexpf(1.0f, shift < 0 ? 0 : (shift > 12 ? 12 : shift));
             dw_fl = (size_t)9 * K;
           }
@@ -670,7 +646,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
             c->wunscale[i] /= ascale;
             c->wascale[i] = ascale;
           }
-        } else if (o.kind == UDA_OP_MBX && mbx_bf16 && o.bn_scale_off >= 0 && o.bn_shift_off >= 0 &&
+        } else if (o.kind == UDA_OP_MBX && o.bn_scale_off >= 0 && o.bn_shift_off >= 0 &&
                    (mbxb_supported(o.se_scale >= 0 ? o.se_mid : K, Nn, o.k, o.stride) || mbxd_supported(K, Nn, o.k, o.stride))) {
           if (o.w2_off < 0 || o.bn2_scale_off < 0 || o.bn2_shift_off < 0) continue;
           const bool fuse0 = o.se_scale >= 0;      // the previous block's projection is computed in this op's prologue
@@ -1303,7 +1279,7 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
           a.c0 = ib.C;
           a.w0t = a.wpar + mbx_par_floats(ob.C, o.k);
           a.sh0f = a.w0t + 32 * 32;
-          static const bool pre = !(getenv("UDA_W0GATE") && atoi(getenv("UDA_W0GATE")) == 0);   // 0: every block redoes the prep
+          static const bool pre = (uda_env_int("UDA_W0GATE", 1) != 0);   // 0: every block redoes the prep
           if (pre && ib.C == 32) {
             // one buffer per chunk lane: with UDA_LANES=2 consecutive chunks run concurrently on two streams, each with its
             // own gates - lane 1's prep must not overwrite the fragments lane 0's block-1 kernel is still reading
@@ -1330,7 +1306,7 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
     }
     case UDA_OP_SEP: {
       const uda_buf_desc_t& ib = c->bufs[o.in[0]];
-      if (c->wsplit_off[oi] < 0) return fail(c, "op %d: fused separable conv needs the split-bf16 path (UDA_PW_TERMS != 0)", oi);
+      if (c->wsplit_off[oi] < 0) return fail(c, "op %d: fused separable conv needs a split scheme (pw_scheme != f32)", oi);
       SepArgs a{};
       a.in = v.ptr(o.in[0]);
       a.out = v.ptr(o.out);
@@ -1362,7 +1338,7 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
         break;
       }
       if (ib.H != ob.H || ib.W != ob.W) return fail(c, "op %d: separable conv changes the map size", oi);
-      static const int sepf_all = getenv("UDA_SEPF_ALL") ? atoi(getenv("UDA_SEPF_ALL")) : 0;     // A/B: the tile kernel for every conv
+      static const int sepf_all = uda_env_int("UDA_SEPF_ALL", 0);     // A/B: the tile kernel for every conv
       if (sepf_all && sepf_supported(a.C, a.Cout, a.wparts)) launch_sepf(a, nullptr, rows, v.stream());
       else launch_sep(a, rows, v.stream());
       break;
@@ -1408,9 +1384,7 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
 // ops[oi .. oi + n): the separable convs of one head layer on all pyramid levels (uda_op_t.launch_group) as ONE launch.
 // Returns -1 when the run does not qualify (the caller then executes the ops one by one), 0 on success, > 0 on failure.
 static int run_sep_group(uda_ctx* c, const ChunkView& v, int oi, int n) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("UDA_SEP_MULTI"); on = e ? atoi(e) : 1; }
-  if (!on || n < 2 || n > UDA_SEP_MAX_LV || oi + n > (int)c->ops.size()) return -1;
+  if (n < 2 || n > UDA_SEP_MAX_LV || oi + n > (int)c->ops.size()) return -1;
   const uda_op_t& o0 = c->ops[oi];
   const uda_buf_desc_t& ib0 = c->bufs[o0.in[0]];
   const uda_buf_desc_t& ob0 = c->bufs[o0.out];
@@ -1508,7 +1482,7 @@ static int run_network(uda_ctx* c, int post_mode = 0, bool chunk_post = false, h
   // 32-image batch) are skipped; UDA_STEM_U8=0 restores the separate pass
   bool stem_u8 = false;
   if (c->have_u8) {
-    static const bool on = !(getenv("UDA_STEM_U8") && atoi(getenv("UDA_STEM_U8")) == 0);
+    static const bool on = (uda_env_int("UDA_STEM_U8", 1) != 0);
     const uda_ctx::U8Slot& sl = c->u8[c->cur];
     stem_u8 = on && c->noise_from < 0 && c->stem_co > 0 && stem_u8_supported(c->stem_co) && c->stem_act == UDA_ACT_SWISH;
     for (int i = 0; i < n && stem_u8; ++i) stem_u8 = sl.geo[i].sh == sl.geo[i].h && sl.geo[i].sw == sl.geo[i].w;
@@ -1554,7 +1528,7 @@ static int run_network(uda_ctx* c, int post_mode = 0, bool chunk_post = false, h
         gated = true;
       }
       const int grp = c->ops[oi].launch_group;
-      static const bool sepf_all_ = getenv("UDA_SEPF_ALL") && atoi(getenv("UDA_SEPF_ALL"));     // A/B: per-level tile-kernel launches
+      static const bool sepf_all_ = (uda_env_int("UDA_SEPF_ALL", 0) != 0);     // A/B: per-level tile-kernel launches
       if (grp > 1 && !sepf_all_) {
         const int rg = run_sep_group(c, v, oi, grp);
         if (rg > 0) return rg;
@@ -1635,8 +1609,7 @@ static bool run_nms(const NmsArgs& na, const float* scores, int M, hipStream_t s
   // all chunks in parallel, is 4x faster (measured: 35 vs 7.9 ms for 32 images).  UDA_NMS_SOLO = candidates per
   // problem up to which the single-launch kernel is used (0 = never).
   const int solo = solo_limit();
-  static int reg = -1;
-  if (reg < 0) { const char* e = getenv("UDA_NMS_REG"); reg = e ? atoi(e) : 1; }
+  static const int reg = uda_env_int("UDA_NMS_REG", 1);
   if (na.K <= solo && reg && nms_reg_supported(na)) {
     launch_nms_reg(na, scores, st);
     return false;
@@ -1646,8 +1619,7 @@ static bool run_nms(const NmsArgs& na, const float* scores, int M, hipStream_t s
     return false;
   }
   // The whole set: all epochs in one launch of a co-resident grid when the device holds it (UDA_NMS_COOP=0: never) ...
-  static int coop_on = -1;
-  if (coop_on < 0) { const char* e = getenv("UDA_NMS_COOP"); coop_on = e ? atoi(e) : 1; }
+  static const int coop_on = uda_env_int("UDA_NMS_COOP", 1);
   if (coop_on && coop.bar && coop.err) {
     const int lc = launch_nms_coop(na, scores, coop.bar + p0 * nms_coop_slot_words(M), coop.err, st);
     if (lc > 0) {
@@ -1892,7 +1864,7 @@ static void set_f16_storage(uda_ctx* c) {
 // Re-pack op `oi` (and the ops that share its launch: the pyramid levels of a head layer) with three bf16 pieces.
 static int demote_ops(uda_ctx* c, int oi) {
   const int n_ops = (int)c->ops.size();
-  if (oi < 0 || oi >= n_ops) return fail(c, "fp16 range flag outside the op list (word %d): re-create the handle with UDA_PW_SCHEME=bf16x3", oi);
+  if (oi < 0 || oi >= n_ops) return fail(c, "fp16 range flag outside the op list (word %d): re-create the handle with pw_scheme bf16x3", oi);
   int g0 = oi, g1 = oi + 1;
   for (int i = 0; i < n_ops; ++i) {
     const int lg = c->ops[i].launch_group;
@@ -1912,19 +1884,19 @@ static int demote_ops(uda_ctx* c, int oi) {
       lds = o.fuse_in ? sepf_lds_bytes(K, Nn, sch) : sep_lds_bytes(K, Nn, sch, tin);
       if (o.fuse_in && !sepf_supported(K, Nn, sch))
         return fail(c, "op %d raised the fp16 range flag and has no three-piece kernel (fused-input separable conv %d -> %d): "
-                       "re-create the handle with UDA_PW_SCHEME=bf16x3", i, K, Nn);
+                       "re-create the handle with pw_scheme bf16x3", i, K, Nn);
       // (fp16 pieces need less LDS than three bf16 pieces, one or two of them: a deferred-input conv that fits them may
       // have no three-piece deferred-input mode - D2's 112 -> 112 head layers under head-only MC dropout)
       if (tin && !sep_tin_supported(K, Nn, sch))
         return fail(c, "op %d raised the fp16 range flag and its deferred-input separable conv %d -> %d has no three-piece kernel: "
-                       "re-create the handle with UDA_PW_SCHEME=bf16x3", i, K, Nn);
+                       "re-create the handle with pw_scheme bf16x3", i, K, Nn);
     } else if (o.kind == UDA_OP_MBX) {
       const int Ke = o.se_scale >= 0 ? o.se_mid : K;
       lds = mbx_lds_bytes(Ke, Nn, o.k, o.stride, sch, c->bufs[o.out].H, c->bufs[o.out].W);
     }
     if (lds > (size_t)160 * 1024)
       return fail(c, "op %d raised the fp16 range flag and its three-piece launch needs %zu bytes of LDS (a CU has 163840): "
-                     "re-create the handle with UDA_PW_SCHEME=bf16x3", i, lds);
+                     "re-create the handle with pw_scheme bf16x3", i, lds);
   }
   int done = 0;      // (0: re-packed already - a pipelined run queued before that demotion raised the same flag)
   for (int i = g0; i < g1 && i < n_ops; ++i) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/uda_hip.h"
 
@@ -68,15 +69,15 @@ __device__ __forceinline__ float act_relu_family(float v, int act) {
 }
 #endif
 
+// An executor knob of the environment (A/B switches, test hooks; DESIGN.md 7 lists them): the integer value of `name`, `dflt` when
+// unset.  Call sites keep the result in a function-local static, i.e. read it once per process.
+static inline int uda_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 // ---------------------------------------------------------------- split-precision schemes of the 1x1 contractions
-// (`wparts` of the argument blocks below = PARTS of the kernels; see mfma_common.h)
-enum {
-  UDA_SPLIT_NONE = 0,     // exact f32-input MFMA kernels (kernels_conv.hip)
-  UDA_SPLIT_BF16X2 = 2,   // two bf16 pieces per operand, three cross terms (~2^-17 per product)
-  UDA_SPLIT_BF16X3 = 3,   // three bf16 pieces, six cross terms (~2^-24)
-  UDA_SPLIT_F16X2 = 4,    // two fp16 pieces, three cross terms (~2^-22; operands must stay below 65504)
-  UDA_SPLIT_F16X1 = 5,    // one fp16 piece, one product (~2^-11: Keras mixed_float16 operands; same range limit)
-};
+// (`wparts` of the argument blocks below = PARTS of the kernels; see mfma_common.h): enum uda_pw_scheme of uda_hip.h
 inline int uda_split_pieces(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : (scheme == UDA_SPLIT_F16X1 ? 1 : 2); }
 inline bool uda_split_f16(int scheme) { return scheme == UDA_SPLIT_F16X2 || scheme == UDA_SPLIT_F16X1; }   // fp16 pieces: range-tracked
 

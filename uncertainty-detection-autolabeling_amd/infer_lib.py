@@ -105,27 +105,10 @@ class ServingDriver:
         self.weights = weights
         if chunk_images is None:
             chunk_images = min(self._plan_images, int(self.params.get("uda_chunk_images", 16)))
-        # `uda_pw_scheme` in model_params (f16x2 | bf16x3 | bf16x2 | f32 | f16): the split scheme of THIS handle's 1x1 contractions.  The
-        # planner and uda_create both read UDA_PW_SCHEME when they run; the key sets it for exactly that long (a
-        # per-handle choice instead of a process-wide environment variable).
-        import os
-        want = self.params.get("uda_pw_scheme")
-        saved = (os.environ.get("UDA_PW_SCHEME"), os.environ.get("UDA_PW_TERMS"))
-        if want:
-            if want not in plan_mod.PW_SCHEMES:
-                raise ValueError("uda_pw_scheme=%r: expected one of %s" % (want, ", ".join(plan_mod.PW_SCHEMES)))
-            os.environ["UDA_PW_SCHEME"] = want
-            os.environ.pop("UDA_PW_TERMS", None)
-        try:
-            self.pw_scheme = plan_mod.pw_scheme()
-            self._create(weights, chunk_images, post_only, post_mode, device)
-        finally:
-            if want:
-                for k, v in zip(("UDA_PW_SCHEME", "UDA_PW_TERMS"), saved):
-                    if v is None:
-                        os.environ.pop(k, None)
-                    else:
-                        os.environ[k] = v
+        # `uda_pw_scheme` in model_params (f16x2 | bf16x3 | bf16x2 | f32 | f16): the split scheme of THIS handle's 1x1 contractions,
+        # default plan.pw_scheme().  The Plan resolves and validates it (ValueError) and hands it to uda_create in the model struct.
+        self._create(weights, chunk_images, post_only, post_mode, device)
+        self.pw_scheme = self.plan.pw_scheme
         self.device = int(device)
         self.image_size = hparams_config.parse_image_size(self.params["image_size"])
         self.T = self.plan.T

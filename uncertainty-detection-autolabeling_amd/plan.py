@@ -15,6 +15,8 @@ What the lowering adds over the reference's graph:
     pre-normalised (relu(w_i)/(sum+1e-4), efficientdet_keras.py:101-108).
   * activation memory is planned by liveness into one arena per chunk of images.
 """
+import os
+
 import numpy as np
 
 from . import arch, capi
@@ -51,15 +53,22 @@ def dw_tiles(C, Ho, Wo, k, stride):
 
 PW_SCHEMES = ("f16x2", "bf16x3", "bf16x2", "f32", "f16")
 PW_SCHEME_DEFAULT = "f16x2"
+PW_SCHEME_CODES = {"f32": 0, "bf16x2": 2, "bf16x3": 3, "f16x2": 4, "f16": 5}     # enum uda_pw_scheme of include/uda_hip.h
+
+# The planner's on/off switches (environment, read once per Plan into Plan.sw) and their defaults; "0" turns a fusion off.  The
+# library reads none of them: an op the planner does not emit / a launch_group it does not set is what turns a fusion off.
+PLAN_SWITCHES = {"UDA_DEFER_DROPOUT": 1, "UDA_FUSE_SEP": 1, "UDA_FUSE_PROJ": 1, "UDA_FUSE_MBX": 1, "UDA_FUSE_MBX6": 1,
+                 "UDA_FUSE_MBXD": 1, "UDA_FUSE_MBXD_S2": 1, "UDA_MBXD_MAXKSF": 14, "UDA_FUSE_IN": 1, "UDA_DEFER_HEAD": 1,
+                 "UDA_SEP_MULTI": 1}
 
 
 def pw_scheme():
-    """Split scheme of the 1x1 contractions (mirror of parse_pw_scheme in csrc/uda_api.hip): UDA_PW_SCHEME =
+    """DEFAULT split scheme of the 1x1 contractions, for a handle whose params carry no `uda_pw_scheme` (the one reader of these
+    two variables; the library learns the scheme from uda_model_t.pw_scheme): UDA_PW_SCHEME =
     f16x2 (two fp16 pieces, three cross terms, ~2^-22 per product: the default) | bf16x3 (three bf16 pieces, six terms,
     ~2^-24) | bf16x2 (two bf16 pieces, three terms, ~2^-17) | f32 (exact f32-input MFMA kernels, unfused) | f16 (ONE fp16
     piece, one product, ~2^-11: the operands of Keras mixed_float16, fp32 accumulation; opt-in, see split_pieces);
     the older UDA_PW_TERMS = 6 | 3 | 0 selects the last three when UDA_PW_SCHEME is not set."""
-    import os
     v = os.environ.get("UDA_PW_SCHEME")
     if v:
         if v not in PW_SCHEMES:
@@ -79,72 +88,55 @@ def split_pieces(sch):
     return {"bf16x3": 3, "f16": 1}.get(sch, 2)
 
 
+# The predicates below are pure functions of shape and split scheme `sch` ("a kernel exists for this shape"), mirrors of the
+# library's; the switches that turn a fusion off although a kernel exists are applied by Plan (Plan.sw).
 def mbx_deep(cin):
     """Cin > 48: the deep variant of the fused kernel (mbxd_kernel in csrc/kernels_pwb.hip)."""
     return cin > 48
 
 
-def mbx_tile(k, stride, cin=16, Ho=None, Wo=None):
-    """(TH, TW) output tile of the fused expand+depthwise kernels (mirror of mbx_cfg / mbxd_cfg / mbxd_wide in csrc)."""
+def mbx_tile(k, stride, cin, Ho, Wo, sch):
+    """(TH, TW) output tile of the fused expand+depthwise kernels (mirror of mbx_cfg / mbxb_cfg / mbxd_cfg / mbxd_wide in csrc)."""
     if mbx_deep(cin):       # mirror of mbxd_cfg
         if stride == 1:
-            import os
             normal, wide = ((12, 16), (8, 20)) if k == 3 else ((8, 16), (6, 20))
-            if Ho is not None and int(os.environ.get("UDA_MBXD_WIDE", "1")):
-                slots = lambda t: -(-Ho // t[0]) * t[0] * -(-Wo // t[1]) * t[1]
-                if slots(wide) < slots(normal):      # mbxd_wide: 20-column tiles cover the map with fewer output slots
-                    return wide
-            return normal
+            slots = lambda t: -(-Ho // t[0]) * t[0] * -(-Wo // t[1]) * t[1]
+            return wide if slots(wide) < slots(normal) else normal   # mbxd_wide: 20-column tiles cover the map with fewer output slots
         return (7, 8) if k == 3 else (4, 10)
-    import os
-    if pw_scheme() == "f32" or not int(os.environ.get("UDA_MBX_BF16", "1")):
-        return (8, 16) if stride == 1 else ((4, 16) if k == 3 else (4, 8))      # f32-MFMA fallback kernel (mbx_cfg)
-    s2_k3 = (7, 8) if os.environ.get("UDA_MBXB_S2_TILE", "78") == "78" else (4, 12)     # (A/B builds: -DUDA_MBXB_S2_TILE=412)
-    return ((12, 16) if k == 3 else (8, 16)) if stride == 1 else (s2_k3 if k == 3 else (4, 10))
+    if sch == "f32":
+        return (8, 16) if stride == 1 else ((4, 16) if k == 3 else (4, 8))      # exact-f32 kernel (mbx_cfg)
+    return ((12, 16) if k == 3 else (8, 16)) if stride == 1 else ((7, 8) if k == 3 else (4, 10))
 
 
-def mbx_tiles(Ho, Wo, k, stride, cin=16):
-    th, tw = mbx_tile(k, stride, cin, Ho, Wo)
+def mbx_tiles(Ho, Wo, k, stride, cin, sch):
+    th, tw = mbx_tile(k, stride, cin, Ho, Wo, sch)
     return -(-Ho // th) * -(-Wo // tw)
 
 
-def mbx_supported(cin, cmid, k, stride):
-    import os
-    if not (int(os.environ.get("UDA_FUSE_MBX", "1")) and cin % 8 == 0 and cmid % 4 == 0 and k in (3, 5)):
+def mbx_supported(cin, cmid, k, stride, sch):
+    """A fused expand+depthwise kernel exists (mirror of mbx_supported / mbxb_supported / mbxd_supported in csrc)."""
+    if not (cin % 8 == 0 and cmid % 4 == 0 and k in (3, 5) and stride in (1, 2)):
         return False
-    if pw_scheme() == "bf16x3" and not int(os.environ.get("UDA_FUSE_MBX6", "1")):
-        # six cross terms = float32-equivalent products EVERYWHERE.  The fused MBConv kernels have three-piece variants
-        # (mbxb_kernel / mbxd_kernel<..., PARTS = 3>, csrc/kernels_pwb.hip) and stay fused; UDA_FUSE_MBX6=0 restores the
-        # round-2 behaviour (stand-alone six-term 1x1 convs + depthwise) for A/B runs
-        return False
-    if mbx_deep(cin):       # mirror of mbxd_supported: 16-deep k-steps of Cin + 1 in {6, 8, 13, 14}, split-bf16 path on
-        return (int(os.environ.get("UDA_FUSE_MBXD", "1")) and pw_scheme() != "f32"
-                and int(os.environ.get("UDA_MBX_BF16", "1"))
-                and (stride == 1 or (stride == 2 and int(os.environ.get("UDA_FUSE_MBXD_S2", "1"))))
-                and (cin + 1 + 15) // 16 in (6, 8, 13, 14)
-                and (cin + 1 + 15) // 16 <= int(os.environ.get("UDA_MBXD_MAXKSF", "14")))
-    return 16 <= cin and stride in (1, 2)
+    if mbx_deep(cin):       # 16-deep k-steps of Cin + 1 in {6, 8, 13, 14}, split path only
+        return sch != "f32" and (cin + 1 + 15) // 16 in (6, 8, 13, 14)
+    return 16 <= cin
 
 
-def sepf_supported(C, Cout):
+def sepf_supported(C, Cout, sch):
     """The BiFPN fusion of a node can be computed inside its separable conv (mirror of sepf_supported / sepf_lds_bytes in
     csrc/kernels_sep.hip: an 18 x 18 x (32 + 4) float32 tile + the weight fragments of two k-steps, two blocks per CU)."""
-    import os
-    sch = pw_scheme()
-    if sch == "f32" or not int(os.environ.get("UDA_FUSE_IN", "1")):
+    if sch == "f32":
         return False
     npc = split_pieces(sch)
     lds = 18 * 18 * 36 * 4 + 2 * (-(-Cout // 32)) * npc * 1024
     return C % 8 == 0 and 16 <= C <= 128 and Cout % 4 == 0 and 4 <= Cout <= 128 and lds <= 80 * 1024
 
 
-def sep_tin_supported(C, Cout, sch=None):
+def sep_tin_supported(C, Cout, sch):
     """A plain separable conv can take a DEFERRED dropout site of its producer (mirror of sep_tin_supported in
     csrc/kernels_sep.hip): 64 .. 128 input channels, two to four 32-column tiles in one block, the per-sample epilogue staging
-    inside the A image.  `sch`: the split scheme (default: the handle's, pw_scheme())."""
-    import os
-    sch = pw_scheme() if sch is None else sch
-    if sch == "f32" or not int(os.environ.get("UDA_DEFER_HEAD", "1")):
+    inside the A image."""
+    if sch == "f32":
         return False
     if C % 8 or not 64 <= C <= 128 or Cout < 1:
         return False
@@ -309,11 +301,16 @@ class Plan:
         self.sites = []          # (name, channels, rate)
         self.site_index = {}
         self.buffer_names = {}
-        import os
-        self.defer_dropout = bool(int(os.environ.get("UDA_DEFER_DROPOUT", "1")))
-        self.fuse_sep = bool(int(os.environ.get("UDA_FUSE_SEP", "1"))) and pw_scheme() != "f32"
-        self.fuse_proj = (bool(int(os.environ.get("UDA_FUSE_PROJ", "1"))) and pw_scheme() != "f32"
-                          and bool(int(os.environ.get("UDA_MBX_BF16", "1"))) and bool(int(os.environ.get("UDA_FUSE_MBX", "1"))))
+        self.pw_scheme = self.cfg.get("uda_pw_scheme") or pw_scheme()      # this handle's split scheme: its params, else the default
+        if self.pw_scheme not in PW_SCHEMES:
+            raise ValueError("uda_pw_scheme=%r: expected one of %s" % (self.pw_scheme, ", ".join(PW_SCHEMES)))
+        sw = self.sw = {k: int(os.environ.get(k, d)) for k, d in PLAN_SWITCHES.items()}
+        split = self.pw_scheme != "f32"
+        self.defer_dropout = bool(sw["UDA_DEFER_DROPOUT"])
+        self.fuse_sep = bool(sw["UDA_FUSE_SEP"]) and split
+        self.fuse_proj = bool(sw["UDA_FUSE_PROJ"]) and split and bool(sw["UDA_FUSE_MBX"])
+        self.fuse_in = self.fuse_sep and bool(sw["UDA_FUSE_IN"])          # BiFPN fusion inside the node's separable conv
+        self.defer_head = self.fuse_sep and bool(sw["UDA_DEFER_HEAD"])    # head dropout site handed to the next layer
         if self.post_only:
             self._post_only_layout()
             return
@@ -446,7 +443,7 @@ class Plan:
                 kw["bn_scale_off"], kw["bn_shift_off"] = self._bn(bn)
             return self._op(capi.OP_SEP, list(fusion["ins"]), out, **kw)
         xb = self.bufs[x]
-        assert in_site < 0 or (self.fuse_sep and sep_tin_supported(xb.C, cout) and not xb.per_sample), "deferred site without a taker"
+        assert in_site < 0 or (self.defer_head and sep_tin_supported(xb.C, cout, self.pw_scheme) and not xb.per_sample), "deferred site without a taker"
         if not (self.fuse_sep and xb.C % 8 == 0 and 16 <= xb.C <= 128):
             d, _ = self._dw(x, 3, 1, dw_kernel, name + "/dw")
             return self._pw(d, cout, pw_kernel, name, bias=bias, bn=bn, act=act, site=site, out_kind=out_kind, level=level)
@@ -465,9 +462,8 @@ class Plan:
         shape class (same channels, activation, sample axes) and mutually independent, the first one is marked with their
         count: the executor may run them as one launch.  _plan_memory keeps every buffer the run touches alive to its end
         (concurrent problems must not reuse each other's freed inputs)."""
-        import os
         run = self.ops[first:]
-        if len(run) < 2 or len(run) > 8 or not int(os.environ.get("UDA_SEP_MULTI", "1")):
+        if len(run) < 2 or len(run) > 8 or not self.sw["UDA_SEP_MULTI"]:
             return
         if any(o["kind"] != capi.OP_SEP for o in run):
             return
@@ -481,6 +477,17 @@ class Plan:
         if any(o["ins"][0] in outs for o in run) or len(outs) != len(run):
             return
         run[0]["launch_group"] = len(run)
+
+    def _fuse_mbx(self, cin, cmid, k, stride):
+        """The block's expand + depthwise are lowered to one fused op: a kernel exists and no switch turns it off."""
+        sw, ksf = self.sw, (cin + 1 + 15) // 16
+        if not sw["UDA_FUSE_MBX"] or (self.pw_scheme == "bf16x3" and not sw["UDA_FUSE_MBX6"]):
+            # (six cross terms: the fused kernels have three-piece variants and stay fused; UDA_FUSE_MBX6=0 restores the
+            # round-2 behaviour - stand-alone six-term 1x1 convs + depthwise - for A/B runs)
+            return False
+        if mbx_deep(cin) and not (sw["UDA_FUSE_MBXD"] and (stride == 1 or sw["UDA_FUSE_MBXD_S2"]) and ksf <= sw["UDA_MBXD_MAXKSF"]):
+            return False
+        return mbx_supported(cin, cmid, k, stride, self.pw_scheme)
 
     def _resample(self, x, th, tw, prefix, name):
         """ResampleFeatureMap.call: optional 1x1+BN to F channels, then (mode for the consumer)."""
@@ -524,7 +531,7 @@ class Plan:
             deferred = -1
             mid = b["cin"] * b["expand"]
             swish = self.act == capi.ACT_SWISH     # the fused MBConv kernels fold the swish into their BN scales: other activations stay unfused
-            if b["expand"] != 1 and swish and mbx_supported(b["cin"], mid, b["kernel"], b["stride"]):
+            if b["expand"] != 1 and swish and self._fuse_mbx(b["cin"], mid, b["kernel"], b["stride"]):
                 # fused expand + depthwise: the expanded tensor stays on-chip
                 xb = self.bufs[x]
                 Ho, Wo = same_out(xb.H, b["stride"]), same_out(xb.W, b["stride"])
@@ -545,7 +552,7 @@ class Plan:
                 kw["bn_scale_off"], kw["bn_shift_off"] = self._bn(bn_names[0])
                 kw["bn2_scale_off"], kw["bn2_shift_off"] = self._bn(bn_names[1])
                 if b["se"]:
-                    part = self._buf(mbx_tiles(Ho, Wo, b["kernel"], b["stride"], b["cin"]), 1, mid, ps,
+                    part = self._buf(mbx_tiles(Ho, Wo, b["kernel"], b["stride"], b["cin"], self.pw_scheme), 1, mid, ps,
                                      name="blocks_%d/dw/se_partial" % i)
                     kw["se_partial"] = part
                 x = self._op(capi.OP_MBX, [x], out, **kw)
@@ -581,7 +588,7 @@ class Plan:
             nxt = blocks[i + 1] if i + 1 < len(blocks) else None
             absorb = (self.fuse_proj and swish and nxt is not None and b["expand"] == 1 and gate >= 0 and not b["skip"] and b["cout"] == 16
                       and nxt["cin"] == 16 and nxt["expand"] != 1 and not nxt["skip"] and self.bufs[x].C <= 32
-                      and mbx_supported(16, 16 * nxt["expand"], nxt["kernel"], nxt["stride"])
+                      and self._fuse_mbx(16, 16 * nxt["expand"], nxt["kernel"], nxt["stride"])
                       and (i not in red_ids or len([r for r in red_ids if r <= i]) < cfg["min_level"]))
             if absorb:
                 # the next block's fused kernel computes this projection in its prologue: the 16-channel tensor is never stored
@@ -642,7 +649,7 @@ class Plan:
                 op = p + "op_after_combine%d" % nf
                 fuse_act, conv_act = (capi.ACT_NONE, self.act) if cba else (self.act, capi.ACT_NONE)
                 bias = None if cba else op + "/conv/bias"       # use_bias = not conv_bn_act_pattern (:218)
-                if self.fuse_sep and sepf_supported(F, F):
+                if self.fuse_in and sepf_supported(F, F, self.pw_scheme):
                     # the fusion is computed inside the node's separable conv: no fused tensor, no fuse launch
                     cell.append(self._sepconv(None, F, op + "/conv/depthwise_kernel", op + "/conv/pointwise_kernel",
                                               "cell%d/fnode%d/out" % (rep, n), bias=bias, bn=op + "/bn", act=conv_act,
@@ -687,7 +694,7 @@ class Plan:
                     # (T == 1 included - a rank of a sample-sharded serve may run ONE sample: the position of the multiply
                     # must not depend on how many samples a handle runs, or the shards would differ in the last bit)
                     defer = (site >= 0 and pending[li] < 0 and not self.bufs[xs[li]].per_sample
-                             and self.fuse_sep and sep_tin_supported(F, next_cout))
+                             and self.defer_head and sep_tin_supported(F, next_cout, self.pw_scheme))
                     xs[li] = self._sepconv(xs[li], F, pre + "/depthwise_kernel", pre + "/pointwise_kernel",
                                            "%s-%d-%d" % (tag, i, lo + li), bias=pre + "/bias",
                                            bn="%s/%s-%d-bn-%d" % (net, tag, i, lo + li), act=self.act,
@@ -858,6 +865,7 @@ class Plan:
         m.chunk_images, m.max_images = self.chunk_images, self.max_images
         m.arena_floats = self.arena_floats
         m.n_drop_sites = len(self.sites)
+        m.pw_scheme = PW_SCHEME_CODES[self.pw_scheme]
 
         bufs = (capi.BufDesc * len(self.bufs))()
         for i, b in enumerate(self.bufs):
@@ -887,12 +895,12 @@ class Plan:
         return m, bufs, ops, sites, blob, self.anchors()
 
     def mark_f16_storage(self):
-        """Under the one-piece scheme (pw_scheme() == "f16") the output of a fused MBConv front half is stored as fp16 when every
+        """Under the one-piece scheme (self.pw_scheme == "f16") the output of a fused MBConv front half is stored as fp16 when every
         reference to it is the input of a 1x1 conv (its projection) or the geometry-only input of its SE op - mirror of set_f16_storage in csrc/uda_api.hip, which also
         keeps float32 where uda_create or a range demotion gives either side another scheme."""
         for b in self.bufs:
             b.storage = "f32"
-        if pw_scheme() != "f16":
+        if self.pw_scheme != "f16":
             return
         refs, ok = [0] * len(self.bufs), [0] * len(self.bufs)
         for o in self.ops:
