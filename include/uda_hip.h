@@ -18,6 +18,8 @@
  *                            (infer_lib.py:263-267)
  *   uda_assign_ground_truth <- the gt_box_assigner walk of the validate / calibrate modes over the ground-truth rows
  *                            (utils_extra.py:44-64; validate_model.py:314-470, calibrate_model.py:133-190)
+ *   uda_score_images      <- ActiveLearning.score_image's per-detection numbers and per-image mean / max
+ *                            (active_learning_loop.py:528-733)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -338,6 +340,62 @@ int uda_assigned_row_cols(const uda_ctx_t* ctx, int32_t* cols);
 int uda_assign_gt_np(int32_t device, const float* det_boxes, const float* gt_boxes, const float* gt_classes, int32_t n,
                      int32_t M, int32_t G, int32_t method, int32_t keep, int32_t* det_index, double* iou, int32_t* count);
 
+/* Active-learning image scores: what the reference's active-learning loop does with the detections of the unlabeled pool
+ * (ActiveLearning.score_image, active_learning_loop.py:528-733, on the lines Infer.iterate_infer wrote, infer_model.py:836-960) -
+ * one to three uncertainty numbers per detection above min_score, reduced per image with mean or max - done on the detections
+ * RESIDENT in the handle after a global post-process (uda_run / uda_collect, all 4n images of uda_run_consistency, an
+ * ensemble's uda_postprocess_heads).  The dataset-wide part (:733-840) is the caller's (active_learning.py).
+ * A row is kept iff score > min_score (the writer's filter; padded rows score 0).  A component of a kept row is
+ * w0 * term0 (+ w1 * term1); a term is a source under a transform:
+ *   UDA_SCORE_SCALAR    the value itself                                   (ENTROPY, DET_SCORE)
+ *   UDA_SCORE_MEAN      the mean of the 4 (box) or the class-std columns   (ALBOX, MCBOX, MCCLASS)
+ *   UDA_SCORE_REL_MEAN  relativize_uncert (utils_box.py:279-292): entries 0 and 2 divided by y2 - y1, entries 1 and 3 by
+ *                       x2 - x1, then the mean of the four                 (ALBOX, MCBOX)
+ * Every input is converted to float64 first and everything after that is float64; on float32 columns np.nan_to_num (NaN -> 0,
+ * +-inf -> +-FLT_MAX) is applied to ALBOX / MCBOX / MCCLASS before the conversion (infer_model.py:607-631).  A zero side length
+ * divides as IEEE does; NaN propagates through mean and max alike (np.max).  The reduction over the kept rows has a fixed order,
+ * so equal values give bit-identical results on both entry points. */
+enum uda_score_source { UDA_SCORE_ENTROPY = 0, UDA_SCORE_DET_SCORE = 1, UDA_SCORE_ALBOX = 2, UDA_SCORE_MCBOX = 3, UDA_SCORE_MCCLASS = 4 };
+enum uda_score_transform { UDA_SCORE_SCALAR = 0, UDA_SCORE_MEAN = 1, UDA_SCORE_REL_MEAN = 2 };
+#define UDA_SCORE_MAX_COMP 3
+typedef struct uda_score_term {
+  int32_t source;     /* uda_score_source */
+  int32_t transform;  /* uda_score_transform */
+  double weight;
+} uda_score_term_t;
+typedef struct uda_score_desc {
+  int32_t n_comp;                        /* 1..UDA_SCORE_MAX_COMP */
+  int32_t reduce_mean;                   /* 1: mean over the kept rows, 0: max */
+  int32_t n_terms[UDA_SCORE_MAX_COMP];   /* 1 or 2 per component */
+  int32_t reserved;
+  uda_score_term_t term[UDA_SCORE_MAX_COMP][2];
+} uda_score_desc_t;
+/*   uda_score_images      queues the softmax / entropy kernel of uda_get_class_probs when a component reads ENTROPY, then the
+ *                         score kernel, on the handle's stream; forces the deferred fix-ups every reader of detections forces.
+ *                         Refuses: no global post-process yet, a per-class run, a pipelined run still in flight, a source the
+ *                         model does not emit (ENTROPY without enable_softmax, ALBOX without loss attenuation, MCBOX / MCCLASS
+ *                         without MC dropout on that head), max_output_size above 4096.
+ *   uda_image_scores_shape  n (images of the scored run) and n_comp of the last uda_score_images.
+ *   uda_get_image_scores  components [n, n_comp] float64 (0 where nothing is kept), count [n] int32 kept rows, class_counts
+ *                         [n, num_classes] int32 kept rows per class id 1..num_classes; one copy; any pointer may be NULL.  A kept
+ *                         row whose class id is not one of 1..num_classes is an error. */
+int uda_score_images(uda_ctx_t* ctx, const uda_score_desc_t* desc, float min_score);
+int uda_image_scores_shape(const uda_ctx_t* ctx, int32_t* n, int32_t* n_comp);
+int uda_get_image_scores(uda_ctx_t* ctx, double* components, int32_t* count, int32_t* class_counts);
+/* The same scores without a handle, in the manner of uda_assign_gt_np: float64 host arrays boxes [n, M, 4], scores [n, M],
+ * classes [n, M]; optional (NULL: absent, a descriptor that reads it is refused) entropy [n, M], albox / mcbox [n, M, 4],
+ * mcclass [n, M, mcclass_cols]; the same kernel in its float64 instantiation (no nan_to_num: the caller's columns are
+ * finite), the same outputs.  For calibrated columns and for callers that hold detections of their own.  M <= 4096.
+ * uda_score_images_np_f32: the same on float32 arrays, through the instantiation the handle runs. */
+int uda_score_images_np(int32_t device, const uda_score_desc_t* desc, double min_score, const double* boxes, const double* scores,
+                        const double* classes, const double* entropy, const double* albox, const double* mcbox,
+                        const double* mcclass, int32_t n, int32_t M, int32_t num_classes, int32_t mcclass_cols,
+                        double* components, int32_t* count, int32_t* class_counts);
+int uda_score_images_np_f32(int32_t device, const uda_score_desc_t* desc, float min_score, const float* boxes, const float* scores,
+                            const float* classes, const float* entropy, const float* albox, const float* mcbox,
+                            const float* mcclass, int32_t n, int32_t M, int32_t num_classes, int32_t mcclass_cols,
+                            double* components, int32_t* count, int32_t* class_counts);
+
 /* serve = set_images_u8 + run + get_detections */
 int uda_serve(uda_ctx_t* ctx, const uint8_t* images, int32_t n, int32_t h, int32_t w,
               float* boxes, float* scores, float* classes, int32_t* valid, float* logits);
@@ -437,7 +495,8 @@ int uda_per_class_nms_np(int32_t device, const float* boxes, const float* scores
                          float iou_thresh, float sigma, float score_thresh, float* out);
 
 /* Per-op-kind device timing with HIP events recorded on the handle's stream.
- * kind_mask: bit (1 << uda_op_kind) selects op kinds; bit 16 post-process aggregate, bit 17 NMS. */
+ * kind_mask: bit (1 << uda_op_kind) selects op kinds; bit 16 post-process aggregate, bit 17 NMS, bit 19 the score kernel of
+ * uda_score_images (with its softmax / entropy kernel when ENTROPY is read). */
 int uda_profile_enable(uda_ctx_t* ctx, uint32_t kind_mask);
 int uda_profile_read(uda_ctx_t* ctx, int32_t kind, double* total_ms, int64_t* launches, int32_t reset);
 

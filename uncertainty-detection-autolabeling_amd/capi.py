@@ -27,7 +27,10 @@ CALIB_TS_ALL, CALIB_TS_PERCOO, CALIB_ISO_ALL, CALIB_ISO_PERCOO, CALIB_ISO_PERCLS
 CLS_TS, CLS_ISO_ALL, CLS_ISO_PERCLS = 0, 1, 2
 ASSIGN_IOU, ASSIGN_MSE, ASSIGN_RANK = 0, 1, 2
 ASSIGN_KEEP_VALIDATE, ASSIGN_KEEP_CALIBRATE = 0, 1
-PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS = 16, 17, 18
+SCORE_ENTROPY, SCORE_DET_SCORE, SCORE_ALBOX, SCORE_MCBOX, SCORE_MCCLASS = 0, 1, 2, 3, 4
+SCORE_SCALAR, SCORE_MEAN, SCORE_REL_MEAN = 0, 1, 2
+SCORE_MAX_COMP = 3
+PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS, PROF_SCORE = 16, 17, 18, 19
 
 
 class BufDesc(C.Structure):
@@ -66,6 +69,16 @@ class Model(C.Structure):
                 ("post_mode", C.c_int32), ("chunk_images", C.c_int32), ("max_images", C.c_int32),
                 ("arena_floats", C.c_int64), ("n_drop_sites", C.c_int32), ("decode_nsamples", C.c_int32),
                 ("pw_scheme", C.c_int32)]
+
+
+class ScoreTerm(C.Structure):
+    _fields_ = [("source", C.c_int32), ("transform", C.c_int32), ("weight", C.c_double)]
+
+
+class ScoreDesc(C.Structure):
+    """uda_score_desc_t: per component one or two (source, transform, weight) terms; mean or max over the kept rows."""
+    _fields_ = [("n_comp", C.c_int32), ("reduce_mean", C.c_int32), ("n_terms", C.c_int32 * SCORE_MAX_COMP),
+                ("reserved", C.c_int32), ("term", (ScoreTerm * 2) * SCORE_MAX_COMP)]
 
 
 _P = C.c_void_p
@@ -112,6 +125,13 @@ _SIGNATURES = {
     "uda_get_assigned_rows": (C.c_int, [_P, _P, C.c_int64]),
     "uda_assigned_row_cols": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "uda_assign_gt_np": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "uda_score_images": (C.c_int, [_P, C.POINTER(ScoreDesc), C.c_float]),
+    "uda_image_scores_shape": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "uda_get_image_scores": (C.c_int, [_P, _P, _P, _P]),
+    "uda_score_images_np": (C.c_int, [C.c_int32, C.POINTER(ScoreDesc), C.c_double, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, _P, _P, _P]),
+    "uda_score_images_np_f32": (C.c_int, [C.c_int32, C.POINTER(ScoreDesc), C.c_float, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, _P, _P, _P]),
     "uda_calibrate_box": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "uda_calibrate_class": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, _P]),
     "uda_serve": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),

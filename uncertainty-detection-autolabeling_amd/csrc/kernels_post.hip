@@ -344,6 +344,124 @@ void launch_gather_assigned(const AssignRowsArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(gather_assigned_kernel, dim3((unsigned)a.n), dim3(256), (size_t)(a.G > 0 ? a.G : 1) * sizeof(int), s, a);
 }
 
+// ------------------------------------------------------------------------------------ active-learning image scores
+// ActiveLearning.score_image (active_learning_loop.py:528-733) without the text file in between: per kept detection one to three
+// uncertainty numbers, per image their mean or max.  One block of 256 threads per image over all M rows; a row is kept iff
+// score > min_score in the input type (np.where(scores[0] > min_score), infer_model.py:836; padded rows score 0).
+// A component of a row is w0 * term0 (+ w1 * term1, the `combo` strategy); a term is a source under a transform (uda_hip.h).
+// Every input is converted to double first.  The float instantiation cleans ALBOX / MCBOX / MCCLASS as np.nan_to_num does in
+// float32 (infer_model.py:607-631) before that; the double one reads the caller's columns as they are.
+// The sums of a row follow numpy's add.reduce of a contiguous float64 vector (sum_np) - np.mean of the 4 relativized entries
+// and of the C class stds.
+// The reduction over the rows has a fixed order: the thread's rows ascending, an xor butterfly inside the wave, the four waves
+// in wave order through LDS; NaN wins every max, as in np.max.  No float atomics: class_counts are integer LDS adds.
+__device__ __forceinline__ double score_in(float v) {
+  if (v != v) return 0.0;
+  if (v == __builtin_inff()) return (double)3.402823466e+38f;
+  if (v == -__builtin_inff()) return -(double)3.402823466e+38f;
+  return (double)v;
+}
+__device__ __forceinline__ double score_in(double v) { return v; }
+
+// np.add.reduce over the contiguous float64 vector v[0 .. n), n <= 128: numpy's pairwise_sum - sequential below 8 elements, 8
+// running sums combined as a tree above, the n % 8 last elements added one by one.  (Beyond 128 elements numpy splits the
+// vector in halves first; this keeps the 8 running sums, which differs by rounding only.)
+template <typename T>
+__device__ double sum_np(const T* v, int n) {
+  if (n < 8) {
+    double res = score_in(v[0]);
+    for (int i = 1; i < n; ++i) res += score_in(v[i]);
+    return res;
+  }
+  double r[8];
+  for (int j = 0; j < 8; ++j) r[j] = score_in(v[j]);
+  int i = 8;
+  for (; i < n - (n % 8); i += 8)
+    for (int j = 0; j < 8; ++j) r[j] += score_in(v[i + j]);
+  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += score_in(v[i]);
+  return res;
+}
+
+template <typename T>
+__device__ double score_term(const ScoreArgs<T>& a, size_t row, int source, int transform) {
+  if (source == UDA_SCORE_ENTROPY) return (double)a.entropy[row];
+  if (source == UDA_SCORE_DET_SCORE) return (double)a.scores[row];
+  if (source == UDA_SCORE_MCCLASS) return sum_np(a.mcclass + row * a.mcc_stride, a.mcc_w) / (double)a.mcc_w;
+  const T* u = source == UDA_SCORE_ALBOX ? a.albox + row * a.al_stride : a.mcbox + row * a.mc_stride;
+  double v[4] = {score_in(u[0]), score_in(u[1]), score_in(u[2]), score_in(u[3])};
+  if (transform == UDA_SCORE_REL_MEAN) {
+    const T* b = a.boxes + row * a.box_stride;
+    const double h = (double)b[2] - (double)b[0], w = (double)b[3] - (double)b[1];
+    v[0] /= h; v[1] /= w; v[2] /= h; v[3] /= w;
+  }
+  return sum_np(v, 4) / 4.0;
+}
+
+__device__ __forceinline__ double max_np(double a, double b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void score_images_kernel(ScoreArgs<T> a) {
+  extern __shared__ int cls_cnt[];         // [C]
+  __shared__ double wave_acc[4][UDA_SCORE_MAX_COMP];
+  __shared__ int wave_cnt[4];
+  const int i = blockIdx.x, M = a.M, C = a.C, nc = a.desc.n_comp;
+  const bool mean = a.desc.reduce_mean != 0;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) cls_cnt[c] = 0;
+  __syncthreads();
+  double acc[UDA_SCORE_MAX_COMP];
+  for (int k = 0; k < UDA_SCORE_MAX_COMP; ++k) acc[k] = mean ? 0.0 : -(double)__builtin_inff();
+  int cnt = 0;
+  for (int r = threadIdx.x; r < M; r += blockDim.x) {
+    const size_t row = (size_t)i * M + r;
+    if (!(a.scores[row] > a.min_score)) continue;
+    ++cnt;
+    const double cid = (double)a.classes[row * a.cls_stride];
+    const int ci = cid >= 1.0 && cid <= (double)C ? (int)cid : 0;
+    if (ci < 1 || (double)ci != cid) *a.err = 1;
+    else atomicAdd(&cls_cnt[ci - 1], 1);
+#pragma unroll
+    for (int k = 0; k < UDA_SCORE_MAX_COMP; ++k) {         // (unrolled: acc stays in registers)
+      if (k >= nc) break;
+      const uda_score_term_t* t = a.desc.term[k];
+      double v = t[0].weight * score_term(a, row, t[0].source, t[0].transform);
+      if (a.desc.n_terms[k] > 1) v = v + t[1].weight * score_term(a, row, t[1].source, t[1].transform);
+      acc[k] = mean ? acc[k] + v : max_np(acc[k], v);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int k = 0; k < UDA_SCORE_MAX_COMP; ++k) {
+      const double other = __shfl_xor(acc[k], o);
+      acc[k] = mean ? acc[k] + other : max_np(acc[k], other);
+    }
+    cnt += __shfl_xor(cnt, o);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    for (int k = 0; k < UDA_SCORE_MAX_COMP; ++k) wave_acc[wave][k] = acc[k];
+    wave_cnt[wave] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int total = (wave_cnt[0] + wave_cnt[1]) + (wave_cnt[2] + wave_cnt[3]);
+    for (int k = 0; k < nc; ++k) {
+      double v = wave_acc[0][k];
+      for (int w = 1; w < 4; ++w) v = mean ? v + wave_acc[w][k] : max_np(v, wave_acc[w][k]);
+      a.comp[(size_t)i * nc + k] = total ? (mean ? v / (double)total : v) : 0.0;
+    }
+    a.count[i] = total;
+  }
+  for (int c = threadIdx.x; c < C; c += blockDim.x) a.class_counts[(size_t)i * C + c] = cls_cnt[c];
+}
+
+template <typename T>
+static void launch_score_images_t(const ScoreArgs<T>& a, hipStream_t s) {
+  if (a.n <= 0) return;
+  hipLaunchKernelGGL(score_images_kernel<T>, dim3((unsigned)a.n), dim3(256), (size_t)(a.C > 0 ? a.C : 1) * sizeof(int), s, a);
+}
+void launch_score_images(const ScoreArgs<float>& a, hipStream_t s) { launch_score_images_t(a, s); }
+void launch_score_images(const ScoreArgs<double>& a, hipStream_t s) { launch_score_images_t(a, s); }
+
 // ------------------------------------------------------------------------------------ aggregate + decode
 __device__ __forceinline__ float exp32(float x) { return (float)exp((double)x); }
 

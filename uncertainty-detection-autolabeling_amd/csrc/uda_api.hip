@@ -199,6 +199,12 @@ struct uda_ctx {
   int gt_cap = 0, gt_n = 0, gt_G = 0; // rows per image the buffers hold; images / rows per image of the GT that is set (0: none)
   int asg_n = 0, asg_G = 0;          // images / rows per image of the last assignment (0: none)
   int64_t asg_rows = -1;             // sum(count) of the last assignment once the host has seen it
+  // active-learning image scores (uda_score_images), packed for max_images so that ONE copy brings them to the host:
+  // components [n, n_comp] float64 | count [n] int32 | class_counts [n, num_classes] int32 | error flag int32
+  char* d_score_pack = nullptr;
+  std::vector<char> h_score;         // host copy of the pack (filled by the first reader of a scoring)
+  int score_n = 0, score_nc = 0;     // images / components of the last scoring (0: none)
+  bool score_fetched = false;
   int last_post_mode = 0;
   int last_n = 0;
   int last_chunk_i0 = 0, last_chunk_n = 0;
@@ -338,7 +344,7 @@ extern "C" void uda_destroy(uda_ctx_t* c) {
                   c->d_cclasses, c->d_ucls, c->d_ual, c->d_uep, c->d_clsmean, c->d_cand_flat, c->d_merge_keys,
                   c->d_oboxes, c->d_oscores, c->d_oclasses, c->d_ologits, c->d_ovalid, c->d_oprobs, c->d_oentropy,
                   c->d_opacked, c->d_cons_iou, c->d_cons_agree, c->d_gt_boxes, c->d_gt_classes, c->d_asg_pack,
-                  c->d_asg_rows};
+                  c->d_asg_rows, c->d_score_pack};
   if (c->h_gt) hipHostFree(c->h_gt);
   if (c->gt_ev) hipEventDestroy(c->gt_ev);
   for (void* p : ptrs)
@@ -2751,6 +2757,189 @@ extern "C" int uda_assign_gt_np(int32_t device, const float* det_boxes, const fl
   if (e != hipSuccess) return fail(nullptr, "uda_assign_gt_np: %s", hipGetErrorString(e));
   if (err) return fail(nullptr, "uda_assign_gt_np: the rank method met a kept ground-truth row beyond the %d detections", M);
   return 0;
+}
+
+// ---- active-learning image scores (reference active_learning_loop.py:528-733 on the lines of infer_model.py:836-960)
+static const int kScoreMaxM = 4096, kScoreMaxC = 8192;      // rows a block walks; class counters in LDS (4 bytes each)
+
+// what a descriptor reads: bit (1 << uda_score_source); 0 with *why set when it is malformed
+static unsigned score_desc_sources(const uda_score_desc_t* d, const char** why) {
+  *why = nullptr;
+  if (!d) { *why = "NULL descriptor"; return 0; }
+  if (d->n_comp < 1 || d->n_comp > UDA_SCORE_MAX_COMP) { *why = "n_comp outside 1..3"; return 0; }
+  unsigned mask = 0;
+  for (int k = 0; k < d->n_comp; ++k) {
+    if (d->n_terms[k] < 1 || d->n_terms[k] > 2) { *why = "a component has 1 or 2 terms"; return 0; }
+    for (int t = 0; t < d->n_terms[k]; ++t) {
+      const int src = d->term[k][t].source, tr = d->term[k][t].transform;
+      const bool scalar = src == UDA_SCORE_ENTROPY || src == UDA_SCORE_DET_SCORE;
+      const bool box = src == UDA_SCORE_ALBOX || src == UDA_SCORE_MCBOX;
+      if (!scalar && !box && src != UDA_SCORE_MCCLASS) { *why = "unknown source"; return 0; }
+      if (scalar ? tr != UDA_SCORE_SCALAR : !(tr == UDA_SCORE_MEAN || (box && tr == UDA_SCORE_REL_MEAN))) {
+        *why = "transform does not fit the source (SCALAR: entropy / det_score; MEAN: albox / mcbox / mcclass; REL_MEAN: albox / mcbox)";
+        return 0;
+      }
+      mask |= 1u << src;
+    }
+  }
+  return mask;
+}
+
+static size_t score_pack_bytes(size_t n, size_t nc, size_t C) { return n * nc * sizeof(double) + (n + n * C + 1) * sizeof(int32_t); }
+
+extern "C" int uda_score_images(uda_ctx_t* c, const uda_score_desc_t* desc, float min_score) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  const char* why = nullptr;
+  const unsigned need = score_desc_sources(desc, &why);
+  if (why) return fail(c, "score_images: %s", why);
+  if (c->as[0].open || c->as[1].open)
+    return fail(c, "score_images: a pipelined run (uda_run_async) is in flight - uda_collect it first");
+  if (c->last_n < 1) return fail(c, "score_images: no global post-process has run yet");
+  if (c->last_post_mode != UDA_POST_GLOBAL)
+    return fail(c, "score_images: the last post-process ran per class; the scores read the global post-process");
+  if ((need & (1u << UDA_SCORE_ENTROPY)) && !m.enable_softmax)
+    return fail(c, "score_images: the model emits no entropy (enable_softmax is off)");
+  if ((need & (1u << UDA_SCORE_ALBOX)) && !(m.has_uncert && m.loss_attenuation))
+    return fail(c, "score_images: the model emits no aleatoric box uncertainty (no loss attenuation)");
+  if ((need & (1u << UDA_SCORE_MCBOX)) && !(m.has_uncert && m.box_stacked))
+    return fail(c, "score_images: the model emits no epistemic box uncertainty (no MC dropout on the box head)");
+  if ((need & (1u << UDA_SCORE_MCCLASS)) && !(m.has_uncert && m.cls_stacked))
+    return fail(c, "score_images: the model emits no epistemic class uncertainty (no MC dropout on the class head)");
+  if (m.max_output_size > kScoreMaxM) return fail(c, "score_images: max_output_size %d above %d", m.max_output_size, kScoreMaxM);
+  if (m.num_classes < 1 || m.num_classes > kScoreMaxC) return fail(c, "score_images: num_classes %d outside 1..%d", m.num_classes, kScoreMaxC);
+  HIPC(c, hipSetDevice(c->device));
+  if (int rc = finish_post(c)) return rc;      // range replay / prefix redo / NMS fallback: the scores read final detections
+  const int n = c->last_n, M = m.max_output_size, C = m.num_classes, nc = desc->n_comp;
+  if (!c->d_score_pack) HIPC(c, dalloc(&c->d_score_pack, score_pack_bytes((size_t)m.max_images, UDA_SCORE_MAX_COMP, (size_t)C)));
+  {
+    ProfScope ps(c, 19);
+    if (need & (1u << UDA_SCORE_ENTROPY)) {
+      if (!c->d_oprobs) {
+        const size_t N = (size_t)m.max_images;
+        HIPC(c, dalloc(&c->d_oprobs, N * M * C));
+        HIPC(c, dalloc(&c->d_oentropy, N * M));
+      }
+      launch_probs(c->d_ologits, c->d_oprobs, c->d_oentropy, n * M, C, c->stream);
+    }
+    const int bc = box_cols_of(m, UDA_POST_GLOBAL), cc = cls_cols_of(m, UDA_POST_GLOBAL);
+    ScoreArgs<float> a{};
+    a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses; a.entropy = c->d_oentropy;
+    a.albox = c->d_oboxes + 4;                                               // box | aleatoric std | MC std, as each exists
+    a.mcbox = c->d_oboxes + ((m.has_uncert && m.loss_attenuation) ? 8 : 4);
+    a.mcclass = c->d_oclasses + 1;
+    a.box_stride = a.al_stride = a.mc_stride = bc; a.cls_stride = a.mcc_stride = cc; a.mcc_w = cc - 1;
+    a.comp = (double*)c->d_score_pack;
+    a.count = (int32_t*)(c->d_score_pack + (size_t)n * nc * sizeof(double));
+    a.class_counts = a.count + n;
+    a.err = a.class_counts + (size_t)n * C;
+    a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
+    HIPC(c, hipMemsetAsync(a.err, 0, sizeof(int32_t), c->stream));
+    launch_score_images(a, c->stream);
+  }
+  HIPC(c, hipGetLastError());
+  c->score_n = n; c->score_nc = nc; c->score_fetched = false;
+  return 0;
+}
+
+extern "C" int uda_image_scores_shape(const uda_ctx_t* c, int32_t* n, int32_t* n_comp) {
+  if (!c || !n || !n_comp) return 1;
+  *n = c->score_n; *n_comp = c->score_nc;
+  return 0;
+}
+
+extern "C" int uda_get_image_scores(uda_ctx_t* c, double* components, int32_t* count, int32_t* class_counts) {
+  if (!c) return 1;
+  if (c->score_n < 1) return fail(c, "get_image_scores: no scores (uda_score_images)");
+  const size_t n = c->score_n, nc = c->score_nc, C = c->model.num_classes;
+  if (!c->score_fetched) {       // the first reader of a scoring waits for it and brings the pack over in one copy
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->h_score.resize(score_pack_bytes(n, nc, C));
+    HIPC(c, hipMemcpy(c->h_score.data(), c->d_score_pack, c->h_score.size(), hipMemcpyDeviceToHost));
+    c->score_fetched = true;
+  }
+  const char* h = c->h_score.data();
+  const int32_t* cnt = (const int32_t*)(h + n * nc * sizeof(double));
+  if (cnt[n + n * C]) return fail(c, "score_images: a kept detection has a class id outside 1..%d", (int)C);
+  if (components) memcpy(components, h, n * nc * sizeof(double));
+  if (count) memcpy(count, cnt, n * sizeof(int32_t));
+  if (class_counts) memcpy(class_counts, cnt + n, n * C * sizeof(int32_t));
+  return 0;
+}
+
+// score_image for callers that hold detections of their own (calibrated columns, a gathered multi-GPU batch): host arrays in,
+// the same kernel, host arrays out; its own allocations
+template <typename T>
+static int score_images_np(const char* who, int32_t device, const uda_score_desc_t* desc, T min_score, const T* boxes, const T* scores,
+                           const T* classes, const T* entropy, const T* albox, const T* mcbox, const T* mcclass, int32_t n, int32_t M,
+                           int32_t C, int32_t mcw, double* components, int32_t* count, int32_t* class_counts) {
+  const char* why = nullptr;
+  const unsigned need = score_desc_sources(desc, &why);
+  if (why) return fail(nullptr, "%s: %s", who, why);
+  if (n < 0 || M < 0 || M > kScoreMaxM || C < 1 || C > kScoreMaxC || ((size_t)n * M && (!boxes || !scores || !classes)))
+    return fail(nullptr, "%s: bad argument", who);
+  const T* srcs[] = {entropy, scores, albox, mcbox, mcclass};
+  static const char* names[] = {"entropy", "scores", "albox", "mcbox", "mcclass"};
+  for (int s = 0; s < 5; ++s)
+    if ((need & (1u << s)) && (size_t)n * M && !srcs[s]) return fail(nullptr, "%s: the descriptor reads %s, which is not given", who, names[s]);
+  if ((need & (1u << UDA_SCORE_MCCLASS)) && mcw < 1) return fail(nullptr, "%s: mcclass_cols must be at least 1", who);
+  if (n == 0) return 0;
+  const size_t nm = (size_t)n * M, nc = desc->n_comp;
+  const size_t widths[] = {4, 1, 1, 1, 4, 4, (size_t)(mcw > 0 ? mcw : 0)};
+  const T* host[] = {boxes, scores, classes, entropy, albox, mcbox, mcclass};
+  T* dev[7] = {};
+  char* d_pack = nullptr;
+  hipError_t e = hipSetDevice(device);
+  for (int k = 0; k < 7 && e == hipSuccess; ++k) {
+    if (!host[k] || !(nm * widths[k])) continue;
+    e = dalloc(&dev[k], nm * widths[k]);
+    if (e == hipSuccess) e = hipMemcpy(dev[k], host[k], nm * widths[k] * sizeof(T), hipMemcpyHostToDevice);
+  }
+  const size_t bytes = score_pack_bytes((size_t)n, nc, (size_t)C);
+  if (e == hipSuccess) e = dalloc(&d_pack, bytes);
+  if (e == hipSuccess) e = hipMemset(d_pack, 0, bytes);
+  std::vector<char> h(bytes);
+  if (e == hipSuccess) {
+    ScoreArgs<T> a{};
+    a.boxes = dev[0]; a.scores = dev[1]; a.classes = dev[2]; a.entropy = dev[3]; a.albox = dev[4]; a.mcbox = dev[5]; a.mcclass = dev[6];
+    a.box_stride = a.al_stride = a.mc_stride = 4; a.cls_stride = 1; a.mcc_stride = a.mcc_w = mcw > 0 ? mcw : 0;
+    a.comp = (double*)d_pack;
+    a.count = (int32_t*)(d_pack + (size_t)n * nc * sizeof(double));
+    a.class_counts = a.count + n;
+    a.err = a.class_counts + (size_t)n * C;
+    a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
+    launch_score_images(a, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d_pack, bytes, hipMemcpyDeviceToHost);
+  for (T* p : dev)
+    if (p) hipFree(p);
+  if (d_pack) hipFree(d_pack);
+  if (e != hipSuccess) return fail(nullptr, "%s: %s", who, hipGetErrorString(e));
+  const int32_t* cnt = (const int32_t*)(h.data() + (size_t)n * nc * sizeof(double));
+  if (cnt[(size_t)n + (size_t)n * C]) return fail(nullptr, "%s: a kept detection has a class id outside 1..%d", who, C);
+  if (components) memcpy(components, h.data(), (size_t)n * nc * sizeof(double));
+  if (count) memcpy(count, cnt, (size_t)n * sizeof(int32_t));
+  if (class_counts) memcpy(class_counts, cnt + n, (size_t)n * C * sizeof(int32_t));
+  return 0;
+}
+
+extern "C" int uda_score_images_np(int32_t device, const uda_score_desc_t* desc, double min_score, const double* boxes,
+                                   const double* scores, const double* classes, const double* entropy, const double* albox,
+                                   const double* mcbox, const double* mcclass, int32_t n, int32_t M, int32_t num_classes,
+                                   int32_t mcclass_cols, double* components, int32_t* count, int32_t* class_counts) {
+  return score_images_np<double>("uda_score_images_np", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass, n,
+                                 M, num_classes, mcclass_cols, components, count, class_counts);
+}
+
+extern "C" int uda_score_images_np_f32(int32_t device, const uda_score_desc_t* desc, float min_score, const float* boxes,
+                                       const float* scores, const float* classes, const float* entropy, const float* albox,
+                                       const float* mcbox, const float* mcclass, int32_t n, int32_t M, int32_t num_classes,
+                                       int32_t mcclass_cols, double* components, int32_t* count, int32_t* class_counts) {
+  return score_images_np<float>("uda_score_images_np_f32", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass,
+                                n, M, num_classes, mcclass_cols, components, count, class_counts);
 }
 
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,

@@ -395,6 +395,27 @@ struct AssignRowsArgs {
 };
 void launch_gather_assigned(const AssignRowsArgs& a, hipStream_t s);
 
+// active-learning image scores (reference active_learning_loop.py:528-765): T = float for the columns resident in a handle,
+// double for host arrays (uda_score_images_np)
+template <typename T>
+struct ScoreArgs {
+  const T* boxes;           // [n, M, box_stride] y1 x1 y2 x2 in the first four columns
+  const T* scores;          // [n, M]
+  const T* classes;         // [n, M, cls_stride] class id 1..C in the first column
+  const T* entropy;         // [n, M] (source ENTROPY)
+  const T *albox, *mcbox;   // first of the 4 std columns of row 0, rows al_stride / mc_stride apart
+  const T* mcclass;         // first of the mcc_w std columns of row 0, rows mcc_stride apart
+  double* comp;             // [n, n_comp]
+  int32_t* count;           // [n] kept rows
+  int32_t* class_counts;    // [n, C] kept rows per class id 1..C
+  int32_t* err;             // set to 1 by a kept row whose class id is not one of 1..C
+  int n, M, C, box_stride, cls_stride, al_stride, mc_stride, mcc_stride, mcc_w;
+  T min_score;              // a row is kept iff score > min_score
+  uda_score_desc_t desc;
+};
+void launch_score_images(const ScoreArgs<float>& a, hipStream_t s);
+void launch_score_images(const ScoreArgs<double>& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

@@ -291,6 +291,14 @@ class SampleShardedDriver:
     def serve_validate(self, images, gt_boxes, gt_classes, method=None, keep="validate"):
         return self.assign_ground_truth(gt_boxes, gt_classes, method, keep)
 
+    def score_images(self, strategy, min_score, opt_params=None):
+        """As for the ground-truth assignment: no single handle holds the whole batch's detections."""
+        raise ValueError("a sample-sharded serve leaves no handle that holds the whole batch's detections: run "
+                         "active_learning.score_detections(columns, strategy, min_score) on the gathered detections")
+
+    def serve_score(self, images, strategy, min_score, opt_params=None):
+        return self.score_images(strategy, min_score, opt_params)
+
     def close(self):
         self.net.close()
         self.post.close()

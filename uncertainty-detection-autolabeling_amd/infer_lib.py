@@ -500,6 +500,49 @@ class ServingDriver:
         det = self._collect(n, capi.POST_GLOBAL)
         return det, self._fetch_assignment(gb, gc, keep)
 
+    # ------------------------------------------------------------------ active learning: per-image uncertainty scores
+    def _resolve_score(self, strategy, opt_params):
+        from . import active_learning as al
+        st = strategy if isinstance(strategy, al.Strategy) else al.resolve_strategy(strategy, self.params, opt_params)
+        if st.calibrated:
+            raise ValueError("strategy %r reads calibrated columns (%s), which are host arrays: score them with "
+                             "active_learning.score_detections" % (st.name, ", ".join(sorted(st.columns.values()))))
+        return st
+
+    def _fetch_scores(self, st):
+        n, nc = C.c_int32(), C.c_int32()
+        self._ck(self._lib.uda_image_scores_shape(self._h, C.byref(n), C.byref(nc)), "uda_image_scores_shape")
+        n = n.value
+        assert nc.value == st.n_comp
+        comp = np.zeros((n, st.n_comp), np.float64)
+        count = np.zeros((n,), np.int32)
+        cls = np.zeros((n, self.num_classes), np.int32)
+        self._ck(self._lib.uda_get_image_scores(self._h, _ptr(comp), _ptr(count), _ptr(cls)), "uda_get_image_scores")
+        return comp, count, cls
+
+    def score_images(self, strategy, min_score, opt_params=None):
+        """The per-image part of the reference's active-learning score (`ActiveLearning.score_image`,
+        active_learning_loop.py:528-733) on the detections resident in the handle: every detection with score > min_score
+        (the rows `Infer.iterate_infer` writes, infer_model.py:836) gives the strategy's one to three uncertainty numbers,
+        each reduced over the image with mean or max.  strategy: the reference's `scoring_strategy` string
+        (`active_learning.resolve_strategy`) or a resolved `Strategy`; min_score is rounded to float32, the type of the
+        scores it is compared with.
+
+        Returns (components [n, n_comp] float64 - 0 where nothing is kept -, count [n] int32 kept detections, class_counts
+        [n, num_classes] int32 kept detections per class id) for the images of the last run: serve, serve_resident, all 4n
+        images after serve_consistency, inside serve_stream(while_resident=).  `active_learning.ImageScores` accumulates the
+        batches of a pool and does the dataset-wide part."""
+        st = self._resolve_score(strategy, opt_params)
+        desc = st.desc()
+        self._ck(self._lib.uda_score_images(self._h, C.byref(desc), C.c_float(min_score)), "uda_score_images")
+        return self._fetch_scores(st)
+
+    def serve_score(self, image_arrays, strategy, min_score, opt_params=None):
+        """serve resident + `score_images`: the batch's scores without downloading the 100-row detection columns."""
+        st = self._resolve_score(strategy, opt_params)
+        self.serve_resident(image_arrays, post_mode=capi.POST_GLOBAL)
+        return self.score_images(st, min_score)
+
     def serve_resident(self, image_arrays, post_mode=None):
         """serve() without the download: the detections stay in the handle (`detections_device`, calibrators,
         `class_probs`) - what the multi-GPU layer runs before its device-resident gather.  Returns the image count."""
@@ -986,6 +1029,14 @@ class EnsembleDriver:
     def serve_validate(self, image_arrays, gt_boxes, gt_classes, method=None, keep="validate"):
         det = self.serve(image_arrays)
         return det, self.assign_ground_truth(gt_boxes, gt_classes, method=method, keep=keep)
+
+    def score_images(self, strategy, min_score, opt_params=None):
+        """The ensemble's detections live in its aggregating handle: the scores are that handle's."""
+        return self.post.score_images(strategy, min_score, opt_params=opt_params)
+
+    def serve_score(self, image_arrays, strategy, min_score, opt_params=None):
+        self.serve(image_arrays)
+        return self.score_images(strategy, min_score, opt_params=opt_params)
 
     def close(self):
         for d in self.members + [self.post]:
