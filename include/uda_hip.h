@@ -20,6 +20,8 @@
  *                            (utils_extra.py:44-64; validate_model.py:314-470, calibrate_model.py:133-190)
  *   uda_score_images      <- ActiveLearning.score_image's per-detection numbers and per-image mean / max
  *                            (active_learning_loop.py:528-733)
+ *   uda_eval_match        <- COCOeval_all.evaluateImg for the detections and ground truth EvaluationMetric.update_state
+ *                            collects (custom_cocoeval.py:265-349; coco_metric.py:219-283)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -396,6 +398,58 @@ int uda_score_images_np_f32(int32_t device, const uda_score_desc_t* desc, float 
                             const float* mcclass, int32_t n, int32_t M, int32_t num_classes, int32_t mcclass_cols,
                             double* components, int32_t* count, int32_t* class_counts);
 
+/* COCO evaluation: the matching half of the metric eval.py and the training-time COCOCallback hand their detections to
+ * (coco_metric.EvaluationMetric, coco_metric.py:59-283, which runs pycocotools' COCOeval and custom_cocoeval.COCOeval_all) -
+ * evaluateImg (custom_cocoeval.py:265-349) for every (image, category, area range, IoU threshold) at maxDets[-1] = 100 - done on
+ * the detections RESIDENT in the handle after a post-process in either mode (per class is the main caller: eval.py:117-123).
+ * accumulate / summarize (custom_cocoeval.py:351-545) are the caller's (coco_metric.py of the package), on the records.
+ *   detections    a row is used iff class > -1 (coco_metric.py:235); its category is int(class); box [x1, y1, x2 - x1, y2 - y1] in
+ *                 float32 (postprocess.transform_detections, postprocess.py:874-887), area = float32 w * h (pycocotools loadRes on
+ *                 the float32 rows; stated from knowledge of pycocotools, which the reference imports but does not contain)
+ *   ground truth  [n, G, 7] float32 rows y1, x1, y2, x2, is_crowd, area, class (coco_metric.py:256-275): rows with class <= -1 are
+ *                 padding; box [x1, y1, x2 - x1, y2 - y1] and area (x2 - x1) * (y2 - y1) in float32, the area column is not read;
+ *                 crowd = int(is_crowd) != 0.  G <= UDA_EVAL_MAX_GT rows per image (the reference's max_instances_per_image is
+ *                 100); a larger G is refused, never truncated.  Classes must be whole numbers in 1..num_classes and all values
+ *                 finite (the Python layer checks).
+ *   IoU           pycocotools bbIou in float64 on the float32 values: iw = min(dx + dw, gx + gw) - max(dx, gx), ih likewise, 0 when
+ *                 either is <= 0, else i = iw * ih and i / (crowd ? dw * dh : dw * dh + gw * gh - i)
+ *   matching      detections of one (image, category) by score descending, stable, the first 100; ground truth non-ignored rows
+ *                 first, stable, ignored = crowd or area outside [lo, hi] of (0, 1e10), (0, 1024), (1024, 9216), (9216, 1e10),
+ *                 both ends inclusive; per threshold t the greedy scan of custom_cocoeval.py:307-330 from min(t, 1 - 1e-10): an
+ *                 equal IoU moves the match to the later row, a crowd may be matched again, the scan stops at the ignored rows
+ *                 once a non-ignored match is in hand; an unmatched detection whose own area is outside the range is ignored
+ *   record        per detection row: rank inside its (image, category), 0-based, -1 when the row is unused or its category is not
+ *                 one of 1..num_classes; bit t of matched[a] / ignored[a] per area range a; rows of rank >= 100 keep their rank
+ *                 and carry zero masks */
+#define UDA_EVAL_MAX_GT 256
+#define UDA_EVAL_MAX_THRS 32
+typedef struct uda_eval_record {
+  float score;
+  int32_t cls;
+  int32_t rank;
+  uint32_t matched[4];
+  uint32_t ignored[4];
+} uda_eval_record_t;   /* 44 bytes */
+/*   uda_set_eval_ground_truth  gt [n, G, 7]; the handle's buffers hold max_images x G rows and grow only when G grows
+ *                              (as uda_set_ground_truth's do).  Refuses n outside 1..max_images and G above UDA_EVAL_MAX_GT.
+ *   uda_eval_match             iou_thrs [T] float64, T in 1..UDA_EVAL_MAX_THRS (pycocotools' linspace(0.5, 0.95, 10), COCOeval_all's
+ *                              linspace(0.05, 0.95, 19), or both in one pass); queues the match kernel on the handle's stream;
+ *                              forces the deferred fix-ups every reader of detections forces.  Refuses: no ground truth set, no
+ *                              post-process yet, n different from the run's image count, a pipelined run still in flight, T out
+ *                              of range, max_output_size above 4096.
+ *   uda_get_eval_records       records [n, max_output_size] x 44 bytes, npig [n, num_classes, 4] int32 non-ignored ground-truth
+ *                              rows per class id and area range, used [n] int32 used detection rows (an image with none is not
+ *                              evaluated, coco_metric.py:237-238); one copy; any pointer may be NULL. */
+int uda_set_eval_ground_truth(uda_ctx_t* ctx, const float* gt, int32_t n, int32_t G);
+int uda_eval_match(uda_ctx_t* ctx, const double* iou_thrs, int32_t T);
+int uda_get_eval_records(uda_ctx_t* ctx, void* records, int32_t* npig, int32_t* used);
+/* The same match without a handle, in the manner of uda_assign_gt_np: host arrays det_rows [n, M, 7] float32 (image id, x, y, w, h,
+ * score, class - what transform_detections returns and update_state takes, coco_metric.py:230-231; the image id is not read) and
+ * gt [n, G, 7]; the same kernel in its legacy-row layout, the same outputs.  For the nms_np route and for callers that hold rows
+ * of their own.  M <= 4096, G <= UDA_EVAL_MAX_GT, T in 1..UDA_EVAL_MAX_THRS, num_classes in 1..8192. */
+int uda_eval_match_np(int32_t device, const float* det_rows, const float* gt, int32_t n, int32_t M, int32_t G, int32_t num_classes,
+                      const double* iou_thrs, int32_t T, void* records, int32_t* npig, int32_t* used);
+
 /* serve = set_images_u8 + run + get_detections */
 int uda_serve(uda_ctx_t* ctx, const uint8_t* images, int32_t n, int32_t h, int32_t w,
               float* boxes, float* scores, float* classes, int32_t* valid, float* logits);
@@ -496,7 +550,7 @@ int uda_per_class_nms_np(int32_t device, const float* boxes, const float* scores
 
 /* Per-op-kind device timing with HIP events recorded on the handle's stream.
  * kind_mask: bit (1 << uda_op_kind) selects op kinds; bit 16 post-process aggregate, bit 17 NMS, bit 19 the score kernel of
- * uda_score_images (with its softmax / entropy kernel when ENTROPY is read). */
+ * uda_score_images (with its softmax / entropy kernel when ENTROPY is read), bit 20 the match kernel of uda_eval_match. */
 int uda_profile_enable(uda_ctx_t* ctx, uint32_t kind_mask);
 int uda_profile_read(uda_ctx_t* ctx, int32_t kind, double* total_ms, int64_t* launches, int32_t reset);
 

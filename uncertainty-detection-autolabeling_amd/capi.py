@@ -30,7 +30,8 @@ ASSIGN_KEEP_VALIDATE, ASSIGN_KEEP_CALIBRATE = 0, 1
 SCORE_ENTROPY, SCORE_DET_SCORE, SCORE_ALBOX, SCORE_MCBOX, SCORE_MCCLASS = 0, 1, 2, 3, 4
 SCORE_SCALAR, SCORE_MEAN, SCORE_REL_MEAN = 0, 1, 2
 SCORE_MAX_COMP = 3
-PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS, PROF_SCORE = 16, 17, 18, 19
+PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS, PROF_SCORE, PROF_EVAL = 16, 17, 18, 19, 20
+EVAL_MAX_GT, EVAL_MAX_THRS = 256, 32
 
 
 class BufDesc(C.Structure):
@@ -132,6 +133,10 @@ _SIGNATURES = {
                                       C.c_int32, C.c_int32, _P, _P, _P]),
     "uda_score_images_np_f32": (C.c_int, [C.c_int32, C.POINTER(ScoreDesc), C.c_float, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_int32, _P, _P, _P]),
+    "uda_set_eval_ground_truth": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
+    "uda_eval_match": (C.c_int, [_P, _P, C.c_int32]),
+    "uda_get_eval_records": (C.c_int, [_P, _P, _P, _P]),
+    "uda_eval_match_np": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "uda_calibrate_box": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "uda_calibrate_class": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, _P]),
     "uda_serve": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),

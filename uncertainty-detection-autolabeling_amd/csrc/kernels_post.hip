@@ -462,6 +462,198 @@ static void launch_score_images_t(const ScoreArgs<T>& a, hipStream_t s) {
 void launch_score_images(const ScoreArgs<float>& a, hipStream_t s) { launch_score_images_t(a, s); }
 void launch_score_images(const ScoreArgs<double>& a, hipStream_t s) { launch_score_images_t(a, s); }
 
+// ------------------------------------------------------------------------------------ COCO matching
+// COCOeval_all.evaluateImg (custom_cocoeval.py:265-349) at maxDets[-1] = 100 for the containers EvaluationMetric.update_state
+// builds (coco_metric.py:219-283).  One block of two waves per (image, class id c in 1..C):
+//   wave 0 compacts the rows of class c in row order (ballots) and counts the image's used rows (class > -1, :235); a row's
+//          category is int(class) as loadNumpyAnnotations takes it, so c <= class < c + 1
+//   wave 1 compacts the ground-truth rows of class c: box [x1, y1, x2 - x1, y2 - y1] and area (x2 - x1) * (y2 - y1) in float32
+//          (:258-270; the area column is not read), crowd = int(is_crowd) != 0, ignore per area range = crowd or area outside
+//          [lo, hi], both ends inclusive
+//   rank   of a row = #{j : s_j > s_i or (s_j == s_i and j < i)} among the class's rows: the stable argsort of -score (:289).
+//          Ranks below 100 are staged with box and area = float32 w * h (what pycocotools' loadRes computes on the float32 rows;
+//          stated from knowledge of pycocotools, which the reference imports but does not contain)
+//   order  per area range: non-ignored rows first, stable (:287)
+//   scan   thread p = area * T + t walks the ranked detections and, per detection, the ground truth in that order (:307-330);
+//          IoUs are recomputed from the staged boxes in float64 (pycocotools bbIou; no contraction in this file); its
+//          "ground truth taken" bits live in a column of LDS words of its own; matched / ignored bits meet in LDS words per
+//          (area, detection) through integer OR, which has no order to depend on
+// Every detection row gets exactly one record: from its class's block, or from the block of class 1 when it is unused or its
+// class lies outside 1..C (rank -1).  Rows of rank >= 100 keep their rank and carry zero masks.
+__device__ __forceinline__ double bb_iou(const float* d, const float* g, bool crowd) {
+  const double dx = d[0], dy = d[1], dw = d[2], dh = d[3], gx = g[0], gy = g[1], gw = g[2], gh = g[3];
+  const double w = fmin(dw + dx, gw + gx) - fmax(dx, gx);
+  if (w <= 0.0) return 0.0;
+  const double h = fmin(dh + dy, gh + gy) - fmax(dy, gy);
+  if (h <= 0.0) return 0.0;
+  const double i = w * h, da = dw * dh, ga = gw * gh;
+  const double u = crowd ? da : da + ga - i;
+  return i / u;
+}
+
+__device__ __forceinline__ bool coco_area_out(float area, int ar) {
+  const double lo = ar < 2 ? 0.0 : (ar == 2 ? 1024.0 : 9216.0), hi = ar == 1 ? 1024.0 : (ar == 2 ? 9216.0 : 1e10);
+  return (double)area < lo || (double)area > hi;
+}
+
+__device__ __forceinline__ int coco_class_field(float k) {
+  return !(k > -1.0f) ? -1 : (k < 2147483520.0f ? (int)k : 2147483647);
+}
+
+__device__ __forceinline__ void coco_write(uda_eval_record_t* o, float score, int cls, int rank, const unsigned* mm, const unsigned* im) {
+  o->score = score; o->cls = cls; o->rank = rank;
+  for (int k = 0; k < 4; ++k) { o->matched[k] = mm ? mm[k] : 0u; o->ignored[k] = im ? im[k] : 0u; }
+}
+
+template <bool LEGACY>
+__global__ __launch_bounds__(128) void coco_match_kernel(CocoMatchArgs a) {
+  __shared__ float sc[COCO_MAX_M];                 // score of the class's r-th row
+  __shared__ unsigned short row[COCO_MAX_M];       // its row in the image
+  __shared__ float dbox[COCO_MAX_DET][4], darea[COCO_MAX_DET], dscore[COCO_MAX_DET];
+  __shared__ unsigned short drow[COCO_MAX_DET];
+  __shared__ float gbox[COCO_MAX_G][4];
+  __shared__ unsigned char gflag[COCO_MAX_G];      // bit ar: ignored in area range ar; bit 4: crowd
+  __shared__ unsigned short order[4][COCO_MAX_G];
+  __shared__ unsigned taken[COCO_MAX_G / 32][128];
+  __shared__ unsigned mm[COCO_MAX_DET][4], im[COCO_MAX_DET][4];
+  __shared__ int s_mc, s_gc, s_used;
+  const int i = blockIdx.x / a.C, c = blockIdx.x % a.C + 1;
+  const int M = a.M, G = a.G, T = a.T, tid = threadIdx.x;
+  const float clo = (float)c, chi = (float)(c + 1);
+  const size_t r0 = (size_t)i * M;
+  auto cls_of = [&](int r) { return LEGACY ? a.rows[(r0 + r) * 7 + 6] : a.classes[(r0 + r) * a.cls_stride]; };
+  auto score_of = [&](int r) { return LEGACY ? a.rows[(r0 + r) * 7 + 5] : a.scores[r0 + r]; };
+
+  if (tid < 64) {                                  // (wave-uniform branch: the ballots below see whole waves)
+    int run = 0, used = 0;
+    for (int base = 0; base < M; base += 64) {
+      const int r = base + tid;
+      const float k = r < M ? cls_of(r) : -1.0f;
+      const bool u = r < M && k > -1.0f;
+      const bool mine = u && k >= clo && k < chi;
+      const unsigned long long bm = __ballot(mine);
+      if (mine) {
+        const int p = run + __popcll(bm & ((1ull << tid) - 1ull));
+        row[p] = (unsigned short)r;
+        sc[p] = score_of(r);
+      }
+      run += __popcll(bm);
+      used += __popcll(__ballot(u));
+    }
+    if (tid == 0) { s_mc = run; s_used = used; }
+  } else {
+    const int lane = tid - 64;
+    int run = 0;
+    for (int base = 0; base < G; base += 64) {
+      const int g = base + lane;
+      const float* gp = a.gt + ((size_t)i * G + (g < G ? g : 0)) * 7;
+      const float k = g < G ? gp[6] : -1.0f;
+      const bool mine = g < G && k > -1.0f && k >= clo && k < chi;
+      const unsigned long long bm = __ballot(mine);
+      if (mine) {
+        const int p = run + __popcll(bm & ((1ull << lane) - 1ull));
+        const float w = gp[3] - gp[1], h = gp[2] - gp[0];
+        gbox[p][0] = gp[1]; gbox[p][1] = gp[0]; gbox[p][2] = w; gbox[p][3] = h;
+        const float area = w * h;
+        const bool crowd = gp[4] >= 1.0f || gp[4] <= -1.0f;      // int(is_crowd) != 0
+        unsigned f = crowd ? 0x1fu : 0u;
+        for (int ar = 0; ar < 4; ++ar)
+          if (coco_area_out(area, ar)) f |= 1u << ar;
+        gflag[p] = (unsigned char)f;
+      }
+      run += __popcll(bm);
+    }
+    if (lane == 0) s_gc = run;
+  }
+  for (int e = tid; e < COCO_MAX_DET * 4; e += 128) { (&mm[0][0])[e] = 0u; (&im[0][0])[e] = 0u; }
+  for (int w = 0; w < COCO_MAX_G / 32; ++w) taken[w][tid] = 0u;
+  __syncthreads();
+  const int mc = s_mc, gc = s_gc, D = mc < COCO_MAX_DET ? mc : COCO_MAX_DET;
+
+  if (tid < 4) {                                   // non-ignored rows first, stable; their count is npig
+    int p = 0;
+    for (int g = 0; g < gc; ++g)
+      if (!((gflag[g] >> tid) & 1)) order[tid][p++] = (unsigned short)g;
+    a.npig[((size_t)i * a.C + (c - 1)) * 4 + tid] = p;
+    for (int g = 0; g < gc; ++g)
+      if ((gflag[g] >> tid) & 1) order[tid][p++] = (unsigned short)g;
+  }
+  for (int r = tid; r < mc; r += 128) {
+    const float s = sc[r];
+    int rank = 0;
+    for (int j = 0; j < mc; ++j) {
+      const float t = sc[j];
+      rank += (t > s || (t == s && j < r)) ? 1 : 0;
+    }
+    const int R = row[r];
+    if (rank < COCO_MAX_DET) {
+      float x, y, w, h;
+      if (LEGACY) {
+        const float* p = a.rows + (r0 + R) * 7;
+        x = p[1]; y = p[2]; w = p[3]; h = p[4];
+      } else {
+        const float* p = a.boxes + (r0 + R) * a.box_stride;
+        x = p[1]; y = p[0]; w = p[3] - p[1]; h = p[2] - p[0];     // transform_detections, float32
+      }
+      dbox[rank][0] = x; dbox[rank][1] = y; dbox[rank][2] = w; dbox[rank][3] = h;
+      darea[rank] = w * h;
+      dscore[rank] = s;
+      drow[rank] = (unsigned short)R;
+    } else {
+      coco_write(a.rec + r0 + R, s, c, rank, nullptr, nullptr);
+    }
+  }
+  __syncthreads();
+
+  if (tid < 4 * T) {
+    const int ar = tid / T, t = tid - ar * T;
+    const double start = fmin(a.thr[t], 1.0 - 1e-10);
+    for (int d = 0; d < D; ++d) {
+      double best = start;
+      int m = -1;
+      bool m_ig = false;
+      for (int gi = 0; gi < gc; ++gi) {
+        const int g = order[ar][gi];
+        const unsigned f = gflag[g];
+        const bool ig = (f >> ar) & 1, crowd = (f >> 4) & 1;
+        if (((taken[g >> 5][tid] >> (g & 31)) & 1u) && !crowd) continue;
+        if (m >= 0 && !m_ig && ig) break;
+        const double v = bb_iou(dbox[d], gbox[g], crowd);
+        if (v < best) continue;
+        best = v; m = g; m_ig = ig;
+      }
+      bool ign;
+      if (m < 0) {
+        ign = coco_area_out(darea[d], ar);
+      } else {
+        taken[m >> 5][tid] |= 1u << (m & 31);
+        atomicOr(&mm[d][ar], 1u << t);
+        ign = m_ig;
+      }
+      if (ign) atomicOr(&im[d][ar], 1u << t);
+    }
+  }
+  __syncthreads();
+  for (int d = tid; d < D; d += 128) coco_write(a.rec + r0 + drow[d], dscore[d], c, d, mm[d], im[d]);
+
+  if (c == 1) {                                    // the rows no class's block owns
+    for (int r = tid; r < M; r += 128) {
+      const float k = cls_of(r);
+      if (!(k > -1.0f && k >= 1.0f && k < (float)(a.C + 1))) coco_write(a.rec + r0 + r, score_of(r), coco_class_field(k), -1, nullptr, nullptr);
+    }
+    if (tid == 0) a.used[i] = s_used;
+  }
+}
+
+void launch_coco_match(const CocoMatchArgs& a, hipStream_t s) {
+  if (a.n <= 0 || a.C <= 0) return;
+  const dim3 grid((unsigned)a.n * (unsigned)a.C);
+  if (a.legacy)
+    hipLaunchKernelGGL(coco_match_kernel<true>, grid, dim3(128), 0, s, a);
+  else
+    hipLaunchKernelGGL(coco_match_kernel<false>, grid, dim3(128), 0, s, a);
+}
+
 // ------------------------------------------------------------------------------------ aggregate + decode
 __device__ __forceinline__ float exp32(float x) { return (float)exp((double)x); }
 

@@ -205,6 +205,16 @@ struct uda_ctx {
   std::vector<char> h_score;         // host copy of the pack (filled by the first reader of a scoring)
   int score_n = 0, score_nc = 0;     // images / components of the last scoring (0: none)
   bool score_fetched = false;
+  // COCO matching (uda_set_eval_ground_truth / uda_eval_match): ground truth [max_images, egt_cap, 7], grown when a call brings
+  // more rows per image; results packed for max_images so that ONE copy brings them to the host:
+  // records [n, M] x 44 bytes | npig [n, num_classes, 4] int32 | used [n] int32
+  float *d_egt = nullptr, *h_egt = nullptr;   // h_egt: pinned staging
+  hipEvent_t egt_ev = nullptr;       // the upload out of h_egt has been consumed
+  char* d_eval_pack = nullptr;
+  std::vector<char> h_eval;          // host copy of the pack (filled by the first reader of a match)
+  int egt_cap = 0, egt_n = 0, egt_G = 0;   // rows per image the buffer holds; images / rows per image of the GT that is set (0: none)
+  int eval_n = 0;                    // images of the last match (0: none)
+  bool eval_fetched = false;
   int last_post_mode = 0;
   int last_n = 0;
   int last_chunk_i0 = 0, last_chunk_n = 0;
@@ -344,9 +354,11 @@ extern "C" void uda_destroy(uda_ctx_t* c) {
                   c->d_cclasses, c->d_ucls, c->d_ual, c->d_uep, c->d_clsmean, c->d_cand_flat, c->d_merge_keys,
                   c->d_oboxes, c->d_oscores, c->d_oclasses, c->d_ologits, c->d_ovalid, c->d_oprobs, c->d_oentropy,
                   c->d_opacked, c->d_cons_iou, c->d_cons_agree, c->d_gt_boxes, c->d_gt_classes, c->d_asg_pack,
-                  c->d_asg_rows, c->d_score_pack};
+                  c->d_asg_rows, c->d_score_pack, c->d_egt, c->d_eval_pack};
   if (c->h_gt) hipHostFree(c->h_gt);
   if (c->gt_ev) hipEventDestroy(c->gt_ev);
+  if (c->h_egt) hipHostFree(c->h_egt);
+  if (c->egt_ev) hipEventDestroy(c->egt_ev);
   for (void* p : ptrs)
     if (p) hipFree(p);
   free_prefix_ws(c->pfx);
@@ -2940,6 +2952,144 @@ extern "C" int uda_score_images_np_f32(int32_t device, const uda_score_desc_t* d
                                        int32_t mcclass_cols, double* components, int32_t* count, int32_t* class_counts) {
   return score_images_np<float>("uda_score_images_np_f32", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass,
                                 n, M, num_classes, mcclass_cols, components, count, class_counts);
+}
+
+// ---- COCO matching (reference custom_cocoeval.py:265-349 on the containers of coco_metric.py:219-283)
+static const int kEvalMaxC = 8192;
+static size_t eval_pack_bytes(size_t n, size_t M, size_t C) { return n * M * sizeof(uda_eval_record_t) + (n * C * 4 + n) * sizeof(int32_t); }
+static_assert(sizeof(uda_eval_record_t) == 44, "the record is 11 words");
+
+static const char* eval_thrs_bad(const double* thrs, int32_t T) {
+  if (T < 1 || T > COCO_MAX_T) return "T outside 1..32 thresholds";
+  if (!thrs) return "NULL thresholds";
+  return nullptr;
+}
+
+extern "C" int uda_set_eval_ground_truth(uda_ctx_t* c, const float* gt, int32_t n, int32_t G) {
+  if (!c || !gt) return c ? fail(c, "set_eval_ground_truth: NULL argument") : 1;
+  const uda_model_t& m = c->model;
+  if (n < 1 || n > m.max_images) return fail(c, "set_eval_ground_truth: %d images, the handle holds 1..%d", n, m.max_images);
+  if (G < 0 || G > COCO_MAX_G) return fail(c, "set_eval_ground_truth: %d ground-truth rows per image, at most %d", G, (int)COCO_MAX_G);
+  HIPC(c, hipSetDevice(c->device));
+  if (!c->egt_ev) HIPC(c, hipEventCreateWithFlags(&c->egt_ev, hipEventDisableTiming));
+  else HIPC(c, hipEventSynchronize(c->egt_ev));         // the previous upload has left the staging buffer
+  if (G > c->egt_cap || !c->d_egt) {
+    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffer)
+    if (c->d_egt) hipFree(c->d_egt);
+    if (c->h_egt) hipHostFree(c->h_egt);
+    c->d_egt = c->h_egt = nullptr; c->egt_cap = 0; c->egt_n = 0;
+    const size_t cap = (size_t)std::max(G, 1), rows = (size_t)m.max_images * cap;
+    HIPC(c, dalloc(&c->d_egt, rows * 7));
+    HIPC(c, hipHostMalloc((void**)&c->h_egt, rows * 7 * sizeof(float)));
+    c->egt_cap = (int)cap;
+  }
+  const size_t floats = (size_t)n * G * 7;
+  if (floats) {
+    memcpy(c->h_egt, gt, floats * sizeof(float));
+    HIPC(c, hipMemcpyAsync(c->d_egt, c->h_egt, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPC(c, hipEventRecord(c->egt_ev, c->stream));
+  c->egt_n = n; c->egt_G = G;
+  return 0;
+}
+
+extern "C" int uda_eval_match(uda_ctx_t* c, const double* iou_thrs, int32_t T) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  if (const char* why = eval_thrs_bad(iou_thrs, T)) return fail(c, "eval_match: %s", why);
+  if (c->egt_n < 1) return fail(c, "eval_match: no ground truth is set (uda_set_eval_ground_truth)");
+  if (c->as[0].open || c->as[1].open)
+    return fail(c, "eval_match: a pipelined run (uda_run_async) is in flight - uda_collect it first");
+  if (c->last_n < 1) return fail(c, "eval_match: no post-process has run yet");
+  if (c->egt_n != c->last_n)
+    return fail(c, "eval_match: ground truth of %d images, the last post-process holds %d", c->egt_n, c->last_n);
+  if (m.max_output_size > COCO_MAX_M) return fail(c, "eval_match: max_output_size %d above %d", m.max_output_size, (int)COCO_MAX_M);
+  if (m.num_classes < 1 || m.num_classes > kEvalMaxC) return fail(c, "eval_match: num_classes %d outside 1..%d", m.num_classes, kEvalMaxC);
+  HIPC(c, hipSetDevice(c->device));
+  if (int rc = finish_post(c)) return rc;      // range replay / prefix redo / NMS fallback: the match reads final detections
+  const int n = c->last_n, M = m.max_output_size, C = m.num_classes;
+  if (!c->d_eval_pack) HIPC(c, dalloc(&c->d_eval_pack, eval_pack_bytes((size_t)m.max_images, (size_t)M, (size_t)C)));
+  {
+    ProfScope ps(c, 20);
+    CocoMatchArgs a{};
+    a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses;
+    a.box_stride = box_cols_of(m, c->last_post_mode); a.cls_stride = cls_cols_of(m, c->last_post_mode);
+    a.gt = c->d_egt;
+    a.rec = (uda_eval_record_t*)c->d_eval_pack;
+    a.npig = (int32_t*)(c->d_eval_pack + (size_t)n * M * sizeof(uda_eval_record_t));
+    a.used = a.npig + (size_t)n * C * 4;
+    a.n = n; a.M = M; a.G = c->egt_G; a.C = C; a.T = T; a.legacy = 0;
+    for (int t = 0; t < T; ++t) a.thr[t] = iou_thrs[t];
+    launch_coco_match(a, c->stream);
+  }
+  HIPC(c, hipGetLastError());
+  c->eval_n = n; c->eval_fetched = false;
+  return 0;
+}
+
+extern "C" int uda_get_eval_records(uda_ctx_t* c, void* records, int32_t* npig, int32_t* used) {
+  if (!c) return 1;
+  if (c->eval_n < 1) return fail(c, "get_eval_records: no match (uda_eval_match)");
+  const size_t n = c->eval_n, M = c->model.max_output_size, C = c->model.num_classes;
+  if (!c->eval_fetched) {        // the first reader of a match waits for it and brings the pack over in one copy
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->h_eval.resize(eval_pack_bytes(n, M, C));
+    HIPC(c, hipMemcpy(c->h_eval.data(), c->d_eval_pack, c->h_eval.size(), hipMemcpyDeviceToHost));
+    c->eval_fetched = true;
+  }
+  const char* h = c->h_eval.data();
+  const size_t rec_bytes = n * M * sizeof(uda_eval_record_t);
+  if (records) memcpy(records, h, rec_bytes);
+  if (npig) memcpy(npig, h + rec_bytes, n * C * 4 * sizeof(int32_t));
+  if (used) memcpy(used, h + rec_bytes + n * C * 4 * sizeof(int32_t), n * sizeof(int32_t));
+  return 0;
+}
+
+// evaluateImg for callers that hold legacy rows of their own (the nms_np route, gathered detections): host arrays in, the same
+// kernel in its legacy-row layout, host arrays out; its own allocations
+extern "C" int uda_eval_match_np(int32_t device, const float* det_rows, const float* gt, int32_t n, int32_t M, int32_t G,
+                                 int32_t num_classes, const double* iou_thrs, int32_t T, void* records, int32_t* npig, int32_t* used) {
+  if (const char* why = eval_thrs_bad(iou_thrs, T)) return fail(nullptr, "uda_eval_match_np: %s", why);
+  if (G > COCO_MAX_G) return fail(nullptr, "uda_eval_match_np: %d ground-truth rows per image, at most %d", G, (int)COCO_MAX_G);
+  if (M > COCO_MAX_M) return fail(nullptr, "uda_eval_match_np: %d detection rows per image, at most %d", M, (int)COCO_MAX_M);
+  if (n < 0 || M < 0 || G < 0 || num_classes < 1 || num_classes > kEvalMaxC || ((size_t)n * M && !det_rows) || ((size_t)n * G && !gt))
+    return fail(nullptr, "uda_eval_match_np: bad argument");
+  if (n == 0) return 0;
+  const size_t nm = (size_t)n * M, ng = (size_t)n * G, C = (size_t)num_classes;
+  const size_t bytes = eval_pack_bytes((size_t)n, (size_t)M, C);
+  float *d_det = nullptr, *d_gt = nullptr;
+  char* d_pack = nullptr;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = dalloc(&d_det, nm * 7);
+  if (e == hipSuccess) e = dalloc(&d_gt, ng * 7);
+  if (e == hipSuccess) e = dalloc(&d_pack, bytes);
+  if (e == hipSuccess && nm) e = hipMemcpy(d_det, det_rows, nm * 7 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && ng) e = hipMemcpy(d_gt, gt, ng * 7 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_pack, 0, bytes);
+  std::vector<char> h(bytes);
+  if (e == hipSuccess) {
+    CocoMatchArgs a{};
+    a.rows = d_det; a.gt = d_gt;
+    a.rec = (uda_eval_record_t*)d_pack;
+    a.npig = (int32_t*)(d_pack + nm * sizeof(uda_eval_record_t));
+    a.used = a.npig + (size_t)n * C * 4;
+    a.n = n; a.M = M; a.G = G; a.C = num_classes; a.T = T; a.legacy = 1;
+    for (int t = 0; t < T; ++t) a.thr[t] = iou_thrs[t];
+    launch_coco_match(a, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d_pack, bytes, hipMemcpyDeviceToHost);
+  void* ptrs[] = {d_det, d_gt, d_pack};
+  for (void* p : ptrs)
+    if (p) hipFree(p);
+  if (e != hipSuccess) return fail(nullptr, "uda_eval_match_np: %s", hipGetErrorString(e));
+  const size_t rec_bytes = nm * sizeof(uda_eval_record_t);
+  if (records) memcpy(records, h.data(), rec_bytes);
+  if (npig) memcpy(npig, h.data() + rec_bytes, (size_t)n * C * 4 * sizeof(int32_t));
+  if (used) memcpy(used, h.data() + rec_bytes + (size_t)n * C * 4 * sizeof(int32_t), (size_t)n * sizeof(int32_t));
+  return 0;
 }
 
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,

@@ -416,6 +416,22 @@ struct ScoreArgs {
 void launch_score_images(const ScoreArgs<float>& a, hipStream_t s);
 void launch_score_images(const ScoreArgs<double>& a, hipStream_t s);
 
+// COCO matching (reference custom_cocoeval.py:265-349 on the containers of coco_metric.py:219-283): one record per detection row
+enum { COCO_MAX_DET = 100, COCO_MAX_M = 4096, COCO_MAX_G = UDA_EVAL_MAX_GT, COCO_MAX_T = UDA_EVAL_MAX_THRS };
+struct CocoMatchArgs {
+  const float* rows;        // legacy layout: [n, M, 7] image id, x, y, w, h, score, class
+  const float* boxes;       // resident layout: [n, M, box_stride] y1 x1 y2 x2 in the first four columns
+  const float* scores;      //                  [n, M]
+  const float* classes;     //                  [n, M, cls_stride] class id in the first column
+  const float* gt;          // [n, G, 7] y1, x1, y2, x2, is_crowd, area (not read), class; class <= -1: padding row
+  uda_eval_record_t* rec;   // [n, M]
+  int32_t* npig;            // [n, C, 4] non-ignored ground-truth rows per class id 1..C and area range
+  int32_t* used;            // [n] rows with class > -1
+  int n, M, G, C, T, box_stride, cls_stride, legacy;
+  double thr[COCO_MAX_T];
+};
+void launch_coco_match(const CocoMatchArgs& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

@@ -299,6 +299,14 @@ class SampleShardedDriver:
     def serve_score(self, images, strategy, min_score, opt_params=None):
         return self.score_images(strategy, min_score, opt_params)
 
+    def eval_match(self, groundtruth_data, iou_thrs=None):
+        """As for the ground-truth assignment: no single handle holds the whole batch's detections."""
+        raise ValueError("a sample-sharded serve leaves no handle that holds the whole batch's detections: run "
+                         "coco_metric.match_np(transform_detections(rows), groundtruth_data, num_classes) on the gathered rows")
+
+    def serve_eval(self, images, groundtruth_data, evaluator, image_ids=None, post_mode=None):
+        return self.eval_match(groundtruth_data, evaluator.iou_thrs)
+
     def close(self):
         self.net.close()
         self.post.close()

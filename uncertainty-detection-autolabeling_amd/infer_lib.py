@@ -543,6 +543,48 @@ class ServingDriver:
         self.serve_resident(image_arrays, post_mode=capi.POST_GLOBAL)
         return self.score_images(st, min_score)
 
+    # ------------------------------------------------------------------ COCO evaluation: matching on the resident detections
+    def eval_match(self, groundtruth_data, iou_thrs=None):
+        """`COCOeval_all.evaluateImg` (custom_cocoeval.py:265-349) for the detections resident in the handle after a
+        post-process in either mode, against groundtruth_data [n, G, 7] (rows y1, x1, y2, x2, is_crowd, area, class; padding
+        rows class -1; coco_metric.py:228-229): the detection boxes become [x1, y1, x2 - x1, y2 - y1] in float32 as
+        `postprocess.transform_detections` makes them.  iou_thrs: up to 32 thresholds, default pycocotools' ten.
+
+        Returns (records [n, M] `coco_metric.RECORD_DTYPE`, npig [n, num_classes, 4] int32, used [n] int32) for the images of
+        the last run (serve, serve_resident, inside serve_stream(while_resident=)); `coco_metric.CocoAccumulator` does the
+        dataset-wide part."""
+        from . import coco_metric as cm
+        gt = cm.check_groundtruth(groundtruth_data, self.num_classes)
+        thr = cm.check_iou_thrs(iou_thrs)
+        n = gt.shape[0]
+        self._ck(self._lib.uda_set_eval_ground_truth(self._h, _ptr(gt), n, gt.shape[1]), "uda_set_eval_ground_truth")
+        self._ck(self._lib.uda_eval_match(self._h, _ptr(thr), thr.size), "uda_eval_match")
+        rec = np.zeros((n, self.M), cm.RECORD_DTYPE)
+        npig = np.zeros((n, self.num_classes, 4), np.int32)
+        used = np.zeros((n,), np.int32)
+        self._ck(self._lib.uda_get_eval_records(self._h, _ptr(rec), _ptr(npig), _ptr(used)), "uda_get_eval_records")
+        return rec, npig, used
+
+    def legacy_rows(self, detections, image_ids=None):
+        """A detection tuple -> the legacy rows [n, M, 7] image_id, x1, y1, x2, y2, score, class of
+        `postprocess.generate_detections` (postprocess.py:743-785); image_ids None: -1, the evaluator's running counter."""
+        from . import postprocess as pp
+        boxes, scores, classes = detections[0][..., :4], detections[1], detections[2]
+        if classes.ndim == 3:
+            classes = classes[..., 0]
+        ids = np.full((boxes.shape[0],), -1.0, np.float32) if image_ids is None else image_ids
+        return pp.generate_detections_from_nms_output(boxes, classes, scores, ids)
+
+    def serve_eval(self, image_arrays, groundtruth_data, evaluator, image_ids=None, post_mode="per_class"):
+        """The body of eval.py's loop (eval.py:117-127) as one call: serve resident, match on the device, hand the records to
+        `evaluator` (a `coco_metric.EvaluationMetric`, matched with its `iou_thrs`), and return the batch's legacy rows
+        [n, M, 7] (image_id, x1, y1, x2, y2, score, class) as `postprocess.generate_detections` does."""
+        mode = self._mode(post_mode)
+        n = self.serve_resident(image_arrays, post_mode=mode)
+        rec, npig, used = self.eval_match(groundtruth_data, evaluator.iou_thrs)
+        evaluator.add_records(image_ids, rec, npig, used, groundtruth_data)
+        return self.legacy_rows(self._collect(n, mode), image_ids)
+
     def serve_resident(self, image_arrays, post_mode=None):
         """serve() without the download: the detections stay in the handle (`detections_device`, calibrators,
         `class_probs`) - what the multi-GPU layer runs before its device-resident gather.  Returns the image count."""
@@ -1037,6 +1079,16 @@ class EnsembleDriver:
     def serve_score(self, image_arrays, strategy, min_score, opt_params=None):
         self.serve(image_arrays)
         return self.score_images(strategy, min_score, opt_params=opt_params)
+
+    def eval_match(self, groundtruth_data, iou_thrs=None):
+        """The ensemble's detections live in its aggregating handle: the match is that handle's."""
+        return self.post.eval_match(groundtruth_data, iou_thrs=iou_thrs)
+
+    def serve_eval(self, image_arrays, groundtruth_data, evaluator, image_ids=None, post_mode=None):
+        det = self.serve(image_arrays, post_mode=post_mode)
+        rec, npig, used = self.eval_match(groundtruth_data, evaluator.iou_thrs)
+        evaluator.add_records(image_ids, rec, npig, used, groundtruth_data)
+        return self.post.legacy_rows(det, image_ids)
 
     def close(self):
         for d in self.members + [self.post]:
