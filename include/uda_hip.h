@@ -22,6 +22,8 @@
  *                            (active_learning_loop.py:528-733)
  *   uda_eval_match        <- COCOeval_all.evaluateImg for the detections and ground truth EvaluationMetric.update_state
  *                            collects (custom_cocoeval.py:265-349; coco_metric.py:219-283)
+ *   uda_thr_objective_np  <- roc_metrics for the candidates of UncertOptimal._extract_optimal_params
+ *                            (uncertainty_analysis.py:44-152)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -449,6 +451,38 @@ int uda_get_eval_records(uda_ctx_t* ctx, void* records, int32_t* npig, int32_t* 
  * of their own.  M <= 4096, G <= UDA_EVAL_MAX_GT, T in 1..UDA_EVAL_MAX_THRS, num_classes in 1..8192. */
 int uda_eval_match_np(int32_t device, const float* det_rows, const float* gt, int32_t n, int32_t M, int32_t G, int32_t num_classes,
                       const double* iou_thrs, int32_t T, void* records, int32_t* npig, int32_t* used);
+
+/* Thresholding: the objective of the failure-recognition search (UncertOptimal._extract_optimal_params / roc_metrics,
+ * uncertainty_analysis.py:44-152) for P candidate weight vectors and K IoU thresholds in one call, without a handle.  Host arrays:
+ * uncerts [U, N] float64, ious [N] float64, tp_class [N] uint8 (class == gt class), group [N] int32 in 0..G-1 or NULL with G = 0,
+ * iou_thrs [K], params [P, U * max(G, 1)]; outputs thr / rate / auc [P, K] float64 (any may be NULL).
+ *   score      u[i] = params[p, 0] * uncerts[0, i] + params[p, 1] * uncerts[1, i] + ...; with groups params[p, group[i] * U + j];
+ *              float64, every product rounded, added left to right, never fused; -0.0 counts as 0.0
+ *   labels     correct = (ious[i] >= iou_thrs[k]) && tp_class[i]; the curve's positive class is correct == 0 (pos_label=0)
+ *   curve      sklearn's roc_curve with drop_intermediate=True (sklearn >= 1.3): scores descending, one point at the end of each
+ *              run of equal scores (tps = positives so far, fps = 1 + index - tps); with more than 2 points a point stays iff it is
+ *              first, last, or the second difference of fps or tps at it is non-zero; (0, 0) with threshold +inf in front;
+ *              fpr = fps / fps[-1], tpr = tps / tps[-1]
+ *   result     fix_cd != 0: rate = 1 - interp(1 - budget, fpr, tpr), thr = thresholds[argmin |1 - tpr - rate|]; else
+ *              rate = interp(budget, tpr, fpr), thr = thresholds[argmin |fpr - rate|]; numpy.interp (the last j with xp[j] <= x;
+ *              fp[j] when equal, else (fp[j+1] - fp[j]) / (xp[j+1] - xp[j]) * (x - xp[j]) + fp[j]), the first minimum; auc = the
+ *              trapezoid sum over the kept points.  A problem with one label only: thr = +inf, rate = auc = NaN.  budget must lie
+ *              strictly between 0 and 1: there the two early branches of roc_metrics cannot be taken.
+ *   limits     2 <= N <= UDA_THR_MAX_N, 1 <= U <= UDA_THR_MAX_U, 1 <= K <= UDA_THR_MAX_THRS, 1 <= P <= UDA_THR_MAX_P,
+ *              0 <= G <= UDA_THR_MAX_G, group ids inside 0..G-1; anything else is refused, never truncated.  Values must be
+ *              finite (the Python layer checks).
+ *   scratch    allocated and freed inside the call.  Candidates go through in chunks; with Npad = max(2048, N rounded up to a
+ *              power of two) one candidate takes 12 * Npad + 8 * N * K + 24 * K + 8 * U * max(G, 1) bytes, and a chunk is as many
+ *              candidates as fit 64 MiB (at least one, which takes 70 MiB at the limits; at most 16384): scratch never exceeds
+ *              70 MiB whatever P is.  On top: the inputs, 8 * N * (U + 1) + 5 * N bytes, and the mask, 4 * N. */
+#define UDA_THR_MAX_N 262144
+#define UDA_THR_MAX_U 4
+#define UDA_THR_MAX_THRS 32
+#define UDA_THR_MAX_P 65536
+#define UDA_THR_MAX_G 8192
+int uda_thr_objective_np(int32_t device, const double* uncerts, const double* ious, const uint8_t* tp_class, const int32_t* group,
+                         int32_t N, int32_t U, int32_t G, const double* iou_thrs, int32_t K, const double* params, int32_t P,
+                         int32_t fix_cd, double budget, double* thr, double* rate, double* auc);
 
 /* serve = set_images_u8 + run + get_detections */
 int uda_serve(uda_ctx_t* ctx, const uint8_t* images, int32_t n, int32_t h, int32_t w,

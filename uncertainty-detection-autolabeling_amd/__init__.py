@@ -9,4 +9,5 @@ Modules:
   capi            ctypes binding of include/uda_hip.h (csrc/libuda_hip.so)
   infer_lib       ServingDriver-shaped boundary (serve / predict / benchmark)
   dist            image sharding + detection gather (torch.distributed / RCCL)
+  thresholding    failure-recognition weights and threshold from validation rows (roc_objective, UncertOptimal, autolabel_verdict)
 """

@@ -654,6 +654,289 @@ void launch_coco_match(const CocoMatchArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(coco_match_kernel<false>, grid, dim3(128), 0, s, a);
 }
 
+// ------------------------------------------------------------------------------------ thresholding: batched ROC objective
+// roc_metrics(sum(param * uncert), (ious >= iou_thr) * tps_class) of the reference (uncertainty_analysis.py:44-152) for a chunk of
+// candidate weight vectors.  The order of a candidate's combined score does not depend on the IoU threshold, so a candidate is
+// sorted once (bitonic network on (key, row): tiles of THR_TILE in LDS, the wider strides in global memory) and its K curves are
+// scans over that order.  Counts are integers, the few float64 operations are the reference's, in its order (this file is built
+// with FMA contraction off).
+enum { THR_SORT_THREADS = THR_TILE / 2, THR_CURVE_THREADS = 512 };
+
+__global__ void __launch_bounds__(256) thr_mask_kernel(ThrArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.N) return;
+  const double iou = a.ious[i];
+  const bool tp = a.tp_class[i] != 0;
+  uint32_t m = 0;
+  for (int k = 0; k < a.K; ++k) m |= (uint32_t)(tp && iou >= a.thr[k]) << k;
+  a.mask[i] = m;
+}
+
+// ~(bits that order like the value): an ascending sort of the key is a descending sort of the score
+__device__ __forceinline__ uint64_t thr_key_of(double u) {
+  if (u == 0.0) u = 0.0;     // -0.0 and 0.0 are one value
+  const uint64_t b = (uint64_t)__double_as_longlong(u);
+  return ~(b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull));
+}
+__device__ __forceinline__ double thr_score_of(uint64_t key) {
+  const uint64_t o = ~key;
+  return __longlong_as_double((long long)(o ^ ((o >> 63) ? 0x8000000000000000ull : ~0ull)));
+}
+
+// compare-exchange steps k, j = j0 .. 1 of the bitonic network on one tile held in LDS; `base` is the tile's first position
+__device__ __forceinline__ void thr_tile_steps(uint64_t* sk, int32_t* si, int base, int k, int j0) {
+  const int t = threadIdx.x;
+  for (int j = j0; j > 0; j >>= 1) {
+    const int i = 2 * t - (t & (j - 1)), l = i + j;
+    const bool asc = ((base + i) & k) == 0;
+    const uint64_t x = sk[i], y = sk[l];
+    if ((x > y) == asc) {
+      sk[i] = y; sk[l] = x;
+      const int32_t r = si[i]; si[i] = si[l]; si[l] = r;
+    }
+    __syncthreads();
+  }
+}
+
+// combined score of the tile's rows -> keys, then the tile sorted (ascending or descending by its place in the network)
+__global__ void __launch_bounds__(THR_SORT_THREADS) thr_sort_tile_kernel(ThrArgs a) {
+  __shared__ uint64_t sk[THR_TILE];
+  __shared__ int32_t si[THR_TILE];
+  const int base = blockIdx.x * THR_TILE, p = blockIdx.y;
+  const int stride = a.U * (a.G > 0 ? a.G : 1);
+  const double* w = a.params + (size_t)p * stride;
+  for (int e = threadIdx.x; e < THR_TILE; e += THR_SORT_THREADS) {
+    const int i = base + e;
+    uint64_t key = ~0ull;
+    if (i < a.N) {
+      const double* wi = a.group ? w + (size_t)a.group[i] * a.U : w;
+      double u = __dmul_rn(wi[0], a.uncerts[i]);          // every product rounded on its own: a fused one moves the ties
+      for (int j = 1; j < a.U; ++j) u = __dadd_rn(u, __dmul_rn(wi[j], a.uncerts[(size_t)j * a.N + i]));
+      key = thr_key_of(u);
+    }
+    sk[e] = key;
+    si[e] = i < a.N ? i : -1;
+  }
+  __syncthreads();
+  for (int k = 2; k <= THR_TILE; k <<= 1) thr_tile_steps(sk, si, base, k, k >> 1);
+  const size_t o = (size_t)p * a.Npad + base;
+  for (int e = threadIdx.x; e < THR_TILE; e += THR_SORT_THREADS) {
+    a.keys[o + e] = sk[e];
+    a.rows[o + e] = si[e];
+  }
+}
+
+// one step (k, j) with j >= THR_TILE: partners lie in different tiles
+__global__ void __launch_bounds__(256) thr_merge_global_kernel(ThrArgs a, int k, int j) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.Npad / 2) return;
+  const int i = 2 * t - (t & (j - 1)), l = i + j;
+  uint64_t* keys = a.keys + (size_t)blockIdx.y * a.Npad;
+  int32_t* rows = a.rows + (size_t)blockIdx.y * a.Npad;
+  const uint64_t x = keys[i], y = keys[l];
+  if ((x > y) == ((i & k) == 0)) {
+    keys[i] = y; keys[l] = x;
+    const int32_t r = rows[i]; rows[i] = rows[l]; rows[l] = r;
+  }
+}
+
+// the steps j = THR_TILE / 2 .. 1 of stage k, inside one tile
+__global__ void __launch_bounds__(THR_SORT_THREADS) thr_merge_tile_kernel(ThrArgs a, int k) {
+  __shared__ uint64_t sk[THR_TILE];
+  __shared__ int32_t si[THR_TILE];
+  const int base = blockIdx.x * THR_TILE;
+  const size_t o = (size_t)blockIdx.y * a.Npad + base;
+  for (int e = threadIdx.x; e < THR_TILE; e += THR_SORT_THREADS) {
+    sk[e] = a.keys[o + e];
+    si[e] = a.rows[o + e];
+  }
+  __syncthreads();
+  thr_tile_steps(sk, si, base, k, THR_TILE / 2);
+  for (int e = threadIdx.x; e < THR_TILE; e += THR_SORT_THREADS) {
+    a.keys[o + e] = sk[e];
+    a.rows[o + e] = si[e];
+  }
+}
+
+// inclusive sums of two counters over the block (wave shuffles, then the wave totals through LDS); sw: 2 * waves ints
+__device__ __forceinline__ void thr_block_scan_add2(int& x, int& y, int* sw) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int tx = __shfl_up(x, d, 64), ty = __shfl_up(y, d, 64);
+    if (lane >= d) { x += tx; y += ty; }
+  }
+  __syncthreads();               // sw may still be read from the previous use
+  if (lane == 63) { sw[2 * wave] = x; sw[2 * wave + 1] = y; }
+  __syncthreads();
+  for (int v = 0; v < wave; ++v) { x += sw[2 * v]; y += sw[2 * v + 1]; }
+}
+
+// a point of the curve survives drop_intermediate iff it is first, last, or its run and the next differ in positives or negatives
+__device__ __forceinline__ bool thr_kept(const int32_t* E, const int32_t* T, int r, int M) {
+  if (r == 0 || r == M - 1) return true;
+  const int e0 = E[r - 1], e = E[r], e1 = E[r + 1], t0 = T[r - 1], t = T[r], t1 = T[r + 1];
+  const int dt = t - t0, dtn = t1 - t;
+  return dt != dtn || (e - e0) - dt != (e1 - e) - dtn;
+}
+
+// one block per (IoU threshold, candidate) over the candidate's sorted order
+__global__ void __launch_bounds__(THR_CURVE_THREADS) thr_curve_kernel(ThrArgs a) {
+  constexpr int B = THR_CURVE_THREADS, W = B / 64;
+  __shared__ int sw[2 * W];
+  __shared__ int s_incl[B];
+  __shared__ int s_tot[2];
+  __shared__ double s_d[B];
+  __shared__ int s_i[B];
+  __shared__ double s_rate;
+  const int tid = threadIdx.x, k = blockIdx.x, p = blockIdx.y, N = a.N;
+  const uint64_t* keys = a.keys + (size_t)p * a.Npad;
+  const int32_t* rows = a.rows + (size_t)p * a.Npad;
+  int32_t* E = a.runs + ((size_t)p * a.K + k) * 2 * (size_t)N;
+  int32_t* T = E + N;
+  double* out = a.out + ((size_t)p * a.K + k) * 3;
+
+  // 1. runs of equal scores: E[r] = last position of run r, T[r] = positives (correct == 0) up to it
+  int runs = 0, npos = 0;
+  for (int base = 0; base < N; base += B) {
+    const int i = base + tid;
+    int flag = 0, pos = 0;
+    if (i < N) {
+      flag = i + 1 == N || keys[i] != keys[i + 1];
+      const int row = rows[i];              // a padding row cannot come before N for finite scores
+      pos = row >= 0 && !((a.mask[row] >> k) & 1u);
+    }
+    int f = flag, q = pos;
+    thr_block_scan_add2(f, q, sw);
+    if (flag) {
+      const int r = runs + f - 1;
+      E[r] = i;
+      T[r] = npos + q;
+    }
+    if (tid == B - 1) { s_tot[0] = f; s_tot[1] = q; }
+    __syncthreads();
+    runs += s_tot[0];
+    npos += s_tot[1];
+    __syncthreads();
+  }
+  const int M = runs, nneg = N - npos;
+  if (npos == 0 || nneg == 0) {       // one label only: fpr or tpr is 0 / 0 throughout
+    if (tid == 0) {
+      out[0] = __longlong_as_double(0x7ff0000000000000ll);
+      out[1] = out[2] = __longlong_as_double(0x7ff8000000000000ll);
+    }
+    return;
+  }
+  const double dpos = (double)npos, dneg = (double)nneg;
+  const double x = a.fix_cd ? 1.0 - a.budget : a.budget;
+
+  // 2. kept points: trapezoid terms against the previous kept point, and the segment of interp that brackets x
+  int prev_carry = -1, jmax = -1, j1min = 0x7fffffff;
+  double area = 0.0;
+  for (int base = 0; base < M; base += B) {
+    const int r = base + tid;
+    const bool kept = r < M && thr_kept(E, T, r, M);
+    int v = kept ? r : -1;
+    for (int d = 1; d < 64; d <<= 1) v = max(v, __shfl_up(v, d, 64));    // lanes below d read their own value
+    s_incl[tid] = v;
+    __syncthreads();
+    int prev = prev_carry;
+    for (int wv = 0; wv < (tid >> 6); ++wv) prev = max(prev, s_incl[wv * 64 + 63]);
+    if (tid & 63) prev = max(prev, s_incl[tid - 1]);
+    int last = prev_carry;
+    for (int wv = 0; wv < W; ++wv) last = max(last, s_incl[wv * 64 + 63]);
+    prev_carry = last;
+    __syncthreads();
+    if (kept) {
+      const int t = T[r];
+      const double fpr = (double)(E[r] + 1 - t) / dneg, tpr = (double)t / dpos;
+      double fpr0 = 0.0, tpr0 = 0.0;
+      if (prev >= 0) {
+        const int t0 = T[prev];
+        fpr0 = (double)(E[prev] + 1 - t0) / dneg;
+        tpr0 = (double)t0 / dpos;
+      }
+      area += (fpr - fpr0) * (tpr + tpr0) / 2.0;
+      if ((a.fix_cd ? fpr : tpr) <= x) jmax = max(jmax, r); else j1min = min(j1min, r);
+    }
+  }
+  s_d[tid] = area;
+  s_incl[tid] = jmax;
+  s_i[tid] = j1min;
+  __syncthreads();
+  for (int h = B / 2; h > 0; h >>= 1) {
+    if (tid < h) {
+      s_d[tid] += s_d[tid + h];
+      s_incl[tid] = max(s_incl[tid], s_incl[tid + h]);
+      s_i[tid] = min(s_i[tid], s_i[tid + h]);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int j = s_incl[0], j1 = s_i[0];     // j = -1: the point (0, 0) in front; j1 exists, the last point has xp = 1 > x
+    double xj = 0.0, fj = 0.0;
+    if (j >= 0) {
+      const int t = T[j];
+      const double fpr = (double)(E[j] + 1 - t) / dneg, tpr = (double)t / dpos;
+      xj = a.fix_cd ? fpr : tpr;
+      fj = a.fix_cd ? tpr : fpr;
+    }
+    double res = fj;
+    if (x != xj && j1 < M) {
+      const int t = T[j1];
+      const double fpr = (double)(E[j1] + 1 - t) / dneg, tpr = (double)t / dpos;
+      const double x1 = a.fix_cd ? fpr : tpr, f1 = a.fix_cd ? tpr : fpr;
+      const double slope = (f1 - fj) / (x1 - xj);
+      res = slope * (x - xj) + fj;
+    }
+    s_rate = a.fix_cd ? 1.0 - res : res;
+    out[2] = s_d[0];
+  }
+  __syncthreads();
+  const double rate = s_rate;
+
+  // 3. the kept point nearest to the rate, the first of equals; r = -1 is the point in front, whose threshold is +inf
+  double best = a.fix_cd ? fabs(1.0 - 0.0 - rate) : fabs(0.0 - rate);
+  int best_r = -1;
+  if (tid != 0) { best = __longlong_as_double(0x7ff0000000000000ll); best_r = 0x7fffffff; }
+  for (int r = tid; r < M; r += B) {
+    if (!thr_kept(E, T, r, M)) continue;
+    const int t = T[r];
+    const double fpr = (double)(E[r] + 1 - t) / dneg, tpr = (double)t / dpos;
+    const double val = a.fix_cd ? fabs(1.0 - tpr - rate) : fabs(fpr - rate);
+    if (val < best) { best = val; best_r = r; }
+  }
+  s_d[tid] = best;
+  s_i[tid] = best_r;
+  __syncthreads();
+  for (int h = B / 2; h > 0; h >>= 1) {
+    if (tid < h) {
+      const double ov = s_d[tid + h];
+      const int orr = s_i[tid + h];
+      if (ov < s_d[tid] || (ov == s_d[tid] && orr < s_i[tid])) { s_d[tid] = ov; s_i[tid] = orr; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    out[0] = s_i[0] < 0 ? __longlong_as_double(0x7ff0000000000000ll) : thr_score_of(keys[E[s_i[0]]]);
+    out[1] = rate;
+  }
+}
+
+void launch_thr_mask(const ThrArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(thr_mask_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a);
+}
+
+void launch_thr_objective(const ThrArgs& a, hipStream_t s) {
+  const dim3 tiles(a.Npad / THR_TILE, a.Pc);
+  hipLaunchKernelGGL(thr_sort_tile_kernel, tiles, dim3(THR_SORT_THREADS), 0, s, a);
+  for (int k = 2 * THR_TILE; k <= a.Npad; k <<= 1) {
+    for (int j = k >> 1; j >= THR_TILE; j >>= 1)
+      hipLaunchKernelGGL(thr_merge_global_kernel, dim3(a.Npad / 2 / 256, a.Pc), dim3(256), 0, s, a, k, j);
+    hipLaunchKernelGGL(thr_merge_tile_kernel, tiles, dim3(THR_SORT_THREADS), 0, s, a, k);
+  }
+  hipLaunchKernelGGL(thr_curve_kernel, dim3(a.K, a.Pc), dim3(THR_CURVE_THREADS), 0, s, a);
+}
+
 // ------------------------------------------------------------------------------------ aggregate + decode
 __device__ __forceinline__ float exp32(float x) { return (float)exp((double)x); }
 

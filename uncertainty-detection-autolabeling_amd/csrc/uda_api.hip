@@ -3092,6 +3092,82 @@ extern "C" int uda_eval_match_np(int32_t device, const float* det_rows, const fl
   return 0;
 }
 
+// the objective of the thresholding search for P candidates: host arrays in, chunks of candidates through the device (scratch of
+// at most kThrScratchBytes, or one candidate's), host arrays out; its own allocations
+static const size_t kThrScratchBytes = (size_t)64 << 20;
+extern "C" int uda_thr_objective_np(int32_t device, const double* uncerts, const double* ious, const uint8_t* tp_class,
+                                    const int32_t* group, int32_t N, int32_t U, int32_t G, const double* iou_thrs, int32_t K,
+                                    const double* params, int32_t P, int32_t fix_cd, double budget, double* thr, double* rate,
+                                    double* auc) {
+  const char* who = "uda_thr_objective_np";
+  if (N < 2 || N > THR_MAX_N) return fail(nullptr, "%s: %d rows, 2..%d are taken", who, N, (int)THR_MAX_N);
+  if (U < 1 || U > THR_MAX_U) return fail(nullptr, "%s: %d uncertainties, 1..%d are taken", who, U, (int)THR_MAX_U);
+  if (K < 1 || K > THR_MAX_K) return fail(nullptr, "%s: %d IoU thresholds, 1..%d are taken", who, K, (int)THR_MAX_K);
+  if (P < 1 || P > THR_MAX_P) return fail(nullptr, "%s: %d candidates, 1..%d are taken", who, P, (int)THR_MAX_P);
+  if (G < 0 || G > THR_MAX_G) return fail(nullptr, "%s: %d groups, 0..%d are taken", who, G, (int)THR_MAX_G);
+  if (!uncerts || !ious || !tp_class || !iou_thrs || !params) return fail(nullptr, "%s: NULL input", who);
+  if ((G > 0) != (group != nullptr)) return fail(nullptr, "%s: group ids and G > 0 go together", who);
+  if (!(budget > 0.0 && budget < 1.0)) return fail(nullptr, "%s: budget %g is not strictly between 0 and 1", who, budget);
+  for (int i = 0; group && i < N; ++i)
+    if (group[i] < 0 || group[i] >= G) return fail(nullptr, "%s: group id %d of row %d outside 0..%d", who, group[i], i, G - 1);
+  int Npad = THR_TILE;
+  while (Npad < N) Npad <<= 1;
+  const size_t n = (size_t)N, stride = (size_t)U * (size_t)(G > 0 ? G : 1);
+  const size_t per = 12 * (size_t)Npad + 8 * n * K + 24 * (size_t)K + 8 * stride;
+  size_t fit = kThrScratchBytes / per;
+  const int Pc = (int)std::min<size_t>(std::max<size_t>(fit, 1), std::min<size_t>((size_t)P, THR_MAX_CHUNK));
+  double *d_unc = nullptr, *d_iou = nullptr, *d_par = nullptr, *d_out = nullptr;
+  uint8_t* d_tp = nullptr;
+  int32_t *d_group = nullptr, *d_rows = nullptr, *d_runs = nullptr;
+  uint32_t* d_mask = nullptr;
+  uint64_t* d_keys = nullptr;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = dalloc(&d_unc, n * U);
+  if (e == hipSuccess) e = dalloc(&d_iou, n);
+  if (e == hipSuccess) e = dalloc(&d_tp, n);
+  if (e == hipSuccess && group) e = dalloc(&d_group, n);
+  if (e == hipSuccess) e = dalloc(&d_mask, n);
+  if (e == hipSuccess) e = dalloc(&d_par, (size_t)Pc * stride);
+  if (e == hipSuccess) e = dalloc(&d_keys, (size_t)Pc * Npad);
+  if (e == hipSuccess) e = dalloc(&d_rows, (size_t)Pc * Npad);
+  if (e == hipSuccess) e = dalloc(&d_runs, (size_t)Pc * K * 2 * n);
+  if (e == hipSuccess) e = dalloc(&d_out, (size_t)Pc * K * 3);
+  if (e == hipSuccess) e = hipMemcpy(d_unc, uncerts, n * U * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_iou, ious, n * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_tp, tp_class, n, hipMemcpyHostToDevice);
+  if (e == hipSuccess && group) e = hipMemcpy(d_group, group, n * sizeof(int32_t), hipMemcpyHostToDevice);
+  ThrArgs a{};
+  a.uncerts = d_unc; a.ious = d_iou; a.tp_class = d_tp; a.group = d_group; a.params = d_par; a.mask = d_mask;
+  a.keys = d_keys; a.rows = d_rows; a.runs = d_runs; a.out = d_out;
+  a.N = N; a.Npad = Npad; a.U = U; a.G = G; a.K = K; a.fix_cd = fix_cd != 0; a.budget = budget;
+  for (int k = 0; k < K; ++k) a.thr[k] = iou_thrs[k];
+  if (e == hipSuccess) {
+    launch_thr_mask(a, nullptr);
+    e = hipGetLastError();
+  }
+  std::vector<double> h((size_t)Pc * K * 3);
+  for (int p0 = 0; e == hipSuccess && p0 < P; p0 += Pc) {
+    a.Pc = std::min(Pc, P - p0);
+    e = hipMemcpy(d_par, params + (size_t)p0 * stride, (size_t)a.Pc * stride * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+    launch_thr_objective(a, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(h.data(), d_out, (size_t)a.Pc * K * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) break;
+    for (size_t q = 0; q < (size_t)a.Pc * K; ++q) {
+      const size_t o = (size_t)p0 * K + q;
+      if (thr) thr[o] = h[3 * q];
+      if (rate) rate[o] = h[3 * q + 1];
+      if (auc) auc[o] = h[3 * q + 2];
+    }
+  }
+  void* ptrs[] = {d_unc, d_iou, d_tp, d_group, d_mask, d_par, d_keys, d_rows, d_runs, d_out};
+  for (void* p : ptrs)
+    if (p) hipFree(p);
+  if (e != hipSuccess) return fail(nullptr, "%s: %s", who, hipGetErrorString(e));
+  return 0;
+}
+
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,
                                  const int32_t* tab_off, const double* xs, const double* ys, const float* temps, float* out) {
   if (!c || !out) return c ? fail(c, "calibrate_box: NULL out") : 1;

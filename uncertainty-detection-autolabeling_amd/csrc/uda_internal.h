@@ -432,6 +432,29 @@ struct CocoMatchArgs {
 };
 void launch_coco_match(const CocoMatchArgs& a, hipStream_t s);
 
+// thresholding: the batched ROC objective (reference uncertainty_analysis.py:44-152 on sklearn's roc_curve).  One chunk of Pc
+// candidates per launch_thr_objective: combined score -> (descending key, row) sorted per candidate -> one curve per (candidate,
+// IoU threshold).  Every buffer is the caller's; launch_thr_mask fills `mask` once per call.
+enum { THR_MAX_N = UDA_THR_MAX_N, THR_MAX_U = UDA_THR_MAX_U, THR_MAX_K = UDA_THR_MAX_THRS, THR_MAX_P = UDA_THR_MAX_P,
+       THR_MAX_G = UDA_THR_MAX_G, THR_TILE = 2048, THR_MAX_CHUNK = 16384 };
+struct ThrArgs {
+  const double* uncerts;    // [U, N]
+  const double* ious;       // [N]
+  const uint8_t* tp_class;  // [N]
+  const int32_t* group;     // [N] values 0..G-1, or null (G = 0)
+  const double* params;     // [Pc, U * max(G, 1)]
+  uint32_t* mask;           // [N] bit k: (ious >= thr[k]) && tp_class
+  uint64_t* keys;           // [Pc, Npad] scratch: ~(order-preserving bits of the combined score), padded with ~0
+  int32_t* rows;            // [Pc, Npad] scratch: the row a key came from
+  int32_t* runs;            // [Pc, K, 2, N] scratch: last sorted position of every run of equal scores, positives up to it
+  double* out;              // [Pc, K, 3] thr, rate, auc
+  int N, Npad, U, G, K, Pc, fix_cd;
+  double budget;
+  double thr[THR_MAX_K];
+};
+void launch_thr_mask(const ThrArgs& a, hipStream_t s);
+void launch_thr_objective(const ThrArgs& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

@@ -193,6 +193,12 @@ def default_detection_configs():
     h.calib_method_box = "iso_perclscoo"
     h.infer_draw_uncert = True
     h.consistency_ssl = False           # flip / blur / noise agreement columns in prediction_data (hparams_config.py:240)
+    # thresholding (hparams_config.py:243-248): budget, whether it is on correct / missing detections, the IoU thresholds the
+    # weights are optimised over, the uncertainties that are combined (entropy and aleatoric box sigma)
+    h.thr_fpr_tpr = 0.95
+    h.thr_cd = True
+    h.thr_iou_thrs = [0.5, 0.55, 0.6, 0.65, 0.7, 0.75]      # list(np.round(np.arange(0.50, 0.76, 0.05), 2))
+    h.thr_sel_uncert = "ENTALBOX"
     h.early_stopping_patience = 0
 
     # --- training-only keys that the shipped YAMLs set (kept so they load) ---

@@ -201,6 +201,10 @@ MODEL_PARAM_HANDLING = {
                        "variants, infer_model.py:768-848); writers.predict_to_file writes cons_iou / cons_cls",
     "assign_gt_box": "consumed: default method of ServingDriver.assign_ground_truth / serve_validate (IoU | MSE | else the GT "
                      "row's own rank; utils_extra.py:44-64, validate_model.py:337, calibrate_model.py:140)",
+    "thr_fpr_tpr": "consumed by thresholding (budget of the ROC search)",
+    "thr_cd": "consumed by thresholding (budget on correct / missing detections, else on false ones)",
+    "thr_iou_thrs": "consumed by thresholding (IoU thresholds the weights are optimised over)",
+    "thr_sel_uncert": "consumed by thresholding.from_validate_records (ENT and / or ALBOX)",
     # --- training-only keys the shipped YAMLs set
     "early_stopping_patience": "inert: training",
     "count_classes": "inert: training", "boxloss_type": "inert: training", "save_freq": "inert: training",
