@@ -11,246 +11,13 @@
 #include <string>
 #include <vector>
 
-#include "uda_internal.h"
-
-using namespace uda;
+#include "uda_ctx.h"
 
 static thread_local std::string g_create_error;
 
-struct ProfSlot {
-  double total_ms = 0;
-  int64_t launches = 0;       // in units of PLANNED ops: a launch that covers a group of n ops counts n (plan.op_costs counts per op)
-  struct Pending { hipEvent_t first, second; int weight; };
-  std::vector<Pending> pending;
-};
-
-struct uda_ctx {
-  uda_model_t model;
-  std::vector<uda_buf_desc_t> bufs;
-  std::vector<uda_op_t> ops;
-  std::vector<uda_drop_site_t> sites;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-
-  float* d_weights = nullptr;
-  int64_t n_weights = 0;
-  // split-bf16 copies of the 1x1 kernels in MFMA fragment order (kernels_pwb.hip); -1 = op keeps the f32 path
-  uint16_t* d_wsplit = nullptr;
-  std::vector<int64_t> wsplit_off;
-  std::vector<int64_t> wpar_off;   // MBX: offset (uint16 units) of the per-slab depthwise operand block inside d_wsplit
-  int pw_parts = UDA_SPLIT_F16X2;  // requested split scheme of the 1x1 contractions (uda_model_t.pw_scheme)
-  std::vector<int> wscheme;        // per op: the scheme its packed weights use (an op whose weights do not suit fp16 pieces keeps bf16 x3)
-  std::vector<float> wunscale;     // per op: 1 / (power-of-two factor folded into the packed weights); 1 unless fp16 pieces
-  std::vector<float> wascale;      // per op: factor on the A operand (fp16 separable conv: pre-scaled depthwise taps); part of wunscale
-  int n_f16_ops = 0, n_f16_demoted = 0;
-  std::vector<char> buf_f16;       // per buffer: stored as fp16 in its float32-sized slot (set_f16_storage)
-  // fp16 pieces: a kernel that splits an operand above 65504 sets bit 0 of ITS OP's flag word.  Two arrays of n_ops + 1
-  // words (index n_ops: launches outside the op list): pipelined run s raises its flags in array s, everything else in array 0.
-  unsigned* d_oor = nullptr;
-  unsigned* oor_cur = nullptr;     // the array the launches being queued raise their flags in
-  int oor_half = 0;                // the array the readers of the current results look at (check_split_range)
-  bool oor_armed = false;          // a run with fp16-piece ops has been queued since the flags were last read
-  // An op that raises its flag is re-packed with three bf16 pieces (float32 exponent range) and the run is served again
-  // on the same handle (demote_ops / replay_run): the reference computes in float32 and never rejects an input on magnitude.
-  std::vector<float> h_weights;    // host copy of the weight blob (for the re-packing)
-  std::vector<uint16_t*> wovr;     // per op: device copy of its re-packed weights (null: its slice of d_wsplit)
-  std::vector<int64_t> wovr_par;   // per op: uint16 offset of the parameter block inside wovr (-1: none)
-  int64_t range_demotions = 0;     // ops re-packed so far (uda_range_demotions)
-  // What a run read, so that it can be served again: input slot / float image generation, seed, image offset, masks.
-  struct RunRec {
-    bool valid = false, do_post = false, have_u8 = false, masks_injected = false;
-    int pm = 0, cur = 0, n = 0;
-    uint64_t slot_gen = 0, f32_gen = 0, masks_gen = 0, seed = 0;
-    int64_t image_offset = 0;
-  };
-  RunRec last_run;                 // the last synchronous uda_run
-  const RunRec* replay_rec = nullptr;   // the run whose results the readers are looking at (null: cannot be served again)
-  uint64_t f32_gen = 0, masks_gen = 0;
-  float* d_arena = nullptr;
-  uint4* d_w0frag[2] = {nullptr, nullptr};   // gated, split projection kernel per gate row for the fused block-1 kernel (launch_w0gate), per chunk lane
-  size_t w0frag_cap[2] = {0, 0};
-  // chunk lanes: consecutive chunks alternate between independent (stream, arena) pairs so that the
-  // barrier-heavy kernels of one chunk overlap the streaming kernels of the other
-  int n_lanes = 1;
-  hipStream_t lane_stream[2] = {nullptr, nullptr};
-  float* lane_arena[2] = {nullptr, nullptr};
-  hipEvent_t ev_start = nullptr, ev_done[2] = {nullptr, nullptr};
-  int last_lane = 0;
-  // post-process of chunk i (aggregate, NMS, gather: small latency-bound launches) runs on its own stream
-  // beside the conv stack of chunk i + 1; only the last chunk's post-process is exposed
-  hipStream_t post_stream = nullptr;
-  std::vector<hipEvent_t> ev_chunk;
-  hipEvent_t ev_post = nullptr;
-  int post_overlap = 1;
-  float* d_anchors = nullptr;
-  int A_tot = 0;
-  int a_off[UDA_MAX_LEVELS + 1];
-
-  // inputs.  uint8 batches go through one of two slots (device buffer + pinned host staging buffer each): `cur` feeds the
-  // next uda_run; the other one takes a batch that is uploaded on the copy stream while the current one is being
-  // processed (uda_prefetch_images_u8 / uda_swap_prefetched) - the feed then costs no device time.
-  struct U8Slot {
-    uint8_t* d = nullptr;        // device: geometry table, then the images back to back (image i at d_img + geo[i].off)
-    size_t cap = 0;
-    uint8_t* pinned = nullptr;   // host staging (hipHostMalloc): pageable caller memory is copied here, DMA reads this
-    size_t pcap = 0;
-    int n = 0;
-    bool valid = false, uploaded = false;
-    uint64_t gen = 0;            // bumped by every upload into this slot (a run can be served again only from unchanged inputs)
-    std::vector<PreGeo> geo;     // per image: offset, raw size, scaled size, sampling ratios (dataloader.py:123-152)
-    PreGeo* d_geo = nullptr;     // = d (the table leads the buffer)
-    uint8_t* d_img = nullptr;    // = d + header
-    std::vector<float> scales;   // image_scale per image (1 / resize scale)
-    hipEvent_t ev = nullptr;     // upload complete (copy stream)
-  } u8[2];
-  int cur = 0;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_pre_done[2] = {nullptr, nullptr};   // the preprocess kernel has consumed slot i (its buffer may be refilled)
-  bool have_u8 = false;
-  int stem_act = UDA_ACT_SWISH; // activation of the stem op (the uint8 stem is a swish kernel)
-  bool stem_from_u8 = false;   // this run's stem ops read the uint8 slot (set by run_network)
-  bool pre_valid = false;      // d_images holds the preprocessed current batch (false: the stem read the uint8 images itself)
-  int stem_co = 0;             // output channels of the stem op (0: no stem op in the plan)
-  float* d_images = nullptr;   // [max_images, H, W, 3]
-  float* d_scales = nullptr;   // [max_images]
-  // consistency check (uda_run_consistency): images [noise_from, n_images) of the run are the noise variant of images
-  // [0, n_images - noise_from), preprocessed by the NOISE instantiation of the preprocess kernel (-1: an ordinary run)
-  int noise_from = -1;
-  std::vector<PreGeo> cons_geo;      // geometry table of the 4n images of the last consistency run
-  double* d_cons_iou = nullptr;      // [max_images, M] cons_iou of the last consistency run (lazy)
-  uint8_t* d_cons_agree = nullptr;   // [max_images, M] cons_cls
-  int cons_n = 0;                    // originals of the last consistency run (0: none)
-  std::vector<float> h_scales;
-  int n_images = 0;
-  int sh = 0, sw = 0;
-
-  // dropout
-  float* d_masks = nullptr;
-  int64_t mask_cap = 0;        // floats
-  int64_t sum_site_ch = 0;
-  int max_c4 = 0;
-  std::vector<int64_t> site_off;
-  int64_t* d_site_off = nullptr;
-  int32_t* d_site_ch = nullptr;
-  float* d_site_rate = nullptr;
-  bool masks_injected = false;
-  int masks_rows = 0;
-  uint64_t seed = 0;
-  int64_t image_offset = 0;
-  int t_first = 0, t_stride = 1, t_total = 0;      // this handle's samples inside the global sample axis (0: all of them; uda_set_dropout_sample_shard)
-
-  // head outputs [max_images * Tx, hw, ch] per level
-  float* d_cls[UDA_MAX_LEVELS] = {};
-  float* d_box[UDA_MAX_LEVELS] = {};
-  int cls_ch = 0, box_ch = 0;
-
-  // candidates
-  float *d_cboxes = nullptr, *d_cscores = nullptr, *d_clogits = nullptr;
-  int32_t* d_cclasses = nullptr;
-  float *d_ucls = nullptr, *d_ual = nullptr, *d_uep = nullptr;
-  int Kc = 0;                  // candidates per image: A_tot, or max_nms_inputs on the top-k path
-  float* d_clsmean = nullptr;  // [max_images, A_tot*C]  (top-k path)
-  int32_t* d_cand_flat = nullptr;  // [max_images, Kc]   (top-k path)
-  void* d_topk_ws = nullptr;       // scratch of the multi-block top-k selection
-  // nms workspaces: [0] global mode (one problem per image), [1] per-class mode (images*classes problems)
-  struct NmsWs {
-    float *stale = nullptr, *tent = nullptr, *ub = nullptr, *sel_score = nullptr, *sel_box = nullptr;
-    int32_t *ev = nullptr, *begin = nullptr, *sel_idx = nullptr, *nsel = nullptr, *done = nullptr;
-    unsigned long long *bound = nullptr, *win = nullptr;
-    bool ready = false;
-  } ws[2];
-  // NMS on a score prefix (global mode with the whole anchor set as candidates): sub-problem arrays + workspace
-  struct PrefixWs {
-    int32_t *sub_idx = nullptr, *bad = nullptr;
-    float *sub_scores = nullptr, *sub_boxes = nullptr;
-    uint32_t* excl = nullptr;
-    NmsWs ws;
-    int Lcap = 0;
-  } pfx;
-  std::vector<std::pair<int, int>> pfx_pending;   // image ranges whose prefix flags the host has not looked at yet
-  bool pfx_off = false;                            // set while finish_post redoes rejected images
-  int64_t pfx_fallbacks = 0;                       // images redone on the full candidate set so far
-  int pfx_skip = 0, pfx_backoff = 0;               // runs left without the prefix / length of the last pause
-  // cooperative single-launch NMS: per-problem barrier counters + one error word (barrier timed out)
-  unsigned long long* d_coop_bar = nullptr;       // exchange slots, max_images x nms_coop_slot_words(max_output_size)
-  int* d_coop_err = nullptr;
-  bool coop_used = false;
-  bool coop_off = false;                           // set after a barrier time-out: this handle stays on the two-launch version
-  int64_t coop_fallbacks = 0;                      // post-process runs redone with two launches per epoch after such a time-out
-  int64_t coop_not_launched = 0;                   // NMS runs that wanted the single-launch grid and did not get it (capacity query / launch refused)
-  unsigned long long* d_merge_keys = nullptr;
-  // outputs
-  float *d_oboxes = nullptr, *d_oscores = nullptr, *d_oclasses = nullptr, *d_ologits = nullptr;
-  float *d_oprobs = nullptr, *d_oentropy = nullptr;   // stable softmax / entropy of the selected rows (lazy)
-  float* d_opacked = nullptr;                        // packed detection records for the multi-GPU gather (lazy, uda_detections_device)
-  int32_t* d_ovalid = nullptr;
-  // ground-truth assignment (uda_set_ground_truth / uda_assign_ground_truth): buffers for max_images x gt_cap GT rows, grown when a
-  // call brings more rows per image; nothing is allocated per call in the steady state
-  float *d_gt_boxes = nullptr, *d_gt_classes = nullptr, *h_gt = nullptr;   // h_gt: pinned staging [max_images, gt_cap, 5]
-  hipEvent_t gt_ev = nullptr;        // the upload out of h_gt has been consumed
-  // results of an assignment of n images x G rows, packed so that ONE copy brings them to the host:
-  // iou [n G] float64 | det_index [n G] int32 | count [n] int32 | error flag int32 (the four pointers point into d_asg_pack)
-  char* d_asg_pack = nullptr;
-  int32_t *d_asg_index = nullptr, *d_asg_count = nullptr, *d_asg_err = nullptr;
-  double* d_asg_iou = nullptr;
-  std::vector<char> h_asg;           // host copy of the pack (filled by the first reader of an assignment)
-  float* d_asg_rows = nullptr;       // [max_images * gt_cap, assigned_row_cols]
-  int gt_cap = 0, gt_n = 0, gt_G = 0; // rows per image the buffers hold; images / rows per image of the GT that is set (0: none)
-  int asg_n = 0, asg_G = 0;          // images / rows per image of the last assignment (0: none)
-  int64_t asg_rows = -1;             // sum(count) of the last assignment once the host has seen it
-  // active-learning image scores (uda_score_images), packed for max_images so that ONE copy brings them to the host:
-  // components [n, n_comp] float64 | count [n] int32 | class_counts [n, num_classes] int32 | error flag int32
-  char* d_score_pack = nullptr;
-  std::vector<char> h_score;         // host copy of the pack (filled by the first reader of a scoring)
-  int score_n = 0, score_nc = 0;     // images / components of the last scoring (0: none)
-  bool score_fetched = false;
-  // COCO matching (uda_set_eval_ground_truth / uda_eval_match): ground truth [max_images, egt_cap, 7], grown when a call brings
-  // more rows per image; results packed for max_images so that ONE copy brings them to the host:
-  // records [n, M] x 44 bytes | npig [n, num_classes, 4] int32 | used [n] int32
-  float *d_egt = nullptr, *h_egt = nullptr;   // h_egt: pinned staging
-  hipEvent_t egt_ev = nullptr;       // the upload out of h_egt has been consumed
-  char* d_eval_pack = nullptr;
-  std::vector<char> h_eval;          // host copy of the pack (filled by the first reader of a match)
-  int egt_cap = 0, egt_n = 0, egt_G = 0;   // rows per image the buffer holds; images / rows per image of the GT that is set (0: none)
-  int eval_n = 0;                    // images of the last match (0: none)
-  bool eval_fetched = false;
-  int last_post_mode = 0;
-  int last_n = 0;
-  int last_chunk_i0 = 0, last_chunk_n = 0;
-  // Pipelined runs (uda_run_async / uda_collect): the post-process of run k (aggregate, NMS, gather: ~4 ms of latency-bound
-  // launches on the post stream) is NOT joined into the main stream; run k + 1's network starts at once and only its first
-  // head-writing op waits for it.  What run k's post-process reads or writes and run k + 1 could touch exists twice, by
-  // ticket: the detection outputs and the image scales (snapshot taken on the main stream when the run is queued).
-  struct AsyncSlot {
-    hipEvent_t ev = nullptr;             // post-process of this run done
-    bool open = false;                   // queued, not collected yet
-    bool joined = true;                  // the main stream has been made to wait for `ev`
-    int64_t seq = 0;
-    int n = 0, mode = 0;
-    bool coop_used = false, oor_armed = false;
-    bool cands_lost = false;             // an older run was served again after this one: its candidates are gone (no redo of its post-process)
-    RunRec rec;                          // what this run read (replay_run)
-    std::vector<std::pair<int, int>> pending;      // prefix-NMS ranges the host has not checked (rare path: no cooperative NMS)
-    float *oboxes = nullptr, *oscores = nullptr, *oclasses = nullptr, *ologits = nullptr, *scales = nullptr;
-    int32_t* ovalid = nullptr;
-  };
-  AsyncSlot as[2];
-  int as_next = 0;
-  int64_t as_seq = 0;
-  bool as_ready = false;
-  const float* d_scales_post = nullptr;  // what the post-process reads as image scales (null: d_scales)
-  hipStream_t aux_stream = nullptr;      // uda_collect_device packs on it
-  hipEvent_t gate_ev = nullptr;          // run_network: head-writing ops wait for this first (the previous run's post-process)
-
-  uint32_t prof_mask = 0;
-  ProfSlot prof[32];
-};
 static void set_f16_storage(uda_ctx* c);
 
-static void free_prefix_ws(uda_ctx::PrefixWs& w);
-
-static int fail(uda_ctx* c, const char* fmt, ...) {
+int fail(uda_ctx* c, const char* fmt, ...) {
   char buf[1024];
   va_list ap;
   va_start(ap, fmt);
@@ -260,18 +27,6 @@ static int fail(uda_ctx* c, const char* fmt, ...) {
   return 1;
 }
 
-#define HIPC(ctx, expr)                                                                   \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(ctx, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-template <typename T>
-static hipError_t dalloc(T** p, size_t n) {
-  return hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
-}
-
 static inline int same_pad_before(int in, int out, int k, int s) {
   int total = (out - 1) * s + k - in;
   if (total < 0) total = 0;
@@ -279,30 +34,6 @@ static inline int same_pad_before(int in, int out, int k, int s) {
 }
 
 // ------------------------------------------------------------------------------------ profiling helpers
-struct ProfScope {
-  uda_ctx* c;
-  int kind;
-  hipStream_t st;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  bool on;
-  int weight;
-  ProfScope(uda_ctx* c_, int kind_, hipStream_t st_ = nullptr, int weight_ = 1)
-      : c(c_), kind(kind_), st(st_ ? st_ : c_->stream), weight(weight_) {
-    on = (c->prof_mask >> kind) & 1u;
-    if (on) {
-      hipEventCreate(&e0);
-      hipEventCreate(&e1);
-      hipEventRecord(e0, st);
-    }
-  }
-  ~ProfScope() {
-    if (on) {
-      hipEventRecord(e1, st);
-      c->prof[kind].pending.push_back({e0, e1, weight});
-    }
-  }
-};
-
 static void prof_collect(uda_ctx* c, int kind) {
   ProfSlot& s = c->prof[kind];
   for (auto& pr : s.pending) {
@@ -388,19 +119,6 @@ extern "C" void uda_destroy(uda_ctx_t* c) {
   delete c;
 }
 
-static int box_cols_of(const uda_model_t& m, int post_mode) {
-  if (post_mode == UDA_POST_PER_CLASS) return 4;
-  int cols = 4;
-  if (m.has_uncert && m.loss_attenuation) cols += 4;
-  if (m.has_uncert && m.box_stacked) cols += 4;
-  return cols;
-}
-static int cls_cols_of(const uda_model_t& m, int post_mode) {
-  if (post_mode == UDA_POST_PER_CLASS) return 1;
-  // top-k path gathers ONE class-std value per (anchor, class) candidate (postprocess.py:117-121)
-  return 1 + ((m.has_uncert && m.cls_stacked) ? (m.max_nms_inputs > 0 ? 1 : m.num_classes) : 0);
-}
-
 static hipError_t alloc_nms_ws(uda_ctx::NmsWs& w, size_t problems, size_t K, size_t M) {
   if (w.ready) return hipSuccess;
   hipError_t e;
@@ -415,13 +133,13 @@ static hipError_t alloc_nms_ws(uda_ctx::NmsWs& w, size_t problems, size_t K, siz
 }
 
 // UDA_NMS_SOLO = candidates per problem up to which the single-launch NMS kernel is used directly (0 = never)
-static int solo_limit() {
+int solo_limit() {
   static const int solo = uda_env_int("UDA_NMS_SOLO", 8192);
   return solo;
 }
 
 // candidates passed on to the prefix NMS: at least UDA_NMS_PREFIX (default 2048, 0 = always the full set), at most twice that
-static int prefix_target() {
+int prefix_target() {
   static int L = -1;
   if (L < 0) {
     const char* e = getenv("UDA_NMS_PREFIX");
@@ -433,7 +151,7 @@ static int prefix_target() {
   return L;
 }
 
-static hipError_t alloc_prefix_ws(uda_ctx::PrefixWs& w, size_t problems, int Lcap, size_t M) {
+hipError_t alloc_prefix_ws(uda_ctx::PrefixWs& w, size_t problems, int Lcap, size_t M) {
   if (w.Lcap) return hipSuccess;
   hipError_t e;
   if ((e = dalloc(&w.sub_idx, problems * Lcap)) != hipSuccess) return e;
@@ -446,7 +164,7 @@ static hipError_t alloc_prefix_ws(uda_ctx::PrefixWs& w, size_t problems, int Lca
   return hipSuccess;
 }
 
-static void free_prefix_ws(uda_ctx::PrefixWs& w) {
+void free_prefix_ws(uda_ctx::PrefixWs& w) {
   void* p[] = {w.sub_idx, w.sub_scores, w.sub_boxes, w.excl, w.bad, w.ws.stale, w.ws.tent, w.ws.ub, w.ws.sel_score, w.ws.sel_box,
                w.ws.ev, w.ws.begin, w.ws.sel_idx, w.ws.nsel, w.ws.done, w.ws.bound, w.ws.win};
   for (void* q : p)
@@ -1610,17 +1328,7 @@ static int run_network(uda_ctx* c, int post_mode = 0, bool chunk_post = false, h
 // ------------------------------------------------------------------------------------ post-process
 static NmsArgs nms_args_at(uda_ctx::NmsWs& w, size_t p0, int problems, int K, int M, const float* boxes);
 
-// Returns true when the problems were solved on their score prefix (flags in pw->bad[p0 ..] say which ones have to be
-// redone on the full set, see finish_post); `pw` null = never.
-struct NmsCoop {           // scratch of the cooperative kernel; null members = never use it
-  unsigned long long* bar = nullptr;    // exchange slots (per problem nms_coop_slot_words(M) words)
-  int* err = nullptr;
-  bool* used = nullptr;
-  int64_t* not_launched = nullptr;      // counts the runs that wanted the single launch and fell through to the slower versions
-};
-
-static bool run_nms(const NmsArgs& na, const float* scores, int M, hipStream_t st, uda_ctx::PrefixWs* pw = nullptr, size_t p0 = 0,
-                    NmsCoop coop = NmsCoop()) {
+bool run_nms(const NmsArgs& na, const float* scores, int M, hipStream_t st, uda_ctx::PrefixWs* pw, size_t p0, NmsCoop coop) {
   // One launch for all epochs (one block per problem) when a problem is small - the top-k / per-class paths with a
   // few thousand candidates each; with the whole anchor set as candidates (184 k near-tied scores under random-init
   // weights) an epoch revisits 10-20 chunks one after the other inside the block and the grid version, which scans
@@ -1674,7 +1382,7 @@ static bool run_nms(const NmsArgs& na, const float* scores, int M, hipStream_t s
   return false;
 }
 
-static void nms_params(NmsArgs& a, float iou_thr, float score_thr, float soft_sigma) {
+void nms_params(NmsArgs& a, float iou_thr, float score_thr, float soft_sigma) {
   a.iou_thr = iou_thr;
   a.score_thr = score_thr;
   a.soft = soft_sigma > 0.0f;
@@ -2037,7 +1745,7 @@ static int join_async(uda_ctx* c) {
   return 0;
 }
 
-static int finish_post(uda_ctx* c) {
+int finish_post(uda_ctx* c) {
   if (int rc = join_async(c)) return rc;
   {
     // an ordinary reader (uda_get_detections, calibrators, ...) beside an uncollected pipelined run reads the NEWEST run: that
@@ -2566,746 +2274,28 @@ extern "C" int uda_detections_device(uda_ctx_t* c, int32_t rows, int32_t with_lo
   return 0;
 }
 
+int ensure_probs(uda_ctx* c, int rows) {
+  const size_t N = (size_t)c->model.max_images, M = c->model.max_output_size, C = c->model.num_classes;
+  if (!c->d_oprobs) {
+    HIPC(c, dalloc(&c->d_oprobs, N * M * C));
+    HIPC(c, dalloc(&c->d_oentropy, N * M));
+  }
+  launch_probs(c->d_ologits, c->d_oprobs, c->d_oentropy, rows, (int)C, c->stream);
+  return 0;
+}
+
 extern "C" int uda_get_class_probs(uda_ctx_t* c, float* probs, float* entropy) {
   if (!c || !probs || !entropy) return c ? fail(c, "get_class_probs: NULL argument") : 1;
   if (c->last_post_mode != UDA_POST_GLOBAL) return fail(c, "get_class_probs: logits exist only after the global post-process");
   HIPC(c, hipSetDevice(c->device));
   if (int rc = finish_post(c)) return rc;
   const size_t n = c->last_n, M = c->model.max_output_size, C = c->model.num_classes;
-  if (!c->d_oprobs) {
-    const size_t N = (size_t)c->model.max_images;
-    HIPC(c, dalloc(&c->d_oprobs, N * M * C));
-    HIPC(c, dalloc(&c->d_oentropy, N * M));
-  }
-  launch_probs(c->d_ologits, c->d_oprobs, c->d_oentropy, (int)(n * M), (int)C, c->stream);
+  if (int rc = ensure_probs(c, (int)(n * M))) return rc;
   HIPC(c, hipStreamSynchronize(c->stream));
   HIPC(c, hipGetLastError());
   HIPC(c, hipMemcpy(probs, c->d_oprobs, n * M * C * sizeof(float), hipMemcpyDeviceToHost));
   HIPC(c, hipMemcpy(entropy, c->d_oentropy, n * M * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
-}
-
-// ---- ground-truth assignment (reference utils_extra.py:44-64; validate_model.py:314-339, calibrate_model.py:133-147)
-// Width of a matched row: every column the global post-process produced, then what uda_get_class_probs adds.
-static int assigned_row_cols_of(const uda_model_t& m) {
-  return box_cols_of(m, UDA_POST_GLOBAL) + 1 + cls_cols_of(m, UDA_POST_GLOBAL) + (m.enable_softmax ? 2 * m.num_classes + 1 : 0);
-}
-// LDS of the two kernels: M boxes of 16 bytes, G row numbers of 4 bytes, each inside the 64 KiB a block may ask for
-static const int kAssignMaxM = 4096, kAssignMaxG = 16384;
-
-extern "C" int uda_assigned_row_cols(const uda_ctx_t* c, int32_t* cols) {
-  if (!c || !cols) return 1;
-  *cols = assigned_row_cols_of(c->model);
-  return 0;
-}
-
-extern "C" int uda_set_ground_truth(uda_ctx_t* c, const float* boxes, const float* classes, int32_t n, int32_t G) {
-  if (!c || !boxes || !classes) return c ? fail(c, "set_ground_truth: NULL argument") : 1;
-  const uda_model_t& m = c->model;
-  if (n < 1 || n > m.max_images) return fail(c, "set_ground_truth: %d images, the handle holds 1..%d", n, m.max_images);
-  if (G < 0 || G > kAssignMaxG) return fail(c, "set_ground_truth: %d ground-truth rows per image, at most %d", G, kAssignMaxG);
-  HIPC(c, hipSetDevice(c->device));
-  if (!c->gt_ev) HIPC(c, hipEventCreateWithFlags(&c->gt_ev, hipEventDisableTiming));
-  else HIPC(c, hipEventSynchronize(c->gt_ev));          // the previous upload has left the staging buffer
-  if (G > c->gt_cap || !c->d_gt_boxes) {
-    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffers)
-    void* old[] = {c->d_gt_boxes, c->d_gt_classes, c->d_asg_pack, c->d_asg_rows};
-    for (void* p : old)
-      if (p) hipFree(p);
-    if (c->h_gt) hipHostFree(c->h_gt);
-    c->d_gt_boxes = c->d_gt_classes = c->d_asg_rows = c->h_gt = nullptr; c->d_asg_pack = nullptr;
-    c->gt_cap = 0; c->asg_n = 0; c->asg_rows = -1;
-    const size_t cap = (size_t)std::max(G, 1), rows = (size_t)m.max_images * cap;
-    HIPC(c, dalloc(&c->d_gt_boxes, rows * 4));
-    HIPC(c, dalloc(&c->d_gt_classes, rows));
-    HIPC(c, dalloc(&c->d_asg_pack, rows * 12 + ((size_t)m.max_images + 1) * 4));
-    HIPC(c, dalloc(&c->d_asg_rows, rows * (size_t)assigned_row_cols_of(m)));
-    HIPC(c, hipHostMalloc((void**)&c->h_gt, rows * 5 * sizeof(float)));
-    c->gt_cap = (int)cap;
-  }
-  const size_t rows = (size_t)n * G;
-  if (rows) {
-    memcpy(c->h_gt, boxes, rows * 4 * sizeof(float));
-    memcpy(c->h_gt + rows * 4, classes, rows * sizeof(float));
-    HIPC(c, hipMemcpyAsync(c->d_gt_boxes, c->h_gt, rows * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(c->d_gt_classes, c->h_gt + rows * 4, rows * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPC(c, hipEventRecord(c->gt_ev, c->stream));
-  c->gt_n = n; c->gt_G = G;
-  return 0;
-}
-
-extern "C" int uda_assign_ground_truth(uda_ctx_t* c, int32_t method, int32_t keep) {
-  if (!c) return 1;
-  const uda_model_t& m = c->model;
-  if (method < ASSIGN_IOU || method > ASSIGN_RANK) return fail(c, "assign_ground_truth: unknown method %d", method);
-  if (keep != ASSIGN_KEEP_VALIDATE && keep != ASSIGN_KEEP_CALIBRATE) return fail(c, "assign_ground_truth: unknown keep rule %d", keep);
-  if (c->gt_n < 1) return fail(c, "assign_ground_truth: no ground truth is set (uda_set_ground_truth)");
-  if (c->as[0].open || c->as[1].open)
-    return fail(c, "assign_ground_truth: a pipelined run (uda_run_async) is in flight - uda_collect it first");
-  if (c->last_n < 1) return fail(c, "assign_ground_truth: no global post-process has run yet");
-  if (c->last_post_mode != UDA_POST_GLOBAL)
-    return fail(c, "assign_ground_truth: the last post-process ran per class; the assignment reads the global post-process");
-  // after a consistency run the handle holds 4n images, the n originals first: the ground truth belongs to those
-  const bool cons = c->noise_from >= 0 && c->cons_n > 0 && c->last_n == 4 * c->cons_n;
-  if (c->gt_n != (cons ? c->cons_n : c->last_n))
-    return fail(c, "assign_ground_truth: ground truth of %d images, the last post-process holds %d", c->gt_n, cons ? c->cons_n : c->last_n);
-  if (m.max_output_size > kAssignMaxM) return fail(c, "assign_ground_truth: max_output_size %d above %d", m.max_output_size, kAssignMaxM);
-  HIPC(c, hipSetDevice(c->device));
-  if (int rc = finish_post(c)) return rc;      // range replay / prefix redo / NMS fallback: the assignment reads final detections
-  const int n = c->gt_n, M = m.max_output_size, G = c->gt_G, C = m.enable_softmax ? m.num_classes : 0;
-  if (C) {
-    if (!c->d_oprobs) {
-      const size_t N = (size_t)m.max_images;
-      HIPC(c, dalloc(&c->d_oprobs, N * M * C));
-      HIPC(c, dalloc(&c->d_oentropy, N * M));
-    }
-    launch_probs(c->d_ologits, c->d_oprobs, c->d_oentropy, n * M, C, c->stream);
-  }
-  const size_t ng = (size_t)n * G;
-  c->d_asg_iou = (double*)c->d_asg_pack;
-  c->d_asg_index = (int32_t*)(c->d_asg_pack + ng * sizeof(double));
-  c->d_asg_count = c->d_asg_index + ng;
-  c->d_asg_err = c->d_asg_count + n;
-  HIPC(c, hipMemsetAsync(c->d_asg_err, 0, sizeof(int32_t), c->stream));
-  AssignArgs a{};
-  a.det_boxes = c->d_oboxes; a.det_stride = box_cols_of(m, UDA_POST_GLOBAL);
-  a.gt_boxes = c->d_gt_boxes; a.gt_classes = c->d_gt_classes;
-  a.det_index = c->d_asg_index; a.iou = c->d_asg_iou; a.count = c->d_asg_count; a.err = c->d_asg_err;
-  a.n = n; a.M = M; a.G = G; a.method = method; a.keep = keep;
-  launch_assign_gt(a, c->stream);
-  AssignRowsArgs r{};
-  r.det_index = c->d_asg_index; r.count = c->d_asg_count;
-  r.boxes = c->d_oboxes; r.scores = c->d_oscores; r.classes = c->d_oclasses;
-  r.logits = c->d_ologits; r.probs = c->d_oprobs; r.entropy = c->d_oentropy;
-  r.rows = c->d_asg_rows;
-  r.n = n; r.M = M; r.G = G; r.bc = a.det_stride; r.cc = cls_cols_of(m, UDA_POST_GLOBAL); r.C = C; r.cols = assigned_row_cols_of(m);
-  launch_gather_assigned(r, c->stream);
-  HIPC(c, hipGetLastError());
-  c->asg_n = n; c->asg_G = G; c->asg_rows = -1;
-  return 0;
-}
-
-// The first reader of an assignment waits for it and brings the packed results over in one copy.
-static int fetch_assignment(uda_ctx* c) {
-  if (c->asg_rows >= 0) return 0;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  const size_t ng = (size_t)c->asg_n * c->asg_G;
-  c->h_asg.resize(ng * 12 + ((size_t)c->asg_n + 1) * 4);
-  HIPC(c, hipMemcpy(c->h_asg.data(), c->d_asg_pack, c->h_asg.size(), hipMemcpyDeviceToHost));
-  const int32_t* cnt = (const int32_t*)(c->h_asg.data() + ng * 12);
-  if (cnt[c->asg_n]) return fail(c, "assign_ground_truth: the rank method met a kept ground-truth row beyond the %d detections", c->model.max_output_size);
-  int64_t rows = 0;
-  for (int i = 0; i < c->asg_n; ++i) rows += cnt[i];
-  c->asg_rows = rows;
-  return 0;
-}
-
-extern "C" int uda_get_assignment(uda_ctx_t* c, int32_t* det_index, double* iou, int32_t* count) {
-  if (!c) return 1;
-  if (c->asg_n < 1) return fail(c, "get_assignment: no assignment (uda_assign_ground_truth)");
-  if (int rc = fetch_assignment(c)) return rc;
-  const size_t ng = (size_t)c->asg_n * c->asg_G;
-  const char* h = c->h_asg.data();
-  if (iou && ng) memcpy(iou, h, ng * sizeof(double));
-  if (det_index && ng) memcpy(det_index, h + ng * 8, ng * sizeof(int32_t));
-  if (count) memcpy(count, h + ng * 12, (size_t)c->asg_n * sizeof(int32_t));
-  return 0;
-}
-
-extern "C" int uda_get_assigned_rows(uda_ctx_t* c, float* rows, int64_t n_floats) {
-  if (!c) return 1;
-  if (c->asg_n < 1) return fail(c, "get_assigned_rows: no assignment (uda_assign_ground_truth)");
-  if (int rc = fetch_assignment(c)) return rc;
-  const int64_t want = c->asg_rows * assigned_row_cols_of(c->model);
-  if (n_floats != want) return fail(c, "get_assigned_rows: the %lld matched rows take %lld floats, not %lld", (long long)c->asg_rows, (long long)want, (long long)n_floats);
-  if (want && !rows) return fail(c, "get_assigned_rows: NULL output");
-  HIPC(c, hipSetDevice(c->device));
-  if (want) HIPC(c, hipMemcpy(rows, c->d_asg_rows, (size_t)want * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// gt_box_assigner for callers that hold detections of their own: host arrays in, the same kernel, host arrays out
-extern "C" int uda_assign_gt_np(int32_t device, const float* det_boxes, const float* gt_boxes, const float* gt_classes, int32_t n,
-                                int32_t M, int32_t G, int32_t method, int32_t keep, int32_t* det_index, double* iou, int32_t* count) {
-  if (n < 0 || M < 0 || G < 0 || M > kAssignMaxM || G > kAssignMaxG || method < ASSIGN_IOU || method > ASSIGN_RANK ||
-      (keep != ASSIGN_KEEP_VALIDATE && keep != ASSIGN_KEEP_CALIBRATE) || !count ||
-      ((size_t)n * G && (!gt_boxes || !gt_classes || !det_index || !iou)) || ((size_t)n * M && !det_boxes))
-    return fail(nullptr, "uda_assign_gt_np: bad argument");
-  if (n == 0) return 0;
-  float *d_det = nullptr, *d_gb = nullptr, *d_gc = nullptr;
-  int32_t *d_idx = nullptr, *d_cnt = nullptr;
-  double* d_iou = nullptr;
-  const size_t nm = (size_t)n * M, ng = (size_t)n * G;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = dalloc(&d_det, nm * 4);
-  if (e == hipSuccess) e = dalloc(&d_gb, ng * 4);
-  if (e == hipSuccess) e = dalloc(&d_gc, ng);
-  if (e == hipSuccess) e = dalloc(&d_idx, ng);
-  if (e == hipSuccess) e = dalloc(&d_iou, ng);
-  if (e == hipSuccess) e = dalloc(&d_cnt, (size_t)n + 1);
-  if (e == hipSuccess && nm) e = hipMemcpy(d_det, det_boxes, nm * 4 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && ng) e = hipMemcpy(d_gb, gt_boxes, ng * 4 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && ng) e = hipMemcpy(d_gc, gt_classes, ng * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_cnt, 0, ((size_t)n + 1) * sizeof(int32_t));
-  int32_t err = 0;
-  if (e == hipSuccess) {
-    AssignArgs a{};
-    a.det_boxes = d_det; a.det_stride = 4; a.gt_boxes = d_gb; a.gt_classes = d_gc;
-    a.det_index = d_idx; a.iou = d_iou; a.count = d_cnt; a.err = d_cnt + n;
-    a.n = n; a.M = M; a.G = G; a.method = method; a.keep = keep;
-    launch_assign_gt(a, nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess) e = hipMemcpy(count, d_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(&err, d_cnt + n, sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && ng) e = hipMemcpy(det_index, d_idx, ng * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && ng) e = hipMemcpy(iou, d_iou, ng * sizeof(double), hipMemcpyDeviceToHost);
-  void* ptrs[] = {d_det, d_gb, d_gc, d_idx, d_iou, d_cnt};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  if (e != hipSuccess) return fail(nullptr, "uda_assign_gt_np: %s", hipGetErrorString(e));
-  if (err) return fail(nullptr, "uda_assign_gt_np: the rank method met a kept ground-truth row beyond the %d detections", M);
-  return 0;
-}
-
-// ---- active-learning image scores (reference active_learning_loop.py:528-733 on the lines of infer_model.py:836-960)
-static const int kScoreMaxM = 4096, kScoreMaxC = 8192;      // rows a block walks; class counters in LDS (4 bytes each)
-
-// what a descriptor reads: bit (1 << uda_score_source); 0 with *why set when it is malformed
-static unsigned score_desc_sources(const uda_score_desc_t* d, const char** why) {
-  *why = nullptr;
-  if (!d) { *why = "NULL descriptor"; return 0; }
-  if (d->n_comp < 1 || d->n_comp > UDA_SCORE_MAX_COMP) { *why = "n_comp outside 1..3"; return 0; }
-  unsigned mask = 0;
-  for (int k = 0; k < d->n_comp; ++k) {
-    if (d->n_terms[k] < 1 || d->n_terms[k] > 2) { *why = "a component has 1 or 2 terms"; return 0; }
-    for (int t = 0; t < d->n_terms[k]; ++t) {
-      const int src = d->term[k][t].source, tr = d->term[k][t].transform;
-      const bool scalar = src == UDA_SCORE_ENTROPY || src == UDA_SCORE_DET_SCORE;
-      const bool box = src == UDA_SCORE_ALBOX || src == UDA_SCORE_MCBOX;
-      if (!scalar && !box && src != UDA_SCORE_MCCLASS) { *why = "unknown source"; return 0; }
-      if (scalar ? tr != UDA_SCORE_SCALAR : !(tr == UDA_SCORE_MEAN || (box && tr == UDA_SCORE_REL_MEAN))) {
-        *why = "transform does not fit the source (SCALAR: entropy / det_score; MEAN: albox / mcbox / mcclass; REL_MEAN: albox / mcbox)";
-        return 0;
-      }
-      mask |= 1u << src;
-    }
-  }
-  return mask;
-}
-
-static size_t score_pack_bytes(size_t n, size_t nc, size_t C) { return n * nc * sizeof(double) + (n + n * C + 1) * sizeof(int32_t); }
-
-extern "C" int uda_score_images(uda_ctx_t* c, const uda_score_desc_t* desc, float min_score) {
-  if (!c) return 1;
-  const uda_model_t& m = c->model;
-  const char* why = nullptr;
-  const unsigned need = score_desc_sources(desc, &why);
-  if (why) return fail(c, "score_images: %s", why);
-  if (c->as[0].open || c->as[1].open)
-    return fail(c, "score_images: a pipelined run (uda_run_async) is in flight - uda_collect it first");
-  if (c->last_n < 1) return fail(c, "score_images: no global post-process has run yet");
-  if (c->last_post_mode != UDA_POST_GLOBAL)
-    return fail(c, "score_images: the last post-process ran per class; the scores read the global post-process");
-  if ((need & (1u << UDA_SCORE_ENTROPY)) && !m.enable_softmax)
-    return fail(c, "score_images: the model emits no entropy (enable_softmax is off)");
-  if ((need & (1u << UDA_SCORE_ALBOX)) && !(m.has_uncert && m.loss_attenuation))
-    return fail(c, "score_images: the model emits no aleatoric box uncertainty (no loss attenuation)");
-  if ((need & (1u << UDA_SCORE_MCBOX)) && !(m.has_uncert && m.box_stacked))
-    return fail(c, "score_images: the model emits no epistemic box uncertainty (no MC dropout on the box head)");
-  if ((need & (1u << UDA_SCORE_MCCLASS)) && !(m.has_uncert && m.cls_stacked))
-    return fail(c, "score_images: the model emits no epistemic class uncertainty (no MC dropout on the class head)");
-  if (m.max_output_size > kScoreMaxM) return fail(c, "score_images: max_output_size %d above %d", m.max_output_size, kScoreMaxM);
-  if (m.num_classes < 1 || m.num_classes > kScoreMaxC) return fail(c, "score_images: num_classes %d outside 1..%d", m.num_classes, kScoreMaxC);
-  HIPC(c, hipSetDevice(c->device));
-  if (int rc = finish_post(c)) return rc;      // range replay / prefix redo / NMS fallback: the scores read final detections
-  const int n = c->last_n, M = m.max_output_size, C = m.num_classes, nc = desc->n_comp;
-  if (!c->d_score_pack) HIPC(c, dalloc(&c->d_score_pack, score_pack_bytes((size_t)m.max_images, UDA_SCORE_MAX_COMP, (size_t)C)));
-  {
-    ProfScope ps(c, 19);
-    if (need & (1u << UDA_SCORE_ENTROPY)) {
-      if (!c->d_oprobs) {
-        const size_t N = (size_t)m.max_images;
-        HIPC(c, dalloc(&c->d_oprobs, N * M * C));
-        HIPC(c, dalloc(&c->d_oentropy, N * M));
-      }
-      launch_probs(c->d_ologits, c->d_oprobs, c->d_oentropy, n * M, C, c->stream);
-    }
-    const int bc = box_cols_of(m, UDA_POST_GLOBAL), cc = cls_cols_of(m, UDA_POST_GLOBAL);
-    ScoreArgs<float> a{};
-    a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses; a.entropy = c->d_oentropy;
-    a.albox = c->d_oboxes + 4;                                               // box | aleatoric std | MC std, as each exists
-    a.mcbox = c->d_oboxes + ((m.has_uncert && m.loss_attenuation) ? 8 : 4);
-    a.mcclass = c->d_oclasses + 1;
-    a.box_stride = a.al_stride = a.mc_stride = bc; a.cls_stride = a.mcc_stride = cc; a.mcc_w = cc - 1;
-    a.comp = (double*)c->d_score_pack;
-    a.count = (int32_t*)(c->d_score_pack + (size_t)n * nc * sizeof(double));
-    a.class_counts = a.count + n;
-    a.err = a.class_counts + (size_t)n * C;
-    a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
-    HIPC(c, hipMemsetAsync(a.err, 0, sizeof(int32_t), c->stream));
-    launch_score_images(a, c->stream);
-  }
-  HIPC(c, hipGetLastError());
-  c->score_n = n; c->score_nc = nc; c->score_fetched = false;
-  return 0;
-}
-
-extern "C" int uda_image_scores_shape(const uda_ctx_t* c, int32_t* n, int32_t* n_comp) {
-  if (!c || !n || !n_comp) return 1;
-  *n = c->score_n; *n_comp = c->score_nc;
-  return 0;
-}
-
-extern "C" int uda_get_image_scores(uda_ctx_t* c, double* components, int32_t* count, int32_t* class_counts) {
-  if (!c) return 1;
-  if (c->score_n < 1) return fail(c, "get_image_scores: no scores (uda_score_images)");
-  const size_t n = c->score_n, nc = c->score_nc, C = c->model.num_classes;
-  if (!c->score_fetched) {       // the first reader of a scoring waits for it and brings the pack over in one copy
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    c->h_score.resize(score_pack_bytes(n, nc, C));
-    HIPC(c, hipMemcpy(c->h_score.data(), c->d_score_pack, c->h_score.size(), hipMemcpyDeviceToHost));
-    c->score_fetched = true;
-  }
-  const char* h = c->h_score.data();
-  const int32_t* cnt = (const int32_t*)(h + n * nc * sizeof(double));
-  if (cnt[n + n * C]) return fail(c, "score_images: a kept detection has a class id outside 1..%d", (int)C);
-  if (components) memcpy(components, h, n * nc * sizeof(double));
-  if (count) memcpy(count, cnt, n * sizeof(int32_t));
-  if (class_counts) memcpy(class_counts, cnt + n, n * C * sizeof(int32_t));
-  return 0;
-}
-
-// score_image for callers that hold detections of their own (calibrated columns, a gathered multi-GPU batch): host arrays in,
-// the same kernel, host arrays out; its own allocations
-template <typename T>
-static int score_images_np(const char* who, int32_t device, const uda_score_desc_t* desc, T min_score, const T* boxes, const T* scores,
-                           const T* classes, const T* entropy, const T* albox, const T* mcbox, const T* mcclass, int32_t n, int32_t M,
-                           int32_t C, int32_t mcw, double* components, int32_t* count, int32_t* class_counts) {
-  const char* why = nullptr;
-  const unsigned need = score_desc_sources(desc, &why);
-  if (why) return fail(nullptr, "%s: %s", who, why);
-  if (n < 0 || M < 0 || M > kScoreMaxM || C < 1 || C > kScoreMaxC || ((size_t)n * M && (!boxes || !scores || !classes)))
-    return fail(nullptr, "%s: bad argument", who);
-  const T* srcs[] = {entropy, scores, albox, mcbox, mcclass};
-  static const char* names[] = {"entropy", "scores", "albox", "mcbox", "mcclass"};
-  for (int s = 0; s < 5; ++s)
-    if ((need & (1u << s)) && (size_t)n * M && !srcs[s]) return fail(nullptr, "%s: the descriptor reads %s, which is not given", who, names[s]);
-  if ((need & (1u << UDA_SCORE_MCCLASS)) && mcw < 1) return fail(nullptr, "%s: mcclass_cols must be at least 1", who);
-  if (n == 0) return 0;
-  const size_t nm = (size_t)n * M, nc = desc->n_comp;
-  const size_t widths[] = {4, 1, 1, 1, 4, 4, (size_t)(mcw > 0 ? mcw : 0)};
-  const T* host[] = {boxes, scores, classes, entropy, albox, mcbox, mcclass};
-  T* dev[7] = {};
-  char* d_pack = nullptr;
-  hipError_t e = hipSetDevice(device);
-  for (int k = 0; k < 7 && e == hipSuccess; ++k) {
-    if (!host[k] || !(nm * widths[k])) continue;
-    e = dalloc(&dev[k], nm * widths[k]);
-    if (e == hipSuccess) e = hipMemcpy(dev[k], host[k], nm * widths[k] * sizeof(T), hipMemcpyHostToDevice);
-  }
-  const size_t bytes = score_pack_bytes((size_t)n, nc, (size_t)C);
-  if (e == hipSuccess) e = dalloc(&d_pack, bytes);
-  if (e == hipSuccess) e = hipMemset(d_pack, 0, bytes);
-  std::vector<char> h(bytes);
-  if (e == hipSuccess) {
-    ScoreArgs<T> a{};
-    a.boxes = dev[0]; a.scores = dev[1]; a.classes = dev[2]; a.entropy = dev[3]; a.albox = dev[4]; a.mcbox = dev[5]; a.mcclass = dev[6];
-    a.box_stride = a.al_stride = a.mc_stride = 4; a.cls_stride = 1; a.mcc_stride = a.mcc_w = mcw > 0 ? mcw : 0;
-    a.comp = (double*)d_pack;
-    a.count = (int32_t*)(d_pack + (size_t)n * nc * sizeof(double));
-    a.class_counts = a.count + n;
-    a.err = a.class_counts + (size_t)n * C;
-    a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
-    launch_score_images(a, nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess) e = hipMemcpy(h.data(), d_pack, bytes, hipMemcpyDeviceToHost);
-  for (T* p : dev)
-    if (p) hipFree(p);
-  if (d_pack) hipFree(d_pack);
-  if (e != hipSuccess) return fail(nullptr, "%s: %s", who, hipGetErrorString(e));
-  const int32_t* cnt = (const int32_t*)(h.data() + (size_t)n * nc * sizeof(double));
-  if (cnt[(size_t)n + (size_t)n * C]) return fail(nullptr, "%s: a kept detection has a class id outside 1..%d", who, C);
-  if (components) memcpy(components, h.data(), (size_t)n * nc * sizeof(double));
-  if (count) memcpy(count, cnt, (size_t)n * sizeof(int32_t));
-  if (class_counts) memcpy(class_counts, cnt + n, (size_t)n * C * sizeof(int32_t));
-  return 0;
-}
-
-extern "C" int uda_score_images_np(int32_t device, const uda_score_desc_t* desc, double min_score, const double* boxes,
-                                   const double* scores, const double* classes, const double* entropy, const double* albox,
-                                   const double* mcbox, const double* mcclass, int32_t n, int32_t M, int32_t num_classes,
-                                   int32_t mcclass_cols, double* components, int32_t* count, int32_t* class_counts) {
-  return score_images_np<double>("uda_score_images_np", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass, n,
-                                 M, num_classes, mcclass_cols, components, count, class_counts);
-}
-
-extern "C" int uda_score_images_np_f32(int32_t device, const uda_score_desc_t* desc, float min_score, const float* boxes,
-                                       const float* scores, const float* classes, const float* entropy, const float* albox,
-                                       const float* mcbox, const float* mcclass, int32_t n, int32_t M, int32_t num_classes,
-                                       int32_t mcclass_cols, double* components, int32_t* count, int32_t* class_counts) {
-  return score_images_np<float>("uda_score_images_np_f32", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass,
-                                n, M, num_classes, mcclass_cols, components, count, class_counts);
-}
-
-// ---- COCO matching (reference custom_cocoeval.py:265-349 on the containers of coco_metric.py:219-283)
-static const int kEvalMaxC = 8192;
-static size_t eval_pack_bytes(size_t n, size_t M, size_t C) { return n * M * sizeof(uda_eval_record_t) + (n * C * 4 + n) * sizeof(int32_t); }
-static_assert(sizeof(uda_eval_record_t) == 44, "the record is 11 words");
-
-static const char* eval_thrs_bad(const double* thrs, int32_t T) {
-  if (T < 1 || T > COCO_MAX_T) return "T outside 1..32 thresholds";
-  if (!thrs) return "NULL thresholds";
-  return nullptr;
-}
-
-extern "C" int uda_set_eval_ground_truth(uda_ctx_t* c, const float* gt, int32_t n, int32_t G) {
-  if (!c || !gt) return c ? fail(c, "set_eval_ground_truth: NULL argument") : 1;
-  const uda_model_t& m = c->model;
-  if (n < 1 || n > m.max_images) return fail(c, "set_eval_ground_truth: %d images, the handle holds 1..%d", n, m.max_images);
-  if (G < 0 || G > COCO_MAX_G) return fail(c, "set_eval_ground_truth: %d ground-truth rows per image, at most %d", G, (int)COCO_MAX_G);
-  HIPC(c, hipSetDevice(c->device));
-  if (!c->egt_ev) HIPC(c, hipEventCreateWithFlags(&c->egt_ev, hipEventDisableTiming));
-  else HIPC(c, hipEventSynchronize(c->egt_ev));         // the previous upload has left the staging buffer
-  if (G > c->egt_cap || !c->d_egt) {
-    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffer)
-    if (c->d_egt) hipFree(c->d_egt);
-    if (c->h_egt) hipHostFree(c->h_egt);
-    c->d_egt = c->h_egt = nullptr; c->egt_cap = 0; c->egt_n = 0;
-    const size_t cap = (size_t)std::max(G, 1), rows = (size_t)m.max_images * cap;
-    HIPC(c, dalloc(&c->d_egt, rows * 7));
-    HIPC(c, hipHostMalloc((void**)&c->h_egt, rows * 7 * sizeof(float)));
-    c->egt_cap = (int)cap;
-  }
-  const size_t floats = (size_t)n * G * 7;
-  if (floats) {
-    memcpy(c->h_egt, gt, floats * sizeof(float));
-    HIPC(c, hipMemcpyAsync(c->d_egt, c->h_egt, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPC(c, hipEventRecord(c->egt_ev, c->stream));
-  c->egt_n = n; c->egt_G = G;
-  return 0;
-}
-
-extern "C" int uda_eval_match(uda_ctx_t* c, const double* iou_thrs, int32_t T) {
-  if (!c) return 1;
-  const uda_model_t& m = c->model;
-  if (const char* why = eval_thrs_bad(iou_thrs, T)) return fail(c, "eval_match: %s", why);
-  if (c->egt_n < 1) return fail(c, "eval_match: no ground truth is set (uda_set_eval_ground_truth)");
-  if (c->as[0].open || c->as[1].open)
-    return fail(c, "eval_match: a pipelined run (uda_run_async) is in flight - uda_collect it first");
-  if (c->last_n < 1) return fail(c, "eval_match: no post-process has run yet");
-  if (c->egt_n != c->last_n)
-    return fail(c, "eval_match: ground truth of %d images, the last post-process holds %d", c->egt_n, c->last_n);
-  if (m.max_output_size > COCO_MAX_M) return fail(c, "eval_match: max_output_size %d above %d", m.max_output_size, (int)COCO_MAX_M);
-  if (m.num_classes < 1 || m.num_classes > kEvalMaxC) return fail(c, "eval_match: num_classes %d outside 1..%d", m.num_classes, kEvalMaxC);
-  HIPC(c, hipSetDevice(c->device));
-  if (int rc = finish_post(c)) return rc;      // range replay / prefix redo / NMS fallback: the match reads final detections
-  const int n = c->last_n, M = m.max_output_size, C = m.num_classes;
-  if (!c->d_eval_pack) HIPC(c, dalloc(&c->d_eval_pack, eval_pack_bytes((size_t)m.max_images, (size_t)M, (size_t)C)));
-  {
-    ProfScope ps(c, 20);
-    CocoMatchArgs a{};
-    a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses;
-    a.box_stride = box_cols_of(m, c->last_post_mode); a.cls_stride = cls_cols_of(m, c->last_post_mode);
-    a.gt = c->d_egt;
-    a.rec = (uda_eval_record_t*)c->d_eval_pack;
-    a.npig = (int32_t*)(c->d_eval_pack + (size_t)n * M * sizeof(uda_eval_record_t));
-    a.used = a.npig + (size_t)n * C * 4;
-    a.n = n; a.M = M; a.G = c->egt_G; a.C = C; a.T = T; a.legacy = 0;
-    for (int t = 0; t < T; ++t) a.thr[t] = iou_thrs[t];
-    launch_coco_match(a, c->stream);
-  }
-  HIPC(c, hipGetLastError());
-  c->eval_n = n; c->eval_fetched = false;
-  return 0;
-}
-
-extern "C" int uda_get_eval_records(uda_ctx_t* c, void* records, int32_t* npig, int32_t* used) {
-  if (!c) return 1;
-  if (c->eval_n < 1) return fail(c, "get_eval_records: no match (uda_eval_match)");
-  const size_t n = c->eval_n, M = c->model.max_output_size, C = c->model.num_classes;
-  if (!c->eval_fetched) {        // the first reader of a match waits for it and brings the pack over in one copy
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    c->h_eval.resize(eval_pack_bytes(n, M, C));
-    HIPC(c, hipMemcpy(c->h_eval.data(), c->d_eval_pack, c->h_eval.size(), hipMemcpyDeviceToHost));
-    c->eval_fetched = true;
-  }
-  const char* h = c->h_eval.data();
-  const size_t rec_bytes = n * M * sizeof(uda_eval_record_t);
-  if (records) memcpy(records, h, rec_bytes);
-  if (npig) memcpy(npig, h + rec_bytes, n * C * 4 * sizeof(int32_t));
-  if (used) memcpy(used, h + rec_bytes + n * C * 4 * sizeof(int32_t), n * sizeof(int32_t));
-  return 0;
-}
-
-// evaluateImg for callers that hold legacy rows of their own (the nms_np route, gathered detections): host arrays in, the same
-// kernel in its legacy-row layout, host arrays out; its own allocations
-extern "C" int uda_eval_match_np(int32_t device, const float* det_rows, const float* gt, int32_t n, int32_t M, int32_t G,
-                                 int32_t num_classes, const double* iou_thrs, int32_t T, void* records, int32_t* npig, int32_t* used) {
-  if (const char* why = eval_thrs_bad(iou_thrs, T)) return fail(nullptr, "uda_eval_match_np: %s", why);
-  if (G > COCO_MAX_G) return fail(nullptr, "uda_eval_match_np: %d ground-truth rows per image, at most %d", G, (int)COCO_MAX_G);
-  if (M > COCO_MAX_M) return fail(nullptr, "uda_eval_match_np: %d detection rows per image, at most %d", M, (int)COCO_MAX_M);
-  if (n < 0 || M < 0 || G < 0 || num_classes < 1 || num_classes > kEvalMaxC || ((size_t)n * M && !det_rows) || ((size_t)n * G && !gt))
-    return fail(nullptr, "uda_eval_match_np: bad argument");
-  if (n == 0) return 0;
-  const size_t nm = (size_t)n * M, ng = (size_t)n * G, C = (size_t)num_classes;
-  const size_t bytes = eval_pack_bytes((size_t)n, (size_t)M, C);
-  float *d_det = nullptr, *d_gt = nullptr;
-  char* d_pack = nullptr;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = dalloc(&d_det, nm * 7);
-  if (e == hipSuccess) e = dalloc(&d_gt, ng * 7);
-  if (e == hipSuccess) e = dalloc(&d_pack, bytes);
-  if (e == hipSuccess && nm) e = hipMemcpy(d_det, det_rows, nm * 7 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && ng) e = hipMemcpy(d_gt, gt, ng * 7 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_pack, 0, bytes);
-  std::vector<char> h(bytes);
-  if (e == hipSuccess) {
-    CocoMatchArgs a{};
-    a.rows = d_det; a.gt = d_gt;
-    a.rec = (uda_eval_record_t*)d_pack;
-    a.npig = (int32_t*)(d_pack + nm * sizeof(uda_eval_record_t));
-    a.used = a.npig + (size_t)n * C * 4;
-    a.n = n; a.M = M; a.G = G; a.C = num_classes; a.T = T; a.legacy = 1;
-    for (int t = 0; t < T; ++t) a.thr[t] = iou_thrs[t];
-    launch_coco_match(a, nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess) e = hipMemcpy(h.data(), d_pack, bytes, hipMemcpyDeviceToHost);
-  void* ptrs[] = {d_det, d_gt, d_pack};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  if (e != hipSuccess) return fail(nullptr, "uda_eval_match_np: %s", hipGetErrorString(e));
-  const size_t rec_bytes = nm * sizeof(uda_eval_record_t);
-  if (records) memcpy(records, h.data(), rec_bytes);
-  if (npig) memcpy(npig, h.data() + rec_bytes, (size_t)n * C * 4 * sizeof(int32_t));
-  if (used) memcpy(used, h.data() + rec_bytes + (size_t)n * C * 4 * sizeof(int32_t), (size_t)n * sizeof(int32_t));
-  return 0;
-}
-
-// the objective of the thresholding search for P candidates: host arrays in, chunks of candidates through the device (scratch of
-// at most kThrScratchBytes, or one candidate's), host arrays out; its own allocations
-static const size_t kThrScratchBytes = (size_t)64 << 20;
-extern "C" int uda_thr_objective_np(int32_t device, const double* uncerts, const double* ious, const uint8_t* tp_class,
-                                    const int32_t* group, int32_t N, int32_t U, int32_t G, const double* iou_thrs, int32_t K,
-                                    const double* params, int32_t P, int32_t fix_cd, double budget, double* thr, double* rate,
-                                    double* auc) {
-  const char* who = "uda_thr_objective_np";
-  if (N < 2 || N > THR_MAX_N) return fail(nullptr, "%s: %d rows, 2..%d are taken", who, N, (int)THR_MAX_N);
-  if (U < 1 || U > THR_MAX_U) return fail(nullptr, "%s: %d uncertainties, 1..%d are taken", who, U, (int)THR_MAX_U);
-  if (K < 1 || K > THR_MAX_K) return fail(nullptr, "%s: %d IoU thresholds, 1..%d are taken", who, K, (int)THR_MAX_K);
-  if (P < 1 || P > THR_MAX_P) return fail(nullptr, "%s: %d candidates, 1..%d are taken", who, P, (int)THR_MAX_P);
-  if (G < 0 || G > THR_MAX_G) return fail(nullptr, "%s: %d groups, 0..%d are taken", who, G, (int)THR_MAX_G);
-  if (!uncerts || !ious || !tp_class || !iou_thrs || !params) return fail(nullptr, "%s: NULL input", who);
-  if ((G > 0) != (group != nullptr)) return fail(nullptr, "%s: group ids and G > 0 go together", who);
-  if (!(budget > 0.0 && budget < 1.0)) return fail(nullptr, "%s: budget %g is not strictly between 0 and 1", who, budget);
-  for (int i = 0; group && i < N; ++i)
-    if (group[i] < 0 || group[i] >= G) return fail(nullptr, "%s: group id %d of row %d outside 0..%d", who, group[i], i, G - 1);
-  int Npad = THR_TILE;
-  while (Npad < N) Npad <<= 1;
-  const size_t n = (size_t)N, stride = (size_t)U * (size_t)(G > 0 ? G : 1);
-  const size_t per = 12 * (size_t)Npad + 8 * n * K + 24 * (size_t)K + 8 * stride;
-  size_t fit = kThrScratchBytes / per;
-  const int Pc = (int)std::min<size_t>(std::max<size_t>(fit, 1), std::min<size_t>((size_t)P, THR_MAX_CHUNK));
-  double *d_unc = nullptr, *d_iou = nullptr, *d_par = nullptr, *d_out = nullptr;
-  uint8_t* d_tp = nullptr;
-  int32_t *d_group = nullptr, *d_rows = nullptr, *d_runs = nullptr;
-  uint32_t* d_mask = nullptr;
-  uint64_t* d_keys = nullptr;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = dalloc(&d_unc, n * U);
-  if (e == hipSuccess) e = dalloc(&d_iou, n);
-  if (e == hipSuccess) e = dalloc(&d_tp, n);
-  if (e == hipSuccess && group) e = dalloc(&d_group, n);
-  if (e == hipSuccess) e = dalloc(&d_mask, n);
-  if (e == hipSuccess) e = dalloc(&d_par, (size_t)Pc * stride);
-  if (e == hipSuccess) e = dalloc(&d_keys, (size_t)Pc * Npad);
-  if (e == hipSuccess) e = dalloc(&d_rows, (size_t)Pc * Npad);
-  if (e == hipSuccess) e = dalloc(&d_runs, (size_t)Pc * K * 2 * n);
-  if (e == hipSuccess) e = dalloc(&d_out, (size_t)Pc * K * 3);
-  if (e == hipSuccess) e = hipMemcpy(d_unc, uncerts, n * U * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_iou, ious, n * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_tp, tp_class, n, hipMemcpyHostToDevice);
-  if (e == hipSuccess && group) e = hipMemcpy(d_group, group, n * sizeof(int32_t), hipMemcpyHostToDevice);
-  ThrArgs a{};
-  a.uncerts = d_unc; a.ious = d_iou; a.tp_class = d_tp; a.group = d_group; a.params = d_par; a.mask = d_mask;
-  a.keys = d_keys; a.rows = d_rows; a.runs = d_runs; a.out = d_out;
-  a.N = N; a.Npad = Npad; a.U = U; a.G = G; a.K = K; a.fix_cd = fix_cd != 0; a.budget = budget;
-  for (int k = 0; k < K; ++k) a.thr[k] = iou_thrs[k];
-  if (e == hipSuccess) {
-    launch_thr_mask(a, nullptr);
-    e = hipGetLastError();
-  }
-  std::vector<double> h((size_t)Pc * K * 3);
-  for (int p0 = 0; e == hipSuccess && p0 < P; p0 += Pc) {
-    a.Pc = std::min(Pc, P - p0);
-    e = hipMemcpy(d_par, params + (size_t)p0 * stride, (size_t)a.Pc * stride * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) break;
-    launch_thr_objective(a, nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(h.data(), d_out, (size_t)a.Pc * K * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) break;
-    for (size_t q = 0; q < (size_t)a.Pc * K; ++q) {
-      const size_t o = (size_t)p0 * K + q;
-      if (thr) thr[o] = h[3 * q];
-      if (rate) rate[o] = h[3 * q + 1];
-      if (auc) auc[o] = h[3 * q + 2];
-    }
-  }
-  void* ptrs[] = {d_unc, d_iou, d_tp, d_group, d_mask, d_par, d_keys, d_rows, d_runs, d_out};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  if (e != hipSuccess) return fail(nullptr, "%s: %s", who, hipGetErrorString(e));
-  return 0;
-}
-
-extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,
-                                 const int32_t* tab_off, const double* xs, const double* ys, const float* temps, float* out) {
-  if (!c || !out) return c ? fail(c, "calibrate_box: NULL out") : 1;
-  if (c->last_post_mode != UDA_POST_GLOBAL) return fail(c, "calibrate_box: needs the global post-process (uncertainty columns)");
-  const int bc = box_cols_of(c->model, UDA_POST_GLOBAL), cc = cls_cols_of(c->model, UDA_POST_GLOBAL);
-  if (col0 < 4 || col0 + 4 > bc || (col0 & 3)) return fail(c, "calibrate_box: columns %d..%d outside the %d box columns", col0, col0 + 3, bc);
-  const bool iso = mode >= UDA_CALIB_ISO_ALL;
-  if (mode < 0 || mode > UDA_CALIB_ISO_PERCLSCOO) return fail(c, "calibrate_box: unknown mode %d", mode);
-  if (!iso && !temps) return fail(c, "calibrate_box: temperature scaling needs temps");
-  if (relative && mode != UDA_CALIB_ISO_PERCLSCOO) return fail(c, "calibrate_box: the relative variant exists per class and coordinate only");
-  const int want = mode == UDA_CALIB_ISO_ALL ? 1 : (mode == UDA_CALIB_ISO_PERCOO ? 4 : 4 * c->model.num_classes);
-  if (iso && (n_tables != want || !tab_off || !xs || !ys))
-    return fail(c, "calibrate_box: mode %d needs %d tables, got %d", mode, want, n_tables);
-  HIPC(c, hipSetDevice(c->device));
-  if (int rc = finish_post(c)) return rc;
-  CalibArgs a{};
-  double *d_xs = nullptr, *d_ys = nullptr;
-  int32_t* d_off = nullptr;
-  float* d_out = nullptr;
-  const size_t rows = (size_t)c->last_n * c->model.max_output_size;
-  if (iso) {
-    const size_t tot = (size_t)tab_off[n_tables];
-    for (int t = 0; t < n_tables; ++t)
-      if (tab_off[t + 1] < tab_off[t]) return fail(c, "calibrate_box: table offsets must be non-decreasing");
-    HIPC(c, dalloc(&d_xs, tot)); HIPC(c, dalloc(&d_ys, tot)); HIPC(c, dalloc(&d_off, (size_t)n_tables + 1));
-    HIPC(c, hipMemcpyAsync(d_xs, xs, tot * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(d_ys, ys, tot * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(d_off, tab_off, ((size_t)n_tables + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPC(c, dalloc(&d_out, rows * 4));
-  a.boxes = c->d_oboxes; a.classes = c->d_oclasses; a.out = d_out;
-  a.xs = d_xs; a.ys = d_ys; a.tab_off = d_off;
-  for (int j = 0; j < 4; ++j) a.temps[j] = temps ? temps[mode == UDA_CALIB_TS_ALL ? 0 : j] : 1.f;
-  a.rows = (int)rows; a.box_cols = bc; a.cls_cols = cc; a.col0 = col0;
-  a.mode = mode; a.relative = relative; a.n_tables = n_tables;
-  launch_calib(a, c->stream);
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, rows * 4 * sizeof(float), hipMemcpyDeviceToHost);
-  if (d_xs) hipFree(d_xs);
-  if (d_ys) hipFree(d_ys);
-  if (d_off) hipFree(d_off);
-  hipFree(d_out);
-  if (e != hipSuccess) return fail(c, "calibrate_box: %s", hipGetErrorString(e));
-  return 0;
-}
-
-extern "C" int uda_calibrate_class(uda_ctx_t* c, int32_t mode, int32_t n_tables, const int32_t* tab_off, const double* xs,
-                                   const double* ys, const float* temps, int32_t draws, uint64_t seed, float* probs,
-                                   float* entropy, float* uncert) {
-  if (!c || !probs || !entropy) return c ? fail(c, "calibrate_class: NULL output") : 1;
-  const uda_model_t& m = c->model;
-  if (c->last_post_mode != UDA_POST_GLOBAL || !m.enable_softmax)
-    return fail(c, "calibrate_class: needs the logits of the global post-process (enable_softmax)");
-  if (mode < UDA_CLS_TS || mode > UDA_CLS_ISO_PERCLS) return fail(c, "calibrate_class: unknown mode %d", mode);
-  const int C = m.num_classes;
-  if (C > 128) return fail(c, "calibrate_class: more than 128 classes");
-  if (mode == UDA_CLS_TS && !temps) return fail(c, "calibrate_class: temperature scaling needs %d temperatures", C);
-  const int want = mode == UDA_CLS_ISO_ALL ? 1 : C;
-  if (mode != UDA_CLS_TS && (n_tables != want || !tab_off || !xs || !ys))
-    return fail(c, "calibrate_class: mode %d needs %d isotonic tables, got %d", mode, want, n_tables);
-  const int cc = cls_cols_of(m, UDA_POST_GLOBAL);
-  if (draws < 0 || draws > 1000) return fail(c, "calibrate_class: draws %d outside [0, 1000]", draws);
-  if (draws > 0 && cc != 1 + C)
-    return fail(c, "calibrate_class: sampling needs the MC std of every class logit (MC dropout on the class head, max_nms_inputs = 0)");
-  HIPC(c, hipSetDevice(c->device));
-  if (int rc = finish_post(c)) return rc;
-  const size_t rows = (size_t)c->last_n * m.max_output_size;
-  double *d_xs = nullptr, *d_ys = nullptr;
-  int32_t* d_off = nullptr;
-  float *d_t = nullptr, *d_p = nullptr, *d_e = nullptr, *d_u = nullptr;
-  hipError_t e = hipSuccess;
-  auto up = [&](auto** dst, const void* src, size_t bytes) {
-    if (e != hipSuccess) return;
-    e = hipMalloc((void**)dst, bytes ? bytes : 1);
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, c->stream);
-  };
-  if (mode != UDA_CLS_TS) {
-    for (int t = 0; t < n_tables; ++t)
-      if (tab_off[t + 1] <= tab_off[t]) return fail(c, "calibrate_class: every isotonic table needs at least one threshold");
-    const size_t tot = (size_t)tab_off[n_tables];
-    up(&d_xs, xs, tot * sizeof(double)); up(&d_ys, ys, tot * sizeof(double)); up(&d_off, tab_off, ((size_t)n_tables + 1) * sizeof(int32_t));
-  } else {
-    up(&d_t, temps, (size_t)C * sizeof(float));
-  }
-  if (e == hipSuccess) e = hipMalloc((void**)&d_p, rows * C * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_e, rows * sizeof(float));
-  if (e == hipSuccess && uncert) e = hipMalloc((void**)&d_u, rows * C * sizeof(float));
-  if (e == hipSuccess) {
-    ClsCalibArgs k{};
-    k.logits = c->d_ologits; k.classes = c->d_oclasses; k.probs = d_p; k.entropy = d_e; k.uncert = d_u;
-    k.xs = d_xs; k.ys = d_ys; k.tab_off = d_off; k.temps = d_t;
-    k.rows = (int)rows; k.C = C; k.cls_cols = cc; k.mode = mode; k.draws = draws; k.seed = seed;
-    launch_class_calib(k, c->stream);
-    e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(probs, d_p, rows * C * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(entropy, d_e, rows * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && uncert) {
-    if (draws > 0) e = hipMemcpy(uncert, d_u, rows * C * sizeof(float), hipMemcpyDeviceToHost);
-    else memset(uncert, 0, rows * C * sizeof(float));
-  }
-  void* fr[] = {d_xs, d_ys, d_off, d_t, d_p, d_e, d_u};
-  for (void* p : fr) if (p) hipFree(p);
-  if (e != hipSuccess) return fail(c, "calibrate_class: %s", hipGetErrorString(e));
-  return 0;
-}
-
-// CRC-32C (Castagnoli, reflected polynomial 0x82F63B78), slicing-by-8 on the host: the per-tensor checksum of TensorFlow
-// checkpoint bundles (ckpt_reader.py verifies every tensor it restores; a pure-Python table CRC manages ~1 MB/s).
-extern "C" uint32_t uda_crc32c(const void* data, uint64_t n, uint32_t crc) {
-  struct Tables {
-    uint32_t t[8][256];
-    Tables() {
-      for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0x82F63B78u : c >> 1;
-        t[0][i] = c;
-      }
-      for (uint32_t i = 0; i < 256; ++i)
-        for (int k = 1; k < 8; ++k) t[k][i] = (t[k - 1][i] >> 8) ^ t[0][t[k - 1][i] & 0xFFu];
-    }
-  };
-  static const Tables tables;          // function-local static: initialised once, thread-safe (C++11) - ctypes releases the GIL
-  const uint32_t (*T)[256] = tables.t;
-  const uint8_t* p = (const uint8_t*)data;
-  crc = ~crc;
-  while (n >= 8) {
-    uint64_t w;
-    memcpy(&w, p, 8);
-    w ^= crc;
-    crc = T[7][w & 0xFF] ^ T[6][(w >> 8) & 0xFF] ^ T[5][(w >> 16) & 0xFF] ^ T[4][(w >> 24) & 0xFF] ^
-          T[3][(w >> 32) & 0xFF] ^ T[2][(w >> 40) & 0xFF] ^ T[1][(w >> 48) & 0xFF] ^ T[0][(w >> 56) & 0xFF];
-    p += 8; n -= 8;
-  }
-  while (n--) crc = T[0][(crc ^ *p++) & 0xFFu] ^ (crc >> 8);
-  return ~crc;
 }
 
 extern "C" int uda_serve(uda_ctx_t* c, const uint8_t* images, int32_t n, int32_t h, int32_t w,
@@ -3509,86 +2499,6 @@ extern "C" int uda_get_preprocessed(uda_ctx_t* c, float* images, float* scales) 
   return 0;
 }
 
-// ------------------------------------------------------------------------------------ standalone NMS
-extern "C" int uda_nms(uda_ctx_t* c, const float* boxes, const float* scores, int32_t n_img, int32_t k,
-                       int32_t max_out, float iou_thresh, float score_thresh, float soft_sigma, int32_t pad,
-                       int32_t* idx, float* out_scores, int32_t* valid) {
-  if (!c || !boxes || !scores || !idx || !out_scores || !valid) return c ? fail(c, "uda_nms: NULL argument") : 1;
-  if (n_img < 1 || k < 0 || max_out < 1 || max_out > 128) return fail(c, "uda_nms: bad sizes (max_out must be in [1, 128])");
-  HIPC(c, hipSetDevice(c->device));
-  const size_t NK = (size_t)n_img * (k ? k : 1), NM = (size_t)n_img * max_out;
-  float *d_boxes, *d_scores, *d_stale, *d_tent, *d_ub, *d_ss, *d_sb;
-  int32_t *d_begin, *d_ev, *d_si, *d_nsel, *d_done;
-  unsigned long long *d_bound, *d_win;
-  HIPC(c, dalloc(&d_boxes, NK * 4)); HIPC(c, dalloc(&d_scores, NK)); HIPC(c, dalloc(&d_stale, NK));
-  HIPC(c, dalloc(&d_tent, NK)); HIPC(c, dalloc(&d_ub, NK)); HIPC(c, dalloc(&d_ev, NK)); HIPC(c, dalloc(&d_begin, NK)); HIPC(c, dalloc(&d_si, NM));
-  HIPC(c, dalloc(&d_ss, NM)); HIPC(c, dalloc(&d_sb, NM * 4)); HIPC(c, dalloc(&d_bound, NM));
-  HIPC(c, dalloc(&d_win, NM)); HIPC(c, dalloc(&d_nsel, (size_t)n_img)); HIPC(c, dalloc(&d_done, (size_t)n_img));
-  if (k) {
-    HIPC(c, hipMemcpyAsync(d_boxes, boxes, NK * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(d_scores, scores, NK * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  }
-  NmsArgs a{};
-  a.boxes = d_boxes; a.stale = d_stale; a.begin = d_begin; a.tent = d_tent; a.ub = d_ub; a.ev = d_ev;
-  a.sel_idx = d_si; a.sel_score = d_ss; a.sel_box = d_sb; a.bound_key = d_bound; a.win_key = d_win;
-  a.nsel = d_nsel; a.done = d_done; a.n_img = n_img; a.K = k; a.M = max_out;
-  a.segs = 1; a.classes = nullptr;
-  nms_params(a, iou_thresh, score_thresh, soft_sigma);
-  uda_ctx::PrefixWs pw;
-  const int lp = prefix_target();
-  if (lp > 0 && k > solo_limit() && k > 2 * lp) HIPC(c, alloc_prefix_ws(pw, (size_t)n_img, 2 * lp, (size_t)max_out));
-  bool prefix = false;
-  {
-    ProfScope ps(c, 17);
-    NmsCoop coop;
-    if ((size_t)n_img * nms_coop_slot_words(max_out) <= (size_t)c->model.max_images * nms_coop_slot_words(c->model.max_output_size) && !c->coop_off) { coop.bar = c->d_coop_bar; coop.err = c->d_coop_err; coop.used = &c->coop_used; coop.not_launched = &c->coop_not_launched; }
-    if (k > 0) prefix = run_nms(a, d_scores, max_out, c->stream, pw.Lcap ? &pw : nullptr, 0, coop);
-    else launch_nms_init(a, d_scores, c->stream);
-  }
-  HIPC(c, hipStreamSynchronize(c->stream));
-  HIPC(c, hipGetLastError());
-  if (prefix) {            // problems whose prefix was not sufficient: the full candidate set, one problem at a time
-    std::vector<int32_t> bad((size_t)n_img);
-    HIPC(c, hipMemcpy(bad.data(), pw.bad, (size_t)n_img * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int p = 0; p < n_img; ++p) {
-      if (!bad[(size_t)p]) continue;
-      const size_t pk = (size_t)p * k, pm = (size_t)p * max_out;
-      NmsArgs f = a;
-      f.boxes = d_boxes + pk * 4; f.stale = d_stale + pk; f.begin = d_begin + pk; f.tent = d_tent + pk; f.ub = d_ub + pk; f.ev = d_ev + pk;
-      f.sel_idx = d_si + pm; f.sel_score = d_ss + pm; f.sel_box = d_sb + pm * 4; f.bound_key = d_bound + pm; f.win_key = d_win + pm;
-      f.nsel = d_nsel + p; f.done = d_done + p; f.n_img = 1;
-      ProfScope ps(c, 17);
-      NmsCoop coop;
-      if (!c->coop_off) { coop.bar = c->d_coop_bar; coop.err = c->d_coop_err; coop.used = &c->coop_used; coop.not_launched = &c->coop_not_launched; }
-      run_nms(f, d_scores + pk, max_out, c->stream, nullptr, 0, coop);
-      ++c->pfx_fallbacks;
-    }
-    HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipGetLastError());
-  }
-  free_prefix_ws(pw);
-  if (c->coop_used) {
-    c->coop_used = false;
-    int e = 0;
-    hipMemcpy(&e, c->d_coop_err, sizeof(int), hipMemcpyDeviceToHost);
-    if (e) {           // barrier time-out: redo with the two-launch version (see finish_post)
-      hipMemset(c->d_coop_err, 0, sizeof(int));
-      c->coop_off = true;
-      ++c->coop_fallbacks;
-      fprintf(stderr, "[uda] cooperative NMS: grid barrier timed out; falling back to two launches per epoch\n");
-      run_nms(a, d_scores, max_out, c->stream);
-      HIPC(c, hipStreamSynchronize(c->stream));
-    }
-  }
-  HIPC(c, hipMemcpy(valid, d_nsel, n_img * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPC(c, hipMemcpy(idx, d_si, NM * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPC(c, hipMemcpy(out_scores, d_ss, NM * sizeof(float), hipMemcpyDeviceToHost));
-  (void)pad;  // slots >= valid already hold index 0 / score 0.0 (the padded form); callers slice when pad == 0
-  void* frees[] = {d_boxes, d_scores, d_stale, d_tent, d_ub, d_ev, d_begin, d_si, d_ss, d_sb, d_bound, d_win, d_nsel, d_done};
-  for (void* p : frees) hipFree(p);
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------ profiling
 extern "C" int uda_profile_enable(uda_ctx_t* c, uint32_t kind_mask) {
   if (!c) return 1;
@@ -3603,189 +2513,5 @@ extern "C" int uda_profile_read(uda_ctx_t* c, int32_t kind, double* total_ms, in
   if (total_ms) *total_ms = c->prof[kind].total_ms;
   if (launches) *launches = c->prof[kind].launches;
   if (reset) { c->prof[kind].total_ms = 0; c->prof[kind].launches = 0; }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------ standalone 1x1 conv
-extern "C" int uda_debug_pw(int32_t device, const float* in, const float* w, const float* bias, const float* bn_scale,
-                            const float* bn_shift, const float* se, const float* mask, const float* res,
-                            int32_t rows, int32_t in_div, int32_t hw, int32_t cin, int32_t cout, int32_t act,
-                            int32_t terms, int32_t reps, float* out, float* avg_ms) {
-  if (!in || !w || !out || rows < 1 || in_div < 1 || rows % in_div || hw < 1 || cin < 4 || cin % 4 || cout < 1)
-    return fail(nullptr, "uda_debug_pw: bad argument");
-  if (terms != 0 && terms != 1 && terms != 3 && terms != 6 && terms != 16)
-    return fail(nullptr, "uda_debug_pw: terms must be 0 (f32 MFMA), 1 (fp16 x1), 3 (bf16 x2), 6 (bf16 x3) or 16 (fp16 x2)");
-  HIPC(nullptr, hipSetDevice(device));
-  const size_t rows_in = rows / in_div;
-  std::vector<void*> owned;
-  auto up = [&](const float* h, size_t n) -> float* {
-    if (!h) return nullptr;
-    float* d = nullptr;
-    if (hipMalloc((void**)&d, n * sizeof(float)) != hipSuccess) return nullptr;
-    owned.push_back(d);
-    hipMemcpy(d, h, n * sizeof(float), hipMemcpyHostToDevice);
-    return d;
-  };
-  PwArgs a{};
-  a.in = up(in, rows_in * hw * cin);
-  a.w = up(w, (size_t)cin * cout);
-  a.bias = up(bias, cout);
-  a.bn_scale = up(bn_scale, cout);
-  a.bn_shift = up(bn_shift, cout);
-  a.se = up(se, rows_in * cin);
-  a.mask = up(mask, (size_t)rows * cout);
-  a.res = up(res, (size_t)rows * hw * cout);
-  float* d_out = nullptr;
-  HIPC(nullptr, hipMalloc((void**)&d_out, (size_t)rows * hw * cout * sizeof(float)));
-  owned.push_back(d_out);
-  a.out = d_out;
-  a.HW = hw; a.Cin = cin; a.Cout = cout; a.in_div = in_div; a.res_div = 1; a.se_div = in_div; a.act = act;
-  uint16_t* d_ws = nullptr;
-  unsigned* d_oor = nullptr;
-  if (terms) {
-    const int scheme = terms == 6 ? UDA_SPLIT_BF16X3 : (terms == 16 ? UDA_SPLIT_F16X2 : (terms == 1 ? UDA_SPLIT_F16X1 : UDA_SPLIT_BF16X2));
-    // (as uda_create packs a 1x1 conv: fp16 pieces, one or two, carry the power-of-two weight scale)
-    const float scale = uda_split_f16(scheme) ? split_weight_scale(w, (size_t)cin * cout) : 1.0f;
-    std::vector<uint16_t> packed(pwb_packed_elems(cin, cout, scheme));
-    pwb_pack_weights(w, cin, cout, scheme, packed.data(), scale);
-    HIPC(nullptr, hipMalloc((void**)&d_ws, packed.size() * sizeof(uint16_t)));
-    owned.push_back(d_ws);
-    HIPC(nullptr, hipMemcpy(d_ws, packed.data(), packed.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIPC(nullptr, hipMalloc((void**)&d_oor, sizeof(unsigned)));
-    owned.push_back(d_oor);
-    HIPC(nullptr, hipMemset(d_oor, 0, sizeof(unsigned)));
-    a.wsplit = d_ws;
-    a.wparts = scheme;
-    a.wunscale = 1.0f / scale;
-    a.oor = d_oor;
-  }
-  hipStream_t st;
-  HIPC(nullptr, hipStreamCreate(&st));
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
-  auto go = [&]() { if (terms) launch_pwb(a, rows, st); else launch_pw(a, rows, st); };
-  go();                                   // warm-up (and the result that is read back)
-  hipEventRecord(e0, st);
-  for (int i = 0; i < reps; ++i) go();
-  hipEventRecord(e1, st);
-  hipError_t err = hipStreamSynchronize(st);
-  if (err == hipSuccess) err = hipGetLastError();
-  float ms = 0;
-  hipEventElapsedTime(&ms, e0, e1);
-  if (avg_ms) *avg_ms = reps > 0 ? ms / reps : 0.f;
-  if (err == hipSuccess) err = hipMemcpy(out, d_out, (size_t)rows * hw * cout * sizeof(float), hipMemcpyDeviceToHost);
-  unsigned oor = 0;
-  if (err == hipSuccess && d_oor) err = hipMemcpy(&oor, d_oor, sizeof(unsigned), hipMemcpyDeviceToHost);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  hipStreamDestroy(st);
-  for (void* p : owned) hipFree(p);
-  if (err != hipSuccess) return fail(nullptr, "uda_debug_pw: %s", hipGetErrorString(err));
-  if (oor) return fail(nullptr, "uda_debug_pw: an input above 65504 cannot be split into fp16 pieces (terms = %d)", terms);
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------ numpy NMS family (a18)
-template <typename T>
-static int run_nmsnp(int device, const std::vector<T>& dets, const std::vector<int32_t>& off, int method, double iou_thr,
-                     double sigma, double score_thr, std::vector<T>& out, std::vector<int32_t>& n_out) {
-  const int problems = (int)off.size() - 1;
-  const size_t total = (size_t)off.back();
-  out.assign(total * 5, (T)0);
-  n_out.assign(problems > 0 ? problems : 0, 0);
-  if (problems <= 0 || total == 0) return 0;
-  HIPC(nullptr, hipSetDevice(device));
-  T *d_dets = nullptr, *d_score = nullptr, *d_out = nullptr;
-  int32_t *d_off = nullptr, *d_state = nullptr, *d_nout = nullptr;
-  HIPC(nullptr, dalloc(&d_dets, total * 5)); HIPC(nullptr, dalloc(&d_score, total)); HIPC(nullptr, dalloc(&d_out, total * 5));
-  HIPC(nullptr, dalloc(&d_off, off.size())); HIPC(nullptr, dalloc(&d_state, total)); HIPC(nullptr, dalloc(&d_nout, (size_t)problems));
-  HIPC(nullptr, hipMemcpy(d_dets, dets.data(), total * 5 * sizeof(T), hipMemcpyHostToDevice));
-  HIPC(nullptr, hipMemcpy(d_off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  NmsNpArgs<T> a{};
-  a.dets = d_dets; a.off = d_off; a.score = d_score; a.state = d_state; a.out = d_out; a.n_out = d_nout;
-  a.method = method; a.iou_thr = (T)iou_thr; a.sigma = (T)sigma; a.score_thr = (T)score_thr;
-  launch_nmsnp<T>(a, problems, nullptr);
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, total * 5 * sizeof(T), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(n_out.data(), d_nout, (size_t)problems * sizeof(int32_t), hipMemcpyDeviceToHost);
-  void* fr[] = {d_dets, d_score, d_out, d_off, d_state, d_nout};
-  for (void* p : fr) hipFree(p);
-  if (e != hipSuccess) return fail(nullptr, "nms_np: %s", hipGetErrorString(e));
-  return 0;
-}
-
-// rows sorted by score, descending (what `dets[:, 4].argsort()[::-1]` yields for distinct scores; ties: later index first)
-template <typename T>
-static void sort_desc(std::vector<T>& dets, int begin, int n) {
-  std::vector<int> idx(n);
-  std::iota(idx.begin(), idx.end(), 0);
-  std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) {
-    const T sx = dets[(size_t)(begin + x) * 5 + 4], sy = dets[(size_t)(begin + y) * 5 + 4];
-    return sx > sy || (sx == sy && x > y);
-  });
-  std::vector<T> tmp((size_t)n * 5);
-  for (int i = 0; i < n; ++i)
-    for (int k = 0; k < 5; ++k) tmp[(size_t)i * 5 + k] = dets[(size_t)(begin + idx[i]) * 5 + k];
-  std::copy(tmp.begin(), tmp.end(), dets.begin() + (size_t)begin * 5);
-}
-
-extern "C" int uda_nms_np(int32_t device, const double* dets, int32_t n, int32_t method, double iou_thresh, double sigma,
-                          double score_thresh, double* out, int32_t* n_out) {
-  if (!dets || !out || !n_out || n < 0 || method < 0 || method > 3) return fail(nullptr, "uda_nms_np: bad argument");
-  std::vector<double> d(dets, dets + (size_t)n * 5), o;
-  std::vector<int32_t> off = {0, n}, no;
-  if (method <= 1) sort_desc(d, 0, n);
-  const int rc = run_nmsnp<double>(device, d, off, method, iou_thresh, sigma, score_thresh, o, no);
-  if (rc) return rc;
-  *n_out = n ? no[0] : 0;
-  std::copy(o.begin(), o.begin() + (size_t)*n_out * 5, out);
-  return 0;
-}
-
-extern "C" int uda_per_class_nms_np(int32_t device, const float* boxes, const float* scores, const int32_t* classes, int32_t k,
-                                    float image_id, float image_scale, int32_t num_classes, int32_t max_boxes, int32_t method,
-                                    float iou_thresh, float sigma, float score_thresh, float* out) {
-  if (!boxes || !scores || !classes || !out || k < 0 || num_classes < 1 || max_boxes < 1 || method < 0 || method > 3)
-    return fail(nullptr, "uda_per_class_nms_np: bad argument");
-  std::vector<float> d;
-  std::vector<int32_t> off = {0}, cls_of;
-  for (int c = 0; c < num_classes; ++c) {
-    const int begin = off.back();
-    int n = 0;
-    for (int i = 0; i < k; ++i)
-      if (classes[i] == c) {           // boxes arrive y1,x1,y2,x2 -> x1,y1,x2,y2 (nms_np.py:234)
-        d.insert(d.end(), {boxes[i * 4 + 1], boxes[i * 4 + 0], boxes[i * 4 + 3], boxes[i * 4 + 2], scores[i]});
-        ++n;
-      }
-    if (!n) continue;
-    if (method <= 1) sort_desc(d, begin, n);
-    off.push_back(begin + n);
-    cls_of.push_back(c);
-  }
-  std::vector<float> o;
-  std::vector<int32_t> no;
-  const int rc = run_nmsnp<float>(device, d, off, method, iou_thresh, sigma, score_thresh, o, no);
-  if (rc) return rc;
-  struct Row { float v[7]; };
-  std::vector<Row> rows;
-  for (size_t p = 0; p + 1 < off.size(); ++p)
-    for (int i = 0; i < no[p]; ++i) {
-      const float* r = o.data() + ((size_t)off[p] + i) * 5;
-      rows.push_back(Row{{image_id, r[0], r[1], r[2], r[3], r[4], (float)(cls_of[p] + 1)}});
-    }
-  std::stable_sort(rows.begin(), rows.end(), [](const Row& x, const Row& y) { return x.v[5] > y.v[5]; });
-  for (int i = 0; i < max_boxes; ++i) {
-    float* dst = out + (size_t)i * 7;
-    if (i < (int)rows.size()) {
-      for (int j = 0; j < 7; ++j) dst[j] = rows[i].v[j];
-    } else {                           // dummy rows: score -1e5 (nms_np.py:256-274)
-      for (int j = 0; j < 7; ++j) dst[j] = 0.f;
-      dst[0] = image_id;
-      dst[5] = -1e5f;
-    }
-    for (int j = 1; j < 5; ++j) dst[j] *= image_scale;
-  }
   return 0;
 }

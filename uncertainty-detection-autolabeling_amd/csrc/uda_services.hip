@@ -1,0 +1,879 @@
+// The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
+// COCO matching and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
+// on scratch device memory of their own (the *_np twins, the thresholding objective, uda_nms, uda_debug_pw, the numpy NMS family).
+// Host code only: every kernel launched here lives in a kernels_*.hip.
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
+#include "dev_scratch.h"
+#include "uda_ctx.h"
+
+static int hip_failed(uda_ctx* c, const char* who, hipError_t e) { return fail(c, "%s: %s", who, hipGetErrorString(e)); }
+
+// ---- what the services on resident detections share
+// No pipelined run is in flight and a post-process has run - the global one where `reads` ("the assignment reads", ...) is given.
+static int resident_ready(uda_ctx* c, const char* who, const char* reads) {
+  if (c->as[0].open || c->as[1].open) return fail(c, "%s: a pipelined run (uda_run_async) is in flight - uda_collect it first", who);
+  if (c->last_n < 1) return fail(c, "%s: no %spost-process has run yet", who, reads ? "global " : "");
+  if (reads && c->last_post_mode != UDA_POST_GLOBAL)
+    return fail(c, "%s: the last post-process ran per class; %s the global post-process", who, reads);
+  return 0;
+}
+// The handle's device is current and its detections are final (range replay / prefix redo / NMS fallback done).
+static int settle_detections(uda_ctx* c) {
+  HIPC(c, hipSetDevice(c->device));
+  return finish_post(c);
+}
+
+// ---- result packs: one device buffer per service, so that ONE copy brings a result to the host.  Built over the device buffer
+// where the kernel arguments are filled and over the host copy where the results are handed out.
+struct AssignPack {      // iou [n G] float64 | det_index [n G] int32 | count [n] int32 | error flag int32
+  char* base;
+  size_t n, G;
+  AssignPack(void* b, size_t n_, size_t G_) : base((char*)b), n(n_), G(G_) {}
+  size_t bytes() const { return n * G * (sizeof(double) + sizeof(int32_t)) + (n + 1) * sizeof(int32_t); }
+  double* iou() const { return (double*)base; }
+  int32_t* det_index() const { return (int32_t*)(base + n * G * sizeof(double)); }
+  int32_t* count() const { return det_index() + n * G; }
+  int32_t* err() const { return count() + n; }
+  int copy_out(uda_ctx* c, const char* who, int M, int32_t* det_index_out, double* iou_out, int32_t* count_out) const {
+    if (*err()) return fail(c, "%s: the rank method met a kept ground-truth row beyond the %d detections", who, M);
+    if (iou_out && n * G) memcpy(iou_out, iou(), n * G * sizeof(double));
+    if (det_index_out && n * G) memcpy(det_index_out, det_index(), n * G * sizeof(int32_t));
+    if (count_out) memcpy(count_out, count(), n * sizeof(int32_t));
+    return 0;
+  }
+};
+
+struct ScorePack {       // components [n, nc] float64 | count [n] int32 | class_counts [n, C] int32 | error flag int32
+  char* base;
+  size_t n, nc, C;
+  ScorePack(void* b, size_t n_, size_t nc_, size_t C_) : base((char*)b), n(n_), nc(nc_), C(C_) {}
+  size_t bytes() const { return n * nc * sizeof(double) + (n + n * C + 1) * sizeof(int32_t); }
+  double* comp() const { return (double*)base; }
+  int32_t* count() const { return (int32_t*)(base + n * nc * sizeof(double)); }
+  int32_t* class_counts() const { return count() + n; }
+  int32_t* err() const { return class_counts() + n * C; }
+  int copy_out(uda_ctx* c, const char* who, double* components, int32_t* count_out, int32_t* class_counts_out) const {
+    if (*err()) return fail(c, "%s: a kept detection has a class id outside 1..%d", who, (int)C);
+    if (components) memcpy(components, comp(), n * nc * sizeof(double));
+    if (count_out) memcpy(count_out, count(), n * sizeof(int32_t));
+    if (class_counts_out) memcpy(class_counts_out, class_counts(), n * C * sizeof(int32_t));
+    return 0;
+  }
+};
+
+static_assert(sizeof(uda_eval_record_t) == 44, "the record is 11 words");
+struct EvalPack {        // records [n, M] x 44 bytes | npig [n, C, 4] int32 | used [n] int32
+  char* base;
+  size_t n, M, C;
+  EvalPack(void* b, size_t n_, size_t M_, size_t C_) : base((char*)b), n(n_), M(M_), C(C_) {}
+  size_t bytes() const { return n * M * sizeof(uda_eval_record_t) + (n * C * 4 + n) * sizeof(int32_t); }
+  uda_eval_record_t* rec() const { return (uda_eval_record_t*)base; }
+  int32_t* npig() const { return (int32_t*)(base + n * M * sizeof(uda_eval_record_t)); }
+  int32_t* used() const { return npig() + n * C * 4; }
+  void copy_out(void* records, int32_t* npig_out, int32_t* used_out) const {
+    if (records) memcpy(records, rec(), n * M * sizeof(uda_eval_record_t));
+    if (npig_out) memcpy(npig_out, npig(), n * C * 4 * sizeof(int32_t));
+    if (used_out) memcpy(used_out, used(), n * sizeof(int32_t));
+  }
+};
+
+// ---- ground-truth assignment (reference utils_extra.py:44-64; validate_model.py:314-339, calibrate_model.py:133-147)
+// Width of a matched row: every column the global post-process produced, then what uda_get_class_probs adds.
+static int assigned_row_cols_of(const uda_model_t& m) {
+  return box_cols_of(m, UDA_POST_GLOBAL) + 1 + cls_cols_of(m, UDA_POST_GLOBAL) + (m.enable_softmax ? 2 * m.num_classes + 1 : 0);
+}
+// LDS of the two kernels: M boxes of 16 bytes, G row numbers of 4 bytes, each inside the 64 KiB a block may ask for
+static const int kAssignMaxM = 4096, kAssignMaxG = 16384;
+
+extern "C" int uda_assigned_row_cols(const uda_ctx_t* c, int32_t* cols) {
+  if (!c || !cols) return 1;
+  *cols = assigned_row_cols_of(c->model);
+  return 0;
+}
+
+extern "C" int uda_set_ground_truth(uda_ctx_t* c, const float* boxes, const float* classes, int32_t n, int32_t G) {
+  if (!c || !boxes || !classes) return c ? fail(c, "set_ground_truth: NULL argument") : 1;
+  const uda_model_t& m = c->model;
+  if (n < 1 || n > m.max_images) return fail(c, "set_ground_truth: %d images, the handle holds 1..%d", n, m.max_images);
+  if (G < 0 || G > kAssignMaxG) return fail(c, "set_ground_truth: %d ground-truth rows per image, at most %d", G, kAssignMaxG);
+  HIPC(c, hipSetDevice(c->device));
+  if (!c->gt_ev) HIPC(c, hipEventCreateWithFlags(&c->gt_ev, hipEventDisableTiming));
+  else HIPC(c, hipEventSynchronize(c->gt_ev));          // the previous upload has left the staging buffer
+  if (G > c->gt_cap || !c->d_gt_boxes) {
+    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffers)
+    void* old[] = {c->d_gt_boxes, c->d_gt_classes, c->d_asg_pack, c->d_asg_rows};
+    for (void* p : old)
+      if (p) hipFree(p);
+    if (c->h_gt) hipHostFree(c->h_gt);
+    c->d_gt_boxes = c->d_gt_classes = c->d_asg_rows = c->h_gt = nullptr; c->d_asg_pack = nullptr;
+    c->gt_cap = 0; c->asg_n = 0; c->asg_rows = -1;
+    const size_t cap = (size_t)std::max(G, 1), rows = (size_t)m.max_images * cap;
+    HIPC(c, dalloc(&c->d_gt_boxes, rows * 4));
+    HIPC(c, dalloc(&c->d_gt_classes, rows));
+    HIPC(c, dalloc(&c->d_asg_pack, AssignPack(nullptr, (size_t)m.max_images, cap).bytes()));
+    HIPC(c, dalloc(&c->d_asg_rows, rows * (size_t)assigned_row_cols_of(m)));
+    HIPC(c, hipHostMalloc((void**)&c->h_gt, rows * 5 * sizeof(float)));
+    c->gt_cap = (int)cap;
+  }
+  const size_t rows = (size_t)n * G;
+  if (rows) {
+    memcpy(c->h_gt, boxes, rows * 4 * sizeof(float));
+    memcpy(c->h_gt + rows * 4, classes, rows * sizeof(float));
+    HIPC(c, hipMemcpyAsync(c->d_gt_boxes, c->h_gt, rows * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->d_gt_classes, c->h_gt + rows * 4, rows * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPC(c, hipEventRecord(c->gt_ev, c->stream));
+  c->gt_n = n; c->gt_G = G;
+  return 0;
+}
+
+extern "C" int uda_assign_ground_truth(uda_ctx_t* c, int32_t method, int32_t keep) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  if (method < ASSIGN_IOU || method > ASSIGN_RANK) return fail(c, "assign_ground_truth: unknown method %d", method);
+  if (keep != ASSIGN_KEEP_VALIDATE && keep != ASSIGN_KEEP_CALIBRATE) return fail(c, "assign_ground_truth: unknown keep rule %d", keep);
+  if (c->gt_n < 1) return fail(c, "assign_ground_truth: no ground truth is set (uda_set_ground_truth)");
+  if (int rc = resident_ready(c, "assign_ground_truth", "the assignment reads")) return rc;
+  // after a consistency run the handle holds 4n images, the n originals first: the ground truth belongs to those
+  const bool cons = c->noise_from >= 0 && c->cons_n > 0 && c->last_n == 4 * c->cons_n;
+  if (c->gt_n != (cons ? c->cons_n : c->last_n))
+    return fail(c, "assign_ground_truth: ground truth of %d images, the last post-process holds %d", c->gt_n, cons ? c->cons_n : c->last_n);
+  if (m.max_output_size > kAssignMaxM) return fail(c, "assign_ground_truth: max_output_size %d above %d", m.max_output_size, kAssignMaxM);
+  if (int rc = settle_detections(c)) return rc;
+  const int n = c->gt_n, M = m.max_output_size, G = c->gt_G, C = m.enable_softmax ? m.num_classes : 0;
+  if (C)
+    if (int rc = ensure_probs(c, n * M)) return rc;
+  const AssignPack pack(c->d_asg_pack, (size_t)n, (size_t)G);
+  HIPC(c, hipMemsetAsync(pack.err(), 0, sizeof(int32_t), c->stream));
+  AssignArgs a{};
+  a.det_boxes = c->d_oboxes; a.det_stride = box_cols_of(m, UDA_POST_GLOBAL);
+  a.gt_boxes = c->d_gt_boxes; a.gt_classes = c->d_gt_classes;
+  a.det_index = pack.det_index(); a.iou = pack.iou(); a.count = pack.count(); a.err = pack.err();
+  a.n = n; a.M = M; a.G = G; a.method = method; a.keep = keep;
+  launch_assign_gt(a, c->stream);
+  AssignRowsArgs r{};
+  r.det_index = pack.det_index(); r.count = pack.count();
+  r.boxes = c->d_oboxes; r.scores = c->d_oscores; r.classes = c->d_oclasses;
+  r.logits = c->d_ologits; r.probs = c->d_oprobs; r.entropy = c->d_oentropy;
+  r.rows = c->d_asg_rows;
+  r.n = n; r.M = M; r.G = G; r.bc = a.det_stride; r.cc = cls_cols_of(m, UDA_POST_GLOBAL); r.C = C; r.cols = assigned_row_cols_of(m);
+  launch_gather_assigned(r, c->stream);
+  HIPC(c, hipGetLastError());
+  c->asg_n = n; c->asg_G = G; c->asg_rows = -1;
+  return 0;
+}
+
+// The first reader of an assignment waits for it and brings the packed results over in one copy.
+static int fetch_assignment(uda_ctx* c) {
+  if (c->asg_rows >= 0) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  AssignPack h(nullptr, (size_t)c->asg_n, (size_t)c->asg_G);
+  c->h_asg.resize(h.bytes());
+  h.base = c->h_asg.data();
+  HIPC(c, hipMemcpy(h.base, c->d_asg_pack, h.bytes(), hipMemcpyDeviceToHost));
+  if (int rc = h.copy_out(c, "assign_ground_truth", c->model.max_output_size, nullptr, nullptr, nullptr)) return rc;      // (the error word)
+  c->asg_rows = std::accumulate(h.count(), h.count() + h.n, (int64_t)0);
+  return 0;
+}
+
+extern "C" int uda_get_assignment(uda_ctx_t* c, int32_t* det_index, double* iou, int32_t* count) {
+  if (!c) return 1;
+  if (c->asg_n < 1) return fail(c, "get_assignment: no assignment (uda_assign_ground_truth)");
+  if (int rc = fetch_assignment(c)) return rc;
+  return AssignPack(c->h_asg.data(), (size_t)c->asg_n, (size_t)c->asg_G)
+      .copy_out(c, "assign_ground_truth", c->model.max_output_size, det_index, iou, count);
+}
+
+extern "C" int uda_get_assigned_rows(uda_ctx_t* c, float* rows, int64_t n_floats) {
+  if (!c) return 1;
+  if (c->asg_n < 1) return fail(c, "get_assigned_rows: no assignment (uda_assign_ground_truth)");
+  if (int rc = fetch_assignment(c)) return rc;
+  const int64_t want = c->asg_rows * assigned_row_cols_of(c->model);
+  if (n_floats != want) return fail(c, "get_assigned_rows: the %lld matched rows take %lld floats, not %lld", (long long)c->asg_rows, (long long)want, (long long)n_floats);
+  if (want && !rows) return fail(c, "get_assigned_rows: NULL output");
+  HIPC(c, hipSetDevice(c->device));
+  if (want) HIPC(c, hipMemcpy(rows, c->d_asg_rows, (size_t)want * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// gt_box_assigner for callers that hold detections of their own: host arrays in, the same kernel, host arrays out
+extern "C" int uda_assign_gt_np(int32_t device, const float* det_boxes, const float* gt_boxes, const float* gt_classes, int32_t n,
+                                int32_t M, int32_t G, int32_t method, int32_t keep, int32_t* det_index, double* iou, int32_t* count) {
+  if (n < 0 || M < 0 || G < 0 || M > kAssignMaxM || G > kAssignMaxG || method < ASSIGN_IOU || method > ASSIGN_RANK ||
+      (keep != ASSIGN_KEEP_VALIDATE && keep != ASSIGN_KEEP_CALIBRATE) || !count ||
+      ((size_t)n * G && (!gt_boxes || !gt_classes || !det_index || !iou)) || ((size_t)n * M && !det_boxes))
+    return fail(nullptr, "uda_assign_gt_np: bad argument");
+  if (n == 0) return 0;
+  const size_t nm = (size_t)n * M, ng = (size_t)n * G;
+  DevScratch s(device);
+  AssignArgs a{};
+  a.det_boxes = s.upload(det_boxes, nm * 4); a.det_stride = 4;
+  a.gt_boxes = s.upload(gt_boxes, ng * 4); a.gt_classes = s.upload(gt_classes, ng);
+  AssignPack pack(nullptr, (size_t)n, (size_t)G);
+  pack.base = s.alloc<char>(pack.bytes());
+  s.zero(pack.count(), ((size_t)n + 1) * sizeof(int32_t));
+  a.det_index = pack.det_index(); a.iou = pack.iou(); a.count = pack.count(); a.err = pack.err();
+  a.n = n; a.M = M; a.G = G; a.method = method; a.keep = keep;
+  if (s.ok()) launch_assign_gt(a, nullptr);
+  s.sync();
+  std::vector<char> h(pack.bytes());
+  s.download(h.data(), pack.base, h.size());
+  if (!s.ok()) return hip_failed(nullptr, "uda_assign_gt_np", s.err);
+  return AssignPack(h.data(), pack.n, pack.G).copy_out(nullptr, "uda_assign_gt_np", M, det_index, iou, count);
+}
+
+// ---- active-learning image scores (reference active_learning_loop.py:528-733 on the lines of infer_model.py:836-960)
+static const int kScoreMaxM = 4096, kScoreMaxC = 8192;      // rows a block walks; class counters in LDS (4 bytes each)
+
+// what a descriptor reads: bit (1 << uda_score_source); 0 with *why set when it is malformed
+static unsigned score_desc_sources(const uda_score_desc_t* d, const char** why) {
+  *why = nullptr;
+  if (!d) { *why = "NULL descriptor"; return 0; }
+  if (d->n_comp < 1 || d->n_comp > UDA_SCORE_MAX_COMP) { *why = "n_comp outside 1..3"; return 0; }
+  unsigned mask = 0;
+  for (int k = 0; k < d->n_comp; ++k) {
+    if (d->n_terms[k] < 1 || d->n_terms[k] > 2) { *why = "a component has 1 or 2 terms"; return 0; }
+    for (int t = 0; t < d->n_terms[k]; ++t) {
+      const int src = d->term[k][t].source, tr = d->term[k][t].transform;
+      const bool scalar = src == UDA_SCORE_ENTROPY || src == UDA_SCORE_DET_SCORE;
+      const bool box = src == UDA_SCORE_ALBOX || src == UDA_SCORE_MCBOX;
+      if (!scalar && !box && src != UDA_SCORE_MCCLASS) { *why = "unknown source"; return 0; }
+      if (scalar ? tr != UDA_SCORE_SCALAR : !(tr == UDA_SCORE_MEAN || (box && tr == UDA_SCORE_REL_MEAN))) {
+        *why = "transform does not fit the source (SCALAR: entropy / det_score; MEAN: albox / mcbox / mcclass; REL_MEAN: albox / mcbox)";
+        return 0;
+      }
+      mask |= 1u << src;
+    }
+  }
+  return mask;
+}
+
+extern "C" int uda_score_images(uda_ctx_t* c, const uda_score_desc_t* desc, float min_score) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  const char* why = nullptr;
+  const unsigned need = score_desc_sources(desc, &why);
+  if (why) return fail(c, "score_images: %s", why);
+  if (int rc = resident_ready(c, "score_images", "the scores read")) return rc;
+  if ((need & (1u << UDA_SCORE_ENTROPY)) && !m.enable_softmax)
+    return fail(c, "score_images: the model emits no entropy (enable_softmax is off)");
+  if ((need & (1u << UDA_SCORE_ALBOX)) && !(m.has_uncert && m.loss_attenuation))
+    return fail(c, "score_images: the model emits no aleatoric box uncertainty (no loss attenuation)");
+  if ((need & (1u << UDA_SCORE_MCBOX)) && !(m.has_uncert && m.box_stacked))
+    return fail(c, "score_images: the model emits no epistemic box uncertainty (no MC dropout on the box head)");
+  if ((need & (1u << UDA_SCORE_MCCLASS)) && !(m.has_uncert && m.cls_stacked))
+    return fail(c, "score_images: the model emits no epistemic class uncertainty (no MC dropout on the class head)");
+  if (m.max_output_size > kScoreMaxM) return fail(c, "score_images: max_output_size %d above %d", m.max_output_size, kScoreMaxM);
+  if (m.num_classes < 1 || m.num_classes > kScoreMaxC) return fail(c, "score_images: num_classes %d outside 1..%d", m.num_classes, kScoreMaxC);
+  if (int rc = settle_detections(c)) return rc;
+  const int n = c->last_n, M = m.max_output_size, C = m.num_classes, nc = desc->n_comp;
+  if (!c->d_score_pack) HIPC(c, dalloc(&c->d_score_pack, ScorePack(nullptr, (size_t)m.max_images, UDA_SCORE_MAX_COMP, (size_t)C).bytes()));
+  {
+    ProfScope ps(c, 19);
+    if (need & (1u << UDA_SCORE_ENTROPY))
+      if (int rc = ensure_probs(c, n * M)) return rc;
+    const int bc = box_cols_of(m, UDA_POST_GLOBAL), cc = cls_cols_of(m, UDA_POST_GLOBAL);
+    ScoreArgs<float> a{};
+    a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses; a.entropy = c->d_oentropy;
+    a.albox = c->d_oboxes + 4;                                               // box | aleatoric std | MC std, as each exists
+    a.mcbox = c->d_oboxes + ((m.has_uncert && m.loss_attenuation) ? 8 : 4);
+    a.mcclass = c->d_oclasses + 1;
+    a.box_stride = a.al_stride = a.mc_stride = bc; a.cls_stride = a.mcc_stride = cc; a.mcc_w = cc - 1;
+    const ScorePack pack(c->d_score_pack, (size_t)n, (size_t)nc, (size_t)C);
+    a.comp = pack.comp(); a.count = pack.count(); a.class_counts = pack.class_counts(); a.err = pack.err();
+    a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
+    HIPC(c, hipMemsetAsync(a.err, 0, sizeof(int32_t), c->stream));
+    launch_score_images(a, c->stream);
+  }
+  HIPC(c, hipGetLastError());
+  c->score_n = n; c->score_nc = nc; c->score_fetched = false;
+  return 0;
+}
+
+extern "C" int uda_image_scores_shape(const uda_ctx_t* c, int32_t* n, int32_t* n_comp) {
+  if (!c || !n || !n_comp) return 1;
+  *n = c->score_n; *n_comp = c->score_nc;
+  return 0;
+}
+
+extern "C" int uda_get_image_scores(uda_ctx_t* c, double* components, int32_t* count, int32_t* class_counts) {
+  if (!c) return 1;
+  if (c->score_n < 1) return fail(c, "get_image_scores: no scores (uda_score_images)");
+  ScorePack h(nullptr, (size_t)c->score_n, (size_t)c->score_nc, (size_t)c->model.num_classes);
+  if (!c->score_fetched) {       // the first reader of a scoring waits for it and brings the pack over in one copy
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->h_score.resize(h.bytes());
+    HIPC(c, hipMemcpy(c->h_score.data(), c->d_score_pack, h.bytes(), hipMemcpyDeviceToHost));
+    c->score_fetched = true;
+  }
+  h.base = c->h_score.data();
+  return h.copy_out(c, "score_images", components, count, class_counts);
+}
+
+// score_image for callers that hold detections of their own (calibrated columns, a gathered multi-GPU batch): host arrays in,
+// the same kernel, host arrays out; its own allocations
+template <typename T>
+static int score_images_np(const char* who, int32_t device, const uda_score_desc_t* desc, T min_score, const T* boxes, const T* scores,
+                           const T* classes, const T* entropy, const T* albox, const T* mcbox, const T* mcclass, int32_t n, int32_t M,
+                           int32_t C, int32_t mcw, double* components, int32_t* count, int32_t* class_counts) {
+  const char* why = nullptr;
+  const unsigned need = score_desc_sources(desc, &why);
+  if (why) return fail(nullptr, "%s: %s", who, why);
+  if (n < 0 || M < 0 || M > kScoreMaxM || C < 1 || C > kScoreMaxC || ((size_t)n * M && (!boxes || !scores || !classes)))
+    return fail(nullptr, "%s: bad argument", who);
+  const T* srcs[] = {entropy, scores, albox, mcbox, mcclass};
+  static const char* names[] = {"entropy", "scores", "albox", "mcbox", "mcclass"};
+  for (int s = 0; s < 5; ++s)
+    if ((need & (1u << s)) && (size_t)n * M && !srcs[s]) return fail(nullptr, "%s: the descriptor reads %s, which is not given", who, names[s]);
+  if ((need & (1u << UDA_SCORE_MCCLASS)) && mcw < 1) return fail(nullptr, "%s: mcclass_cols must be at least 1", who);
+  if (n == 0) return 0;
+  const size_t nm = (size_t)n * M, nc = desc->n_comp;
+  const size_t widths[] = {4, 1, 1, 1, 4, 4, (size_t)(mcw > 0 ? mcw : 0)};
+  const T* host[] = {boxes, scores, classes, entropy, albox, mcbox, mcclass};
+  DevScratch s(device);
+  T* dev[7] = {};
+  for (int k = 0; k < 7; ++k)
+    if (nm * widths[k]) dev[k] = s.upload(host[k], nm * widths[k]);
+  ScorePack pack(nullptr, (size_t)n, nc, (size_t)C);
+  pack.base = s.alloc<char>(pack.bytes());
+  s.zero(pack.base, pack.bytes());
+  if (s.ok()) {
+    ScoreArgs<T> a{};
+    a.boxes = dev[0]; a.scores = dev[1]; a.classes = dev[2]; a.entropy = dev[3]; a.albox = dev[4]; a.mcbox = dev[5]; a.mcclass = dev[6];
+    a.box_stride = a.al_stride = a.mc_stride = 4; a.cls_stride = 1; a.mcc_stride = a.mcc_w = mcw > 0 ? mcw : 0;
+    a.comp = pack.comp(); a.count = pack.count(); a.class_counts = pack.class_counts(); a.err = pack.err();
+    a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
+    launch_score_images(a, nullptr);
+  }
+  s.sync();
+  std::vector<char> h(pack.bytes());
+  s.download(h.data(), pack.base, h.size());
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  return ScorePack(h.data(), pack.n, pack.nc, pack.C).copy_out(nullptr, who, components, count, class_counts);
+}
+
+extern "C" int uda_score_images_np(int32_t device, const uda_score_desc_t* desc, double min_score, const double* boxes,
+                                   const double* scores, const double* classes, const double* entropy, const double* albox,
+                                   const double* mcbox, const double* mcclass, int32_t n, int32_t M, int32_t num_classes,
+                                   int32_t mcclass_cols, double* components, int32_t* count, int32_t* class_counts) {
+  return score_images_np<double>("uda_score_images_np", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass, n,
+                                 M, num_classes, mcclass_cols, components, count, class_counts);
+}
+
+extern "C" int uda_score_images_np_f32(int32_t device, const uda_score_desc_t* desc, float min_score, const float* boxes,
+                                       const float* scores, const float* classes, const float* entropy, const float* albox,
+                                       const float* mcbox, const float* mcclass, int32_t n, int32_t M, int32_t num_classes,
+                                       int32_t mcclass_cols, double* components, int32_t* count, int32_t* class_counts) {
+  return score_images_np<float>("uda_score_images_np_f32", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass,
+                                n, M, num_classes, mcclass_cols, components, count, class_counts);
+}
+
+// ---- COCO matching (reference custom_cocoeval.py:265-349 on the containers of coco_metric.py:219-283)
+static const int kEvalMaxC = 8192;
+
+static const char* eval_thrs_bad(const double* thrs, int32_t T) {
+  if (T < 1 || T > COCO_MAX_T) return "T outside 1..32 thresholds";
+  if (!thrs) return "NULL thresholds";
+  return nullptr;
+}
+
+extern "C" int uda_set_eval_ground_truth(uda_ctx_t* c, const float* gt, int32_t n, int32_t G) {
+  if (!c || !gt) return c ? fail(c, "set_eval_ground_truth: NULL argument") : 1;
+  const uda_model_t& m = c->model;
+  if (n < 1 || n > m.max_images) return fail(c, "set_eval_ground_truth: %d images, the handle holds 1..%d", n, m.max_images);
+  if (G < 0 || G > COCO_MAX_G) return fail(c, "set_eval_ground_truth: %d ground-truth rows per image, at most %d", G, (int)COCO_MAX_G);
+  HIPC(c, hipSetDevice(c->device));
+  if (!c->egt_ev) HIPC(c, hipEventCreateWithFlags(&c->egt_ev, hipEventDisableTiming));
+  else HIPC(c, hipEventSynchronize(c->egt_ev));         // the previous upload has left the staging buffer
+  if (G > c->egt_cap || !c->d_egt) {
+    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffer)
+    if (c->d_egt) hipFree(c->d_egt);
+    if (c->h_egt) hipHostFree(c->h_egt);
+    c->d_egt = c->h_egt = nullptr; c->egt_cap = 0; c->egt_n = 0;
+    const size_t cap = (size_t)std::max(G, 1), rows = (size_t)m.max_images * cap;
+    HIPC(c, dalloc(&c->d_egt, rows * 7));
+    HIPC(c, hipHostMalloc((void**)&c->h_egt, rows * 7 * sizeof(float)));
+    c->egt_cap = (int)cap;
+  }
+  const size_t floats = (size_t)n * G * 7;
+  if (floats) {
+    memcpy(c->h_egt, gt, floats * sizeof(float));
+    HIPC(c, hipMemcpyAsync(c->d_egt, c->h_egt, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPC(c, hipEventRecord(c->egt_ev, c->stream));
+  c->egt_n = n; c->egt_G = G;
+  return 0;
+}
+
+extern "C" int uda_eval_match(uda_ctx_t* c, const double* iou_thrs, int32_t T) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  if (const char* why = eval_thrs_bad(iou_thrs, T)) return fail(c, "eval_match: %s", why);
+  if (c->egt_n < 1) return fail(c, "eval_match: no ground truth is set (uda_set_eval_ground_truth)");
+  if (int rc = resident_ready(c, "eval_match", nullptr)) return rc;
+  if (c->egt_n != c->last_n)
+    return fail(c, "eval_match: ground truth of %d images, the last post-process holds %d", c->egt_n, c->last_n);
+  if (m.max_output_size > COCO_MAX_M) return fail(c, "eval_match: max_output_size %d above %d", m.max_output_size, (int)COCO_MAX_M);
+  if (m.num_classes < 1 || m.num_classes > kEvalMaxC) return fail(c, "eval_match: num_classes %d outside 1..%d", m.num_classes, kEvalMaxC);
+  if (int rc = settle_detections(c)) return rc;
+  const int n = c->last_n, M = m.max_output_size, C = m.num_classes;
+  if (!c->d_eval_pack) HIPC(c, dalloc(&c->d_eval_pack, EvalPack(nullptr, (size_t)m.max_images, (size_t)M, (size_t)C).bytes()));
+  {
+    ProfScope ps(c, 20);
+    CocoMatchArgs a{};
+    a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses;
+    a.box_stride = box_cols_of(m, c->last_post_mode); a.cls_stride = cls_cols_of(m, c->last_post_mode);
+    a.gt = c->d_egt;
+    const EvalPack pack(c->d_eval_pack, (size_t)n, (size_t)M, (size_t)C);
+    a.rec = pack.rec(); a.npig = pack.npig(); a.used = pack.used();
+    a.n = n; a.M = M; a.G = c->egt_G; a.C = C; a.T = T; a.legacy = 0;
+    for (int t = 0; t < T; ++t) a.thr[t] = iou_thrs[t];
+    launch_coco_match(a, c->stream);
+  }
+  HIPC(c, hipGetLastError());
+  c->eval_n = n; c->eval_fetched = false;
+  return 0;
+}
+
+extern "C" int uda_get_eval_records(uda_ctx_t* c, void* records, int32_t* npig, int32_t* used) {
+  if (!c) return 1;
+  if (c->eval_n < 1) return fail(c, "get_eval_records: no match (uda_eval_match)");
+  EvalPack h(nullptr, (size_t)c->eval_n, (size_t)c->model.max_output_size, (size_t)c->model.num_classes);
+  if (!c->eval_fetched) {        // the first reader of a match waits for it and brings the pack over in one copy
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->h_eval.resize(h.bytes());
+    HIPC(c, hipMemcpy(c->h_eval.data(), c->d_eval_pack, h.bytes(), hipMemcpyDeviceToHost));
+    c->eval_fetched = true;
+  }
+  h.base = c->h_eval.data();
+  h.copy_out(records, npig, used);
+  return 0;
+}
+
+// evaluateImg for callers that hold legacy rows of their own (the nms_np route, gathered detections): host arrays in, the same
+// kernel in its legacy-row layout, host arrays out; its own allocations
+extern "C" int uda_eval_match_np(int32_t device, const float* det_rows, const float* gt, int32_t n, int32_t M, int32_t G,
+                                 int32_t num_classes, const double* iou_thrs, int32_t T, void* records, int32_t* npig, int32_t* used) {
+  if (const char* why = eval_thrs_bad(iou_thrs, T)) return fail(nullptr, "uda_eval_match_np: %s", why);
+  if (G > COCO_MAX_G) return fail(nullptr, "uda_eval_match_np: %d ground-truth rows per image, at most %d", G, (int)COCO_MAX_G);
+  if (M > COCO_MAX_M) return fail(nullptr, "uda_eval_match_np: %d detection rows per image, at most %d", M, (int)COCO_MAX_M);
+  if (n < 0 || M < 0 || G < 0 || num_classes < 1 || num_classes > kEvalMaxC || ((size_t)n * M && !det_rows) || ((size_t)n * G && !gt))
+    return fail(nullptr, "uda_eval_match_np: bad argument");
+  if (n == 0) return 0;
+  DevScratch s(device);
+  CocoMatchArgs a{};
+  a.rows = s.upload(det_rows, (size_t)n * M * 7); a.gt = s.upload(gt, (size_t)n * G * 7);
+  EvalPack pack(nullptr, (size_t)n, (size_t)M, (size_t)num_classes);
+  pack.base = s.alloc<char>(pack.bytes());
+  s.zero(pack.base, pack.bytes());
+  a.rec = pack.rec(); a.npig = pack.npig(); a.used = pack.used();
+  a.n = n; a.M = M; a.G = G; a.C = num_classes; a.T = T; a.legacy = 1;
+  for (int t = 0; t < T; ++t) a.thr[t] = iou_thrs[t];
+  if (s.ok()) launch_coco_match(a, nullptr);
+  s.sync();
+  std::vector<char> h(pack.bytes());
+  s.download(h.data(), pack.base, h.size());
+  if (!s.ok()) return hip_failed(nullptr, "uda_eval_match_np", s.err);
+  EvalPack(h.data(), pack.n, pack.M, pack.C).copy_out(records, npig, used);
+  return 0;
+}
+
+// the objective of the thresholding search for P candidates: host arrays in, chunks of candidates through the device (scratch of
+// at most kThrScratchBytes, or one candidate's), host arrays out; its own allocations
+static const size_t kThrScratchBytes = (size_t)64 << 20;
+extern "C" int uda_thr_objective_np(int32_t device, const double* uncerts, const double* ious, const uint8_t* tp_class,
+                                    const int32_t* group, int32_t N, int32_t U, int32_t G, const double* iou_thrs, int32_t K,
+                                    const double* params, int32_t P, int32_t fix_cd, double budget, double* thr, double* rate,
+                                    double* auc) {
+  const char* who = "uda_thr_objective_np";
+  if (N < 2 || N > THR_MAX_N) return fail(nullptr, "%s: %d rows, 2..%d are taken", who, N, (int)THR_MAX_N);
+  if (U < 1 || U > THR_MAX_U) return fail(nullptr, "%s: %d uncertainties, 1..%d are taken", who, U, (int)THR_MAX_U);
+  if (K < 1 || K > THR_MAX_K) return fail(nullptr, "%s: %d IoU thresholds, 1..%d are taken", who, K, (int)THR_MAX_K);
+  if (P < 1 || P > THR_MAX_P) return fail(nullptr, "%s: %d candidates, 1..%d are taken", who, P, (int)THR_MAX_P);
+  if (G < 0 || G > THR_MAX_G) return fail(nullptr, "%s: %d groups, 0..%d are taken", who, G, (int)THR_MAX_G);
+  if (!uncerts || !ious || !tp_class || !iou_thrs || !params) return fail(nullptr, "%s: NULL input", who);
+  if ((G > 0) != (group != nullptr)) return fail(nullptr, "%s: group ids and G > 0 go together", who);
+  if (!(budget > 0.0 && budget < 1.0)) return fail(nullptr, "%s: budget %g is not strictly between 0 and 1", who, budget);
+  for (int i = 0; group && i < N; ++i)
+    if (group[i] < 0 || group[i] >= G) return fail(nullptr, "%s: group id %d of row %d outside 0..%d", who, group[i], i, G - 1);
+  int Npad = THR_TILE;
+  while (Npad < N) Npad <<= 1;
+  const size_t n = (size_t)N, stride = (size_t)U * (size_t)(G > 0 ? G : 1);
+  const size_t per = 12 * (size_t)Npad + 8 * n * K + 24 * (size_t)K + 8 * stride;
+  size_t fit = kThrScratchBytes / per;
+  const int Pc = (int)std::min<size_t>(std::max<size_t>(fit, 1), std::min<size_t>((size_t)P, THR_MAX_CHUNK));
+  DevScratch s(device);
+  ThrArgs a{};
+  a.uncerts = s.upload(uncerts, n * U); a.ious = s.upload(ious, n); a.tp_class = s.upload(tp_class, n); a.group = s.upload(group, n);
+  a.mask = s.alloc<uint32_t>(n);
+  double* d_par = s.alloc<double>((size_t)Pc * stride);
+  a.params = d_par;
+  a.keys = s.alloc<uint64_t>((size_t)Pc * Npad); a.rows = s.alloc<int32_t>((size_t)Pc * Npad);
+  a.runs = s.alloc<int32_t>((size_t)Pc * K * 2 * n); a.out = s.alloc<double>((size_t)Pc * K * 3);
+  a.N = N; a.Npad = Npad; a.U = U; a.G = G; a.K = K; a.fix_cd = fix_cd != 0; a.budget = budget;
+  for (int k = 0; k < K; ++k) a.thr[k] = iou_thrs[k];
+  if (s.ok()) launch_thr_mask(a, nullptr);
+  std::vector<double> h((size_t)Pc * K * 3);
+  for (int p0 = 0; s.ok() && p0 < P; p0 += Pc) {
+    a.Pc = std::min(Pc, P - p0);
+    s.err = hipMemcpy(d_par, params + (size_t)p0 * stride, (size_t)a.Pc * stride * sizeof(double), hipMemcpyHostToDevice);
+    if (s.ok()) launch_thr_objective(a, nullptr);
+    if (s.ok()) s.err = hipGetLastError();
+    s.download(h.data(), a.out, (size_t)a.Pc * K * 3 * sizeof(double));
+    if (!s.ok()) break;
+    for (size_t q = 0; q < (size_t)a.Pc * K; ++q) {
+      const size_t o = (size_t)p0 * K + q;
+      if (thr) thr[o] = h[3 * q];
+      if (rate) rate[o] = h[3 * q + 1];
+      if (auc) auc[o] = h[3 * q + 2];
+    }
+  }
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  return 0;
+}
+
+extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,
+                                 const int32_t* tab_off, const double* xs, const double* ys, const float* temps, float* out) {
+  if (!c || !out) return c ? fail(c, "calibrate_box: NULL out") : 1;
+  if (c->last_post_mode != UDA_POST_GLOBAL) return fail(c, "calibrate_box: needs the global post-process (uncertainty columns)");
+  const int bc = box_cols_of(c->model, UDA_POST_GLOBAL), cc = cls_cols_of(c->model, UDA_POST_GLOBAL);
+  if (col0 < 4 || col0 + 4 > bc || (col0 & 3)) return fail(c, "calibrate_box: columns %d..%d outside the %d box columns", col0, col0 + 3, bc);
+  const bool iso = mode >= UDA_CALIB_ISO_ALL;
+  if (mode < 0 || mode > UDA_CALIB_ISO_PERCLSCOO) return fail(c, "calibrate_box: unknown mode %d", mode);
+  if (!iso && !temps) return fail(c, "calibrate_box: temperature scaling needs temps");
+  if (relative && mode != UDA_CALIB_ISO_PERCLSCOO) return fail(c, "calibrate_box: the relative variant exists per class and coordinate only");
+  const int want = mode == UDA_CALIB_ISO_ALL ? 1 : (mode == UDA_CALIB_ISO_PERCOO ? 4 : 4 * c->model.num_classes);
+  if (iso && (n_tables != want || !tab_off || !xs || !ys))
+    return fail(c, "calibrate_box: mode %d needs %d tables, got %d", mode, want, n_tables);
+  if (int rc = settle_detections(c)) return rc;
+  for (int t = 0; iso && t < n_tables; ++t)
+    if (tab_off[t + 1] < tab_off[t]) return fail(c, "calibrate_box: table offsets must be non-decreasing");
+  const size_t rows = (size_t)c->last_n * c->model.max_output_size;
+  DevScratch s(c->device);
+  CalibArgs a{};
+  if (iso) {
+    const size_t tot = (size_t)tab_off[n_tables];
+    a.xs = s.upload(xs, tot, c->stream); a.ys = s.upload(ys, tot, c->stream); a.tab_off = s.upload(tab_off, (size_t)n_tables + 1, c->stream);
+  }
+  float* d_out = s.alloc<float>(rows * 4);
+  a.boxes = c->d_oboxes; a.classes = c->d_oclasses; a.out = d_out;
+  for (int j = 0; j < 4; ++j) a.temps[j] = temps ? temps[mode == UDA_CALIB_TS_ALL ? 0 : j] : 1.f;
+  a.rows = (int)rows; a.box_cols = bc; a.cls_cols = cc; a.col0 = col0;
+  a.mode = mode; a.relative = relative; a.n_tables = n_tables;
+  if (s.ok()) launch_calib(a, c->stream);
+  s.sync(c->stream);
+  s.download(out, d_out, rows * 4 * sizeof(float));
+  if (!s.ok()) return hip_failed(c, "calibrate_box", s.err);
+  return 0;
+}
+
+extern "C" int uda_calibrate_class(uda_ctx_t* c, int32_t mode, int32_t n_tables, const int32_t* tab_off, const double* xs,
+                                   const double* ys, const float* temps, int32_t draws, uint64_t seed, float* probs,
+                                   float* entropy, float* uncert) {
+  if (!c || !probs || !entropy) return c ? fail(c, "calibrate_class: NULL output") : 1;
+  const uda_model_t& m = c->model;
+  if (c->last_post_mode != UDA_POST_GLOBAL || !m.enable_softmax)
+    return fail(c, "calibrate_class: needs the logits of the global post-process (enable_softmax)");
+  if (mode < UDA_CLS_TS || mode > UDA_CLS_ISO_PERCLS) return fail(c, "calibrate_class: unknown mode %d", mode);
+  const int C = m.num_classes;
+  if (C > 128) return fail(c, "calibrate_class: more than 128 classes");
+  if (mode == UDA_CLS_TS && !temps) return fail(c, "calibrate_class: temperature scaling needs %d temperatures", C);
+  const int want = mode == UDA_CLS_ISO_ALL ? 1 : C;
+  if (mode != UDA_CLS_TS && (n_tables != want || !tab_off || !xs || !ys))
+    return fail(c, "calibrate_class: mode %d needs %d isotonic tables, got %d", mode, want, n_tables);
+  const int cc = cls_cols_of(m, UDA_POST_GLOBAL);
+  if (draws < 0 || draws > 1000) return fail(c, "calibrate_class: draws %d outside [0, 1000]", draws);
+  if (draws > 0 && cc != 1 + C)
+    return fail(c, "calibrate_class: sampling needs the MC std of every class logit (MC dropout on the class head, max_nms_inputs = 0)");
+  if (int rc = settle_detections(c)) return rc;
+  const size_t rows = (size_t)c->last_n * m.max_output_size;
+  for (int t = 0; mode != UDA_CLS_TS && t < n_tables; ++t)
+    if (tab_off[t + 1] <= tab_off[t]) return fail(c, "calibrate_class: every isotonic table needs at least one threshold");
+  DevScratch s(c->device);
+  ClsCalibArgs k{};
+  if (mode != UDA_CLS_TS) {
+    const size_t tot = (size_t)tab_off[n_tables];
+    k.xs = s.upload(xs, tot, c->stream); k.ys = s.upload(ys, tot, c->stream); k.tab_off = s.upload(tab_off, (size_t)n_tables + 1, c->stream);
+  } else {
+    k.temps = s.upload(temps, (size_t)C, c->stream);
+  }
+  float *d_p = s.alloc<float>(rows * C), *d_e = s.alloc<float>(rows), *d_u = uncert ? s.alloc<float>(rows * C) : nullptr;
+  k.logits = c->d_ologits; k.classes = c->d_oclasses; k.probs = d_p; k.entropy = d_e; k.uncert = d_u;
+  k.rows = (int)rows; k.C = C; k.cls_cols = cc; k.mode = mode; k.draws = draws; k.seed = seed;
+  if (s.ok()) launch_class_calib(k, c->stream);
+  s.sync(c->stream);
+  s.download(probs, d_p, rows * C * sizeof(float));
+  s.download(entropy, d_e, rows * sizeof(float));
+  if (uncert && draws > 0) s.download(uncert, d_u, rows * C * sizeof(float));
+  if (!s.ok()) return hip_failed(c, "calibrate_class", s.err);
+  if (uncert && draws <= 0) memset(uncert, 0, rows * C * sizeof(float));
+  return 0;
+}
+
+// CRC-32C (Castagnoli, reflected polynomial 0x82F63B78), slicing-by-8 on the host: the per-tensor checksum of TensorFlow
+// checkpoint bundles (ckpt_reader.py verifies every tensor it restores; a pure-Python table CRC manages ~1 MB/s).
+extern "C" uint32_t uda_crc32c(const void* data, uint64_t n, uint32_t crc) {
+  struct Tables {
+    uint32_t t[8][256];
+    Tables() {
+      for (uint32_t i = 0; i < 256; ++i) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0x82F63B78u : c >> 1;
+        t[0][i] = c;
+      }
+      for (uint32_t i = 0; i < 256; ++i)
+        for (int k = 1; k < 8; ++k) t[k][i] = (t[k - 1][i] >> 8) ^ t[0][t[k - 1][i] & 0xFFu];
+    }
+  };
+  static const Tables tables;          // function-local static: initialised once, thread-safe (C++11) - ctypes releases the GIL
+  const uint32_t (*T)[256] = tables.t;
+  const uint8_t* p = (const uint8_t*)data;
+  crc = ~crc;
+  while (n >= 8) {
+    uint64_t w;
+    memcpy(&w, p, 8);
+    w ^= crc;
+    crc = T[7][w & 0xFF] ^ T[6][(w >> 8) & 0xFF] ^ T[5][(w >> 16) & 0xFF] ^ T[4][(w >> 24) & 0xFF] ^
+          T[3][(w >> 32) & 0xFF] ^ T[2][(w >> 40) & 0xFF] ^ T[1][(w >> 48) & 0xFF] ^ T[0][(w >> 56) & 0xFF];
+    p += 8; n -= 8;
+  }
+  while (n--) crc = T[0][(crc ^ *p++) & 0xFFu] ^ (crc >> 8);
+  return ~crc;
+}
+
+// ------------------------------------------------------------------------------------ standalone NMS
+extern "C" int uda_nms(uda_ctx_t* c, const float* boxes, const float* scores, int32_t n_img, int32_t k,
+                       int32_t max_out, float iou_thresh, float score_thresh, float soft_sigma, int32_t pad,
+                       int32_t* idx, float* out_scores, int32_t* valid) {
+  if (!c || !boxes || !scores || !idx || !out_scores || !valid) return c ? fail(c, "uda_nms: NULL argument") : 1;
+  if (n_img < 1 || k < 0 || max_out < 1 || max_out > 128) return fail(c, "uda_nms: bad sizes (max_out must be in [1, 128])");
+  const size_t NK = (size_t)n_img * (k ? k : 1), NM = (size_t)n_img * max_out;
+  DevScratch s(c->device);
+  float* d_boxes = k ? s.upload(boxes, NK * 4, c->stream) : s.alloc<float>(NK * 4);
+  float* d_scores = k ? s.upload(scores, NK, c->stream) : s.alloc<float>(NK);
+  NmsArgs a{};
+  a.boxes = d_boxes; a.stale = s.alloc<float>(NK); a.tent = s.alloc<float>(NK); a.ub = s.alloc<float>(NK);
+  a.ev = s.alloc<int32_t>(NK); a.begin = s.alloc<int32_t>(NK);
+  a.sel_idx = s.alloc<int32_t>(NM); a.sel_score = s.alloc<float>(NM); a.sel_box = s.alloc<float>(NM * 4);
+  a.bound_key = s.alloc<unsigned long long>(NM); a.win_key = s.alloc<unsigned long long>(NM);
+  a.nsel = s.alloc<int32_t>((size_t)n_img); a.done = s.alloc<int32_t>((size_t)n_img);
+  a.n_img = n_img; a.K = k; a.M = max_out;
+  a.segs = 1; a.classes = nullptr;
+  nms_params(a, iou_thresh, score_thresh, soft_sigma);
+  struct Prefix {          // the workspace of the score-prefix NMS, as the handle's own: alloc_prefix_ws / free_prefix_ws
+    uda_ctx::PrefixWs ws;
+    ~Prefix() { free_prefix_ws(ws); }
+  } owned;
+  uda_ctx::PrefixWs& pw = owned.ws;
+  const int lp = prefix_target();
+  if (s.ok() && lp > 0 && k > solo_limit() && k > 2 * lp) s.err = alloc_prefix_ws(pw, (size_t)n_img, 2 * lp, (size_t)max_out);
+  if (!s.ok()) return hip_failed(c, "uda_nms", s.err);
+  bool prefix = false;
+  {
+    ProfScope ps(c, 17);
+    NmsCoop coop;
+    if ((size_t)n_img * nms_coop_slot_words(max_out) <= (size_t)c->model.max_images * nms_coop_slot_words(c->model.max_output_size) && !c->coop_off) { coop.bar = c->d_coop_bar; coop.err = c->d_coop_err; coop.used = &c->coop_used; coop.not_launched = &c->coop_not_launched; }
+    if (k > 0) prefix = run_nms(a, d_scores, max_out, c->stream, pw.Lcap ? &pw : nullptr, 0, coop);
+    else launch_nms_init(a, d_scores, c->stream);
+  }
+  s.sync(c->stream);
+  if (prefix) {            // problems whose prefix was not sufficient: the full candidate set, one problem at a time
+    std::vector<int32_t> bad((size_t)n_img);
+    s.download(bad.data(), pw.bad, (size_t)n_img * sizeof(int32_t));
+    for (int p = 0; s.ok() && p < n_img; ++p) {
+      if (!bad[(size_t)p]) continue;
+      const size_t pk = (size_t)p * k, pm = (size_t)p * max_out;
+      NmsArgs f = a;
+      f.boxes += pk * 4; f.stale += pk; f.begin += pk; f.tent += pk; f.ub += pk; f.ev += pk;
+      f.sel_idx += pm; f.sel_score += pm; f.sel_box += pm * 4; f.bound_key += pm; f.win_key += pm;
+      f.nsel += p; f.done += p; f.n_img = 1;
+      ProfScope ps(c, 17);
+      NmsCoop coop;
+      if (!c->coop_off) { coop.bar = c->d_coop_bar; coop.err = c->d_coop_err; coop.used = &c->coop_used; coop.not_launched = &c->coop_not_launched; }
+      run_nms(f, d_scores + pk, max_out, c->stream, nullptr, 0, coop);
+      ++c->pfx_fallbacks;
+    }
+    s.sync(c->stream);
+  }
+  if (s.ok() && c->coop_used) {
+    c->coop_used = false;
+    int e = 0;
+    hipMemcpy(&e, c->d_coop_err, sizeof(int), hipMemcpyDeviceToHost);
+    if (e) {           // barrier time-out: redo with the two-launch version (see finish_post)
+      hipMemset(c->d_coop_err, 0, sizeof(int));
+      c->coop_off = true;
+      ++c->coop_fallbacks;
+      fprintf(stderr, "[uda] cooperative NMS: grid barrier timed out; falling back to two launches per epoch\n");
+      run_nms(a, d_scores, max_out, c->stream);
+      s.sync(c->stream);
+    }
+  }
+  s.download(valid, a.nsel, n_img * sizeof(int32_t));
+  s.download(idx, a.sel_idx, NM * sizeof(int32_t));
+  s.download(out_scores, a.sel_score, NM * sizeof(float));
+  (void)pad;  // slots >= valid already hold index 0 / score 0.0 (the padded form); callers slice when pad == 0
+  if (!s.ok()) return hip_failed(c, "uda_nms", s.err);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------ standalone 1x1 conv
+extern "C" int uda_debug_pw(int32_t device, const float* in, const float* w, const float* bias, const float* bn_scale,
+                            const float* bn_shift, const float* se, const float* mask, const float* res,
+                            int32_t rows, int32_t in_div, int32_t hw, int32_t cin, int32_t cout, int32_t act,
+                            int32_t terms, int32_t reps, float* out, float* avg_ms) {
+  if (!in || !w || !out || rows < 1 || in_div < 1 || rows % in_div || hw < 1 || cin < 4 || cin % 4 || cout < 1)
+    return fail(nullptr, "uda_debug_pw: bad argument");
+  if (terms != 0 && terms != 1 && terms != 3 && terms != 6 && terms != 16)
+    return fail(nullptr, "uda_debug_pw: terms must be 0 (f32 MFMA), 1 (fp16 x1), 3 (bf16 x2), 6 (bf16 x3) or 16 (fp16 x2)");
+  const size_t rows_in = rows / in_div;
+  DevScratch s(device);
+  PwArgs a{};
+  a.in = s.upload(in, rows_in * hw * cin);
+  a.w = s.upload(w, (size_t)cin * cout);
+  a.bias = s.upload(bias, cout);
+  a.bn_scale = s.upload(bn_scale, cout);
+  a.bn_shift = s.upload(bn_shift, cout);
+  a.se = s.upload(se, rows_in * cin);
+  a.mask = s.upload(mask, (size_t)rows * cout);
+  a.res = s.upload(res, (size_t)rows * hw * cout);
+  float* d_out = s.alloc<float>((size_t)rows * hw * cout);
+  a.out = d_out;
+  a.HW = hw; a.Cin = cin; a.Cout = cout; a.in_div = in_div; a.res_div = 1; a.se_div = in_div; a.act = act;
+  unsigned* d_oor = nullptr;
+  if (terms) {
+    const int scheme = terms == 6 ? UDA_SPLIT_BF16X3 : (terms == 16 ? UDA_SPLIT_F16X2 : (terms == 1 ? UDA_SPLIT_F16X1 : UDA_SPLIT_BF16X2));
+    // (as uda_create packs a 1x1 conv: fp16 pieces, one or two, carry the power-of-two weight scale)
+    const float scale = uda_split_f16(scheme) ? split_weight_scale(w, (size_t)cin * cout) : 1.0f;
+    std::vector<uint16_t> packed(pwb_packed_elems(cin, cout, scheme));
+    pwb_pack_weights(w, cin, cout, scheme, packed.data(), scale);
+    a.wsplit = s.upload(packed.data(), packed.size());
+    a.wparts = scheme;
+    a.wunscale = 1.0f / scale;
+    a.oor = d_oor = s.alloc<unsigned>(1);
+    s.zero(d_oor, sizeof(unsigned));
+  }
+  hipStream_t st = s.stream();
+  hipEvent_t e0 = s.event(), e1 = s.event();
+  float ms = 0;
+  if (s.ok()) {
+    auto go = [&]() { if (terms) launch_pwb(a, rows, st); else launch_pw(a, rows, st); };
+    go();                                   // warm-up (and the result that is read back)
+    hipEventRecord(e0, st);
+    for (int i = 0; i < reps; ++i) go();
+    hipEventRecord(e1, st);
+    s.sync(st);
+    hipEventElapsedTime(&ms, e0, e1);
+  }
+  if (avg_ms) *avg_ms = reps > 0 ? ms / reps : 0.f;
+  s.download(out, d_out, (size_t)rows * hw * cout * sizeof(float));
+  unsigned oor = 0;
+  if (d_oor) s.download(&oor, d_oor, sizeof(unsigned));
+  if (!s.ok()) return hip_failed(nullptr, "uda_debug_pw", s.err);
+  if (oor) return fail(nullptr, "uda_debug_pw: an input above 65504 cannot be split into fp16 pieces (terms = %d)", terms);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------ numpy NMS family (a18)
+template <typename T>
+static int run_nmsnp(const char* who, int device, const std::vector<T>& dets, const std::vector<int32_t>& off, int method, double iou_thr,
+                     double sigma, double score_thr, std::vector<T>& out, std::vector<int32_t>& n_out) {
+  const int problems = (int)off.size() - 1;
+  const size_t total = (size_t)off.back();
+  out.assign(total * 5, (T)0);
+  n_out.assign(problems > 0 ? problems : 0, 0);
+  if (problems <= 0 || total == 0) return 0;
+  DevScratch s(device);
+  NmsNpArgs<T> a{};
+  a.dets = s.upload(dets.data(), total * 5); a.score = s.alloc<T>(total); a.out = s.alloc<T>(total * 5);
+  a.off = s.upload(off.data(), off.size()); a.state = s.alloc<int32_t>(total); a.n_out = s.alloc<int32_t>((size_t)problems);
+  a.method = method; a.iou_thr = (T)iou_thr; a.sigma = (T)sigma; a.score_thr = (T)score_thr;
+  if (s.ok()) launch_nmsnp<T>(a, problems, nullptr);
+  s.sync();
+  s.download(out.data(), a.out, total * 5 * sizeof(T));
+  s.download(n_out.data(), a.n_out, (size_t)problems * sizeof(int32_t));
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  return 0;
+}
+
+// rows sorted by score, descending (what `dets[:, 4].argsort()[::-1]` yields for distinct scores; ties: later index first)
+template <typename T>
+static void sort_desc(std::vector<T>& dets, int begin, int n) {
+  std::vector<int> idx(n);
+  std::iota(idx.begin(), idx.end(), 0);
+  std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) {
+    const T sx = dets[(size_t)(begin + x) * 5 + 4], sy = dets[(size_t)(begin + y) * 5 + 4];
+    return sx > sy || (sx == sy && x > y);
+  });
+  std::vector<T> tmp((size_t)n * 5);
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < 5; ++k) tmp[(size_t)i * 5 + k] = dets[(size_t)(begin + idx[i]) * 5 + k];
+  std::copy(tmp.begin(), tmp.end(), dets.begin() + (size_t)begin * 5);
+}
+
+extern "C" int uda_nms_np(int32_t device, const double* dets, int32_t n, int32_t method, double iou_thresh, double sigma,
+                          double score_thresh, double* out, int32_t* n_out) {
+  if (!dets || !out || !n_out || n < 0 || method < 0 || method > 3) return fail(nullptr, "uda_nms_np: bad argument");
+  std::vector<double> d(dets, dets + (size_t)n * 5), o;
+  std::vector<int32_t> off = {0, n}, no;
+  if (method <= 1) sort_desc(d, 0, n);
+  const int rc = run_nmsnp<double>("uda_nms_np", device, d, off, method, iou_thresh, sigma, score_thresh, o, no);
+  if (rc) return rc;
+  *n_out = n ? no[0] : 0;
+  std::copy(o.begin(), o.begin() + (size_t)*n_out * 5, out);
+  return 0;
+}
+
+extern "C" int uda_per_class_nms_np(int32_t device, const float* boxes, const float* scores, const int32_t* classes, int32_t k,
+                                    float image_id, float image_scale, int32_t num_classes, int32_t max_boxes, int32_t method,
+                                    float iou_thresh, float sigma, float score_thresh, float* out) {
+  if (!boxes || !scores || !classes || !out || k < 0 || num_classes < 1 || max_boxes < 1 || method < 0 || method > 3)
+    return fail(nullptr, "uda_per_class_nms_np: bad argument");
+  std::vector<float> d;
+  std::vector<int32_t> off = {0}, cls_of;
+  for (int c = 0; c < num_classes; ++c) {
+    const int begin = off.back();
+    int n = 0;
+    for (int i = 0; i < k; ++i)
+      if (classes[i] == c) {           // boxes arrive y1,x1,y2,x2 -> x1,y1,x2,y2 (nms_np.py:234)
+        d.insert(d.end(), {boxes[i * 4 + 1], boxes[i * 4 + 0], boxes[i * 4 + 3], boxes[i * 4 + 2], scores[i]});
+        ++n;
+      }
+    if (!n) continue;
+    if (method <= 1) sort_desc(d, begin, n);
+    off.push_back(begin + n);
+    cls_of.push_back(c);
+  }
+  std::vector<float> o;
+  std::vector<int32_t> no;
+  const int rc = run_nmsnp<float>("uda_per_class_nms_np", device, d, off, method, iou_thresh, sigma, score_thresh, o, no);
+  if (rc) return rc;
+  struct Row { float v[7]; };
+  std::vector<Row> rows;
+  for (size_t p = 0; p + 1 < off.size(); ++p)
+    for (int i = 0; i < no[p]; ++i) {
+      const float* r = o.data() + ((size_t)off[p] + i) * 5;
+      rows.push_back(Row{{image_id, r[0], r[1], r[2], r[3], r[4], (float)(cls_of[p] + 1)}});
+    }
+  std::stable_sort(rows.begin(), rows.end(), [](const Row& x, const Row& y) { return x.v[5] > y.v[5]; });
+  for (int i = 0; i < max_boxes; ++i) {
+    float* dst = out + (size_t)i * 7;
+    if (i < (int)rows.size()) {
+      for (int j = 0; j < 7; ++j) dst[j] = rows[i].v[j];
+    } else {                           // dummy rows: score -1e5 (nms_np.py:256-274)
+      for (int j = 0; j < 7; ++j) dst[j] = 0.f;
+      dst[0] = image_id;
+      dst[5] = -1e5f;
+    }
+    for (int j = 1; j < 5; ++j) dst[j] *= image_scale;
+  }
+  return 0;
+}
