@@ -20,6 +20,8 @@
  *                            (utils_extra.py:44-64; validate_model.py:314-470, calibrate_model.py:133-190)
  *   uda_score_images      <- ActiveLearning.score_image's per-detection numbers and per-image mean / max
  *                            (active_learning_loop.py:528-733)
+ *   uda_pseudo_rows       <- STAC.score_image's per-detection value, candidate rows and min / max (pseudo-labelling)
+ *                            (SSL_stac.py:302-642)
  *   uda_eval_match        <- COCOeval_all.evaluateImg for the detections and ground truth EvaluationMetric.update_state
  *                            collects (custom_cocoeval.py:265-349; coco_metric.py:219-283)
  *   uda_thr_objective_np  <- roc_metrics for the candidates of UncertOptimal._extract_optimal_params
@@ -400,6 +402,52 @@ int uda_score_images_np_f32(int32_t device, const uda_score_desc_t* desc, float 
                             const float* mcclass, int32_t n, int32_t M, int32_t num_classes, int32_t mcclass_cols,
                             double* components, int32_t* count, int32_t* class_counts);
 
+/* Pseudo-labelling rows: the first half of the semi-supervised teacher's selection (STAC.score_image, SSL_stac.py:302-642, on the
+ * lines Infer.iterate_infer wrote with min_score 0.1) - per detection above min_score ONE value v from a uda_score_desc_t, the
+ * candidate rows and the per-image min / max of v - done on the detections RESIDENT in the handle after a global post-process.
+ * The dataset-wide min-max normalisation, the final rule and the writers are the caller's (pseudo_labels.py).
+ *   kept         score > min_score (the writer's filter; padded rows score 0); only the first max_rows kept rows of an image, in
+ *                rank order, take part (the reference's max_detections_per_image = 99)
+ *   v            invert 0: the descriptor's one component (terms, transforms, float32 nan_to_num exactly as uda_score_images;
+ *                reduce_mean is not read); invert 1: 1.0 / (((c0 + c1) [+ c2]) / n_comp) over its 2 or 3 components
+ *                (1 / np.mean([...], axis=0), SSL_stac.py:575-606).  IEEE throughout: a zero mean gives inf
+ *   candidate    gate 0: det_score > tau (filter_based_on_sigmoid); gate 1: v > tau (the single-column branch); in float64
+ *   min / max    over the rows that take part, candidates or not; NaN is ignored, +-inf take part; (+inf, -inf) where no row does
+ * The order is fixed and nothing is accumulated with float atomics: equal values give bit-identical records on every entry point. */
+typedef struct uda_pseudo_record {
+  int32_t image, row;   /* image of the run, detection row */
+  float box[4];         /* y1 x1 y2 x2 as stored */
+  float det_score;
+  int32_t cls;          /* class id 1..num_classes */
+  double v;
+} uda_pseudo_record_t;  /* 40 bytes */
+/*   uda_pseudo_rows        queues the softmax / entropy kernel when a component reads ENTROPY, then the row kernel and the packing
+ *                          kernel, on the handle's stream.  Refuses what uda_score_images refuses, and max_rows < 1, tau < 0 (or
+ *                          NaN), invert with one component, no invert with several, gate 1 with invert 1.
+ *   uda_pseudo_rows_shape  n (images of the run) and K = the sum of cand.  The first reader of a run waits for it and brings the
+ *                          pack's head over in one copy: minmax, kept, cand and the error flag, 24 n + 8 bytes.
+ *   uda_get_pseudo_rows    records [K] in (image, rank) order (n_records must be K), minmax [n, 2] float64, kept [n] int32 rows above
+ *                          min_score (before the cap), cand [n] int32; any pointer may be NULL.  The K used records, which lie
+ *                          behind the head, come over in one copy of 40 K bytes when `records` is given (the room for
+ *                          n * min(M, max_rows) records is never copied).  A candidate whose class id is not one of
+ *                          1..num_classes is an error. */
+int uda_pseudo_rows(uda_ctx_t* ctx, const uda_score_desc_t* desc, int32_t invert, int32_t gate, float min_score, double tau,
+                    int32_t max_rows);
+int uda_pseudo_rows_shape(uda_ctx_t* ctx, int32_t* n, int64_t* K);
+int uda_get_pseudo_rows(uda_ctx_t* ctx, void* records, int64_t n_records, double* minmax, int32_t* kept, int32_t* cand);
+/* The same without a handle: the argument list of uda_score_images_np / _np_f32, then the five scalars and the outputs.  records
+ * holds room for n * min(M, max_rows) records; *n_records receives K. */
+int uda_pseudo_rows_np(int32_t device, const uda_score_desc_t* desc, double min_score, const double* boxes, const double* scores,
+                       const double* classes, const double* entropy, const double* albox, const double* mcbox,
+                       const double* mcclass, int32_t n, int32_t M, int32_t num_classes, int32_t mcclass_cols, int32_t invert,
+                       int32_t gate, double tau, int32_t max_rows, void* records, int64_t* n_records, double* minmax,
+                       int32_t* kept, int32_t* cand);
+int uda_pseudo_rows_np_f32(int32_t device, const uda_score_desc_t* desc, float min_score, const float* boxes, const float* scores,
+                           const float* classes, const float* entropy, const float* albox, const float* mcbox,
+                           const float* mcclass, int32_t n, int32_t M, int32_t num_classes, int32_t mcclass_cols, int32_t invert,
+                           int32_t gate, double tau, int32_t max_rows, void* records, int64_t* n_records, double* minmax,
+                           int32_t* kept, int32_t* cand);
+
 /* COCO evaluation: the matching half of the metric eval.py and the training-time COCOCallback hand their detections to
  * (coco_metric.EvaluationMetric, coco_metric.py:59-283, which runs pycocotools' COCOeval and custom_cocoeval.COCOeval_all) -
  * evaluateImg (custom_cocoeval.py:265-349) for every (image, category, area range, IoU threshold) at maxDets[-1] = 100 - done on
@@ -584,7 +632,8 @@ int uda_per_class_nms_np(int32_t device, const float* boxes, const float* scores
 
 /* Per-op-kind device timing with HIP events recorded on the handle's stream.
  * kind_mask: bit (1 << uda_op_kind) selects op kinds; bit 16 post-process aggregate, bit 17 NMS, bit 19 the score kernel of
- * uda_score_images (with its softmax / entropy kernel when ENTROPY is read), bit 20 the match kernel of uda_eval_match. */
+ * uda_score_images (with its softmax / entropy kernel when ENTROPY is read), bit 20 the match kernel of uda_eval_match, bit 21
+ * the row and packing kernels of uda_pseudo_rows (with the softmax / entropy kernel when ENTROPY is read). */
 int uda_profile_enable(uda_ctx_t* ctx, uint32_t kind_mask);
 int uda_profile_read(uda_ctx_t* ctx, int32_t kind, double* total_ms, int64_t* launches, int32_t reset);
 

@@ -9,5 +9,6 @@ Modules:
   capi            ctypes binding of include/uda_hip.h (csrc/libuda_hip.so)
   infer_lib       ServingDriver-shaped boundary (serve / predict / benchmark)
   dist            image sharding + detection gather (torch.distributed / RCCL)
+  pseudo_labels   the STAC teacher's selection: candidate rows from the device, dataset-wide rule, KITTI / BDD pseudo ground truth
   thresholding    failure-recognition weights and threshold from validation rows (roc_objective, UncertOptimal, autolabel_verdict)
 """

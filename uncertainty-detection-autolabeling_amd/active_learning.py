@@ -82,43 +82,47 @@ def emitted_sources(params):
     return out
 
 
-def resolve_strategy(strategy, params, opt_params=None):
-    """`ActiveLearning.scoring_strategy` -> `Strategy`, branch for branch in the order of score_image (:544-708): `combo`;
-    `alluncert` | `sota`; `epuncert`; `ental`; otherwise the key add_mode + strategy.split("_")[-1] of a file line.  All tests
-    are substring tests, as in the reference.  params: the model parameters, which decide what a line would contain (a dict
-    of emitted source names -> anything is taken as that set itself).  A branch that reads a column the model does not emit
-    raises ValueError (the reference: KeyError); in the last branch a key the line would not contain falls back to det_score
-    (:707-708), and a key it would contain but that holds no uncertainty number (logits, probab) raises ValueError."""
-    s = str(strategy)
-    has = (set(params) | {"det_score"}) if set(params) <= set(SOURCES) else emitted_sources(params)
-    calib = "calib" in s
-    box_mode = BOX_CALIB_MODE if calib else ""
-    cls_mode = CLASS_CALIB_MODE if calib else ""
-    columns = {}
+def _emitted(params):
+    """The source names a model emits: params are the model parameters, or a dict of source names -> anything."""
+    return (set(params) | {"det_score"}) if set(params) <= set(SOURCES) else emitted_sources(params)
 
-    def term(src, tr, w=1.0):
-        if src not in has:
-            raise ValueError("strategy %r reads %s, which this model does not emit" % (s, src))
+
+class _Terms:
+    """Builds (source, transform, weight) terms for a strategy string and notes the column key of every source read: the part
+    of the grammar the active-learning loop and the pseudo-labelling teacher (pseudo_labels.resolve_selection) share."""
+
+    def __init__(self, s, has):
+        self.s, self.has, self.calib = s, has, "calib" in s
+        self.box_mode = BOX_CALIB_MODE if self.calib else ""
+        self.cls_mode = CLASS_CALIB_MODE if self.calib else ""
+        self.columns = {}
+
+    def term(self, src, tr, w=1.0):
+        if src not in self.has:
+            raise ValueError("strategy %r reads %s, which this model does not emit" % (self.s, src))
         if src != "det_score":
-            columns[src] = (box_mode if src in ("albox", "mcbox") else cls_mode) + src
+            self.columns[src] = (self.box_mode if src in ("albox", "mcbox") else self.cls_mode) + src
         return (src, tr, float(w))
 
-    multi = [k for k in ("alluncert", "sota", "epuncert", "ental") if k in s]
-    if "combo" in s:
-        if multi:
-            raise ValueError("strategy %r: `combo` beside %s has no meaning in the reference (its per-image accumulator "
-                             "is sized for the latter and filled by the former)" % (s, multi[0]))
+    def combo(self, opt_params):
         if opt_params is None or len(opt_params) < 2:
-            raise ValueError("strategy %r needs opt_params = (entropy weight, aleatoric weight)" % s)
-        comps = [[term("entropy", "scalar", opt_params[0]), term("albox", "rel_mean", opt_params[1])]]
-    elif "alluncert" in s or "sota" in s:
-        comps = [[term("mcbox", "rel_mean")], [term("albox", "rel_mean")], [term("mcclass", "mean")]]
-    elif "epuncert" in s:
-        comps = [[term("mcbox", "rel_mean")], [term("mcclass", "mean")]]
-    elif "ental" in s:
-        comps = [[term("albox", "rel_mean")], [term("entropy", "scalar")]]
-    else:
-        if calib:
+            raise ValueError("strategy %r needs opt_params = (entropy weight, aleatoric weight)" % self.s)
+        return [[self.term("entropy", "scalar", opt_params[0]), self.term("albox", "rel_mean", opt_params[1])]]
+
+    def alluncert(self):
+        return [[self.term("mcbox", "rel_mean")], [self.term("albox", "rel_mean")], [self.term("mcclass", "mean")]]
+
+    def epuncert(self):
+        return [[self.term("mcbox", "rel_mean")], [self.term("mcclass", "mean")]]
+
+    def ental(self):
+        return [[self.term("albox", "rel_mean")], [self.term("entropy", "scalar")]]
+
+    def single(self):
+        """The last branch of both loops: the key add_mode + strategy.split("_")[-1] of a file line, det_score when the line
+        would not hold it."""
+        s, has = self.s, self.has
+        if self.calib:
             add_mode = BOX_CALIB_MODE if "box" in s else CLASS_CALIB_MODE
         else:
             add_mode = "uncalib_" if ("box" in s or "class" in s) else ""
@@ -140,14 +144,41 @@ def resolve_strategy(strategy, params, opt_params=None):
                 tr = "rel_mean" if ("box" in s and "norm" in s) else "mean"
             if tr == "rel_mean" and src == "mcclass":
                 raise ValueError("strategy %r relativizes %s, which has no box shape" % (s, key))
-            comps = [[(src, tr, 1.0)]]
             if src != "det_score":
-                columns[src] = mode + src
-        elif "entropy" in has and key in _UNSCORED:
+                self.columns[src] = mode + src
+            return [[(src, tr, 1.0)]]
+        if "entropy" in has and key in _UNSCORED:
             # a key the writer emits (or would, given calibrators) that this path does not turn into a score
             raise ValueError("strategy %r selects the key %r of a prediction line, which this path does not score" % (s, key))
-        else:
-            comps = [[("det_score", "scalar", 1.0)]]           # the reference's fallback (:707-708)
+        return [[("det_score", "scalar", 1.0)]]               # the reference's fallback (:707-708)
+
+    def calibrated(self):
+        return any(v.startswith((BOX_CALIB_MODE, CLASS_CALIB_MODE)) for v in self.columns.values())
+
+
+def resolve_strategy(strategy, params, opt_params=None):
+    """`ActiveLearning.scoring_strategy` -> `Strategy`, branch for branch in the order of score_image (:544-708): `combo`;
+    `alluncert` | `sota`; `epuncert`; `ental`; otherwise the key add_mode + strategy.split("_")[-1] of a file line.  All tests
+    are substring tests, as in the reference.  params: the model parameters, which decide what a line would contain (a dict
+    of emitted source names -> anything is taken as that set itself).  A branch that reads a column the model does not emit
+    raises ValueError (the reference: KeyError); in the last branch a key the line would not contain falls back to det_score
+    (:707-708), and a key it would contain but that holds no uncertainty number (logits, probab) raises ValueError."""
+    s = str(strategy)
+    t = _Terms(s, _emitted(params))
+    multi = [k for k in ("alluncert", "sota", "epuncert", "ental") if k in s]
+    if "combo" in s:
+        if multi:
+            raise ValueError("strategy %r: `combo` beside %s has no meaning in the reference (its per-image accumulator "
+                             "is sized for the latter and filled by the former)" % (s, multi[0]))
+        comps = t.combo(opt_params)
+    elif "alluncert" in s or "sota" in s:
+        comps = t.alluncert()
+    elif "epuncert" in s:
+        comps = t.epuncert()
+    elif "ental" in s:
+        comps = t.ental()
+    else:
+        comps = t.single()
     combine = None
     if len(comps) > 1:
         if "highep_lowal" in s:
@@ -158,8 +189,7 @@ def resolve_strategy(strategy, params, opt_params=None):
             combine = "sota"
         else:
             combine = "sum"
-    calibrated = any(v.startswith((BOX_CALIB_MODE, CLASS_CALIB_MODE)) for v in columns.values())
-    return Strategy(s, comps, "mean" in s, columns, calibrated, combine)
+    return Strategy(s, comps, "mean" in s, t.columns, t.calibrated(), combine)
 
 
 def default_min_score(params, average_score=0, ssl=False):

@@ -30,7 +30,7 @@ ASSIGN_KEEP_VALIDATE, ASSIGN_KEEP_CALIBRATE = 0, 1
 SCORE_ENTROPY, SCORE_DET_SCORE, SCORE_ALBOX, SCORE_MCBOX, SCORE_MCCLASS = 0, 1, 2, 3, 4
 SCORE_SCALAR, SCORE_MEAN, SCORE_REL_MEAN = 0, 1, 2
 SCORE_MAX_COMP = 3
-PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS, PROF_SCORE, PROF_EVAL = 16, 17, 18, 19, 20
+PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS, PROF_SCORE, PROF_EVAL, PROF_PSEUDO = 16, 17, 18, 19, 20, 21
 EVAL_MAX_GT, EVAL_MAX_THRS = 256, 32
 THR_MAX_N, THR_MAX_U, THR_MAX_THRS, THR_MAX_P, THR_MAX_G = 262144, 4, 32, 65536, 8192
 
@@ -134,6 +134,15 @@ _SIGNATURES = {
                                       C.c_int32, C.c_int32, _P, _P, _P]),
     "uda_score_images_np_f32": (C.c_int, [C.c_int32, C.POINTER(ScoreDesc), C.c_float, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_int32, _P, _P, _P]),
+    "uda_pseudo_rows": (C.c_int, [_P, C.POINTER(ScoreDesc), C.c_int32, C.c_int32, C.c_float, C.c_double, C.c_int32]),
+    "uda_pseudo_rows_shape": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "uda_get_pseudo_rows": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "uda_pseudo_rows_np": (C.c_int, [C.c_int32, C.POINTER(ScoreDesc), C.c_double, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(C.c_int64),
+                                     _P, _P, _P]),
+    "uda_pseudo_rows_np_f32": (C.c_int, [C.c_int32, C.POINTER(ScoreDesc), C.c_float, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(C.c_int64),
+                                         _P, _P, _P]),
     "uda_set_eval_ground_truth": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "uda_eval_match": (C.c_int, [_P, _P, C.c_int32]),
     "uda_get_eval_records": (C.c_int, [_P, _P, _P, _P]),

@@ -398,6 +398,15 @@ __device__ double score_term(const ScoreArgs<T>& a, size_t row, int source, int 
   return sum_np(v, 4) / 4.0;
 }
 
+// component k of a row: w0 * term0 (+ w1 * term1) - the one place both the image scores and the pseudo-labelling rows build it
+template <typename T>
+__device__ __forceinline__ double score_component(const ScoreArgs<T>& a, size_t row, int k) {
+  const uda_score_term_t* t = a.desc.term[k];
+  double v = t[0].weight * score_term(a, row, t[0].source, t[0].transform);
+  if (a.desc.n_terms[k] > 1) v = v + t[1].weight * score_term(a, row, t[1].source, t[1].transform);
+  return v;
+}
+
 __device__ __forceinline__ double max_np(double a, double b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
 
 template <typename T>
@@ -423,9 +432,7 @@ __global__ __launch_bounds__(256) void score_images_kernel(ScoreArgs<T> a) {
 #pragma unroll
     for (int k = 0; k < UDA_SCORE_MAX_COMP; ++k) {         // (unrolled: acc stays in registers)
       if (k >= nc) break;
-      const uda_score_term_t* t = a.desc.term[k];
-      double v = t[0].weight * score_term(a, row, t[0].source, t[0].transform);
-      if (a.desc.n_terms[k] > 1) v = v + t[1].weight * score_term(a, row, t[1].source, t[1].transform);
+      const double v = score_component(a, row, k);
       acc[k] = mean ? acc[k] + v : max_np(acc[k], v);
     }
   }
@@ -461,6 +468,116 @@ static void launch_score_images_t(const ScoreArgs<T>& a, hipStream_t s) {
 }
 void launch_score_images(const ScoreArgs<float>& a, hipStream_t s) { launch_score_images_t(a, s); }
 void launch_score_images(const ScoreArgs<double>& a, hipStream_t s) { launch_score_images_t(a, s); }
+
+// ------------------------------------------------------------------------------------ pseudo-labelling rows
+// STAC.score_image (SSL_stac.py:302-642) up to its dataset-wide normalisation, without the text file in between: the per-row form
+// of the image scores above.  One block of 256 threads per image walks the M rows in chunks of 256, row r of a chunk on thread r.
+//   kept         score > min_score in the input type (the writer's filter); its rank among the image's kept rows is an exclusive
+//                scan of the flags: ballot + popcount inside a wave, the four wave totals through LDS, a running base over chunks
+//   takes part   rank < max_rows (the reference's [:99])
+//   v            the descriptor's one component, or 1 / (((c0 + c1) [+ c2]) / n_comp) - np.mean over axis 0, then the divide
+//   candidate    det_score > tau (gate 0) or v > tau (gate 1), float64; ranked by a second scan of the same shape
+// Two barriers per chunk are enough: a chunk's kept totals are read between its two barriers and written again only after the
+// second, its candidate totals are read before the next chunk's first barrier and written again only after it.  min / max over the rows that
+// take part: b < a / b > a never takes a NaN b (the reference's running min(global_min, item)); a thread's rows ascending, an xor
+// butterfly in the wave, the waves in wave order.  No float atomics.  The candidates go to the image's `cap` slots; the packing
+// kernel moves them behind the candidates of the images before (the order the reference appends in).
+template <typename T>
+__global__ __launch_bounds__(256) void pseudo_rows_kernel(PseudoArgs<T> a) {
+  __shared__ int kept_tot[4], cand_tot[4];
+  __shared__ double wave_min[4], wave_max[4];
+  const int i = blockIdx.x, M = a.s.M, C = a.s.C, nc = a.s.desc.n_comp;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int kept_base = 0, cand_base = 0;
+  double vmin = (double)__builtin_inff(), vmax = -(double)__builtin_inff();
+  for (int r0 = 0; r0 < M; r0 += 256) {      // (uniform trip count: every thread reaches the ballots and barriers)
+    const int r = r0 + (int)threadIdx.x;
+    const size_t row = (size_t)i * M + (r < M ? r : 0);
+    const bool kept = r < M && a.s.scores[row] > a.s.min_score;
+    const unsigned long long km = __ballot(kept);
+    if (lane == 0) kept_tot[wave] = __popcll(km);
+    __syncthreads();
+    int rank = kept_base + __popcll(km & below);
+    for (int w = 0; w < wave; ++w) rank += kept_tot[w];
+    kept_base += (kept_tot[0] + kept_tot[1]) + (kept_tot[2] + kept_tot[3]);
+    const bool part = kept && rank < a.max_rows;
+    double v = 0.0;
+    bool cand = false;
+    if (part) {
+      if (a.invert) {
+        double sum = score_component(a.s, row, 0) + score_component(a.s, row, 1);
+        if (nc > 2) sum = sum + score_component(a.s, row, 2);
+        v = 1.0 / (sum / (double)nc);
+      } else {
+        v = score_component(a.s, row, 0);
+      }
+      vmin = v < vmin ? v : vmin;
+      vmax = v > vmax ? v : vmax;
+      cand = a.gate ? v > a.tau : (double)a.s.scores[row] > a.tau;
+    }
+    const unsigned long long cm = __ballot(cand);
+    if (lane == 0) cand_tot[wave] = __popcll(cm);
+    __syncthreads();
+    int slot = cand_base + __popcll(cm & below);
+    for (int w = 0; w < wave; ++w) slot += cand_tot[w];
+    cand_base += (cand_tot[0] + cand_tot[1]) + (cand_tot[2] + cand_tot[3]);
+    if (cand && slot < a.cap) {                              // (slot <= rank < min(M, max_rows) = cap: always true)
+      const double cid = (double)a.s.classes[row * a.s.cls_stride];
+      const int ci = cid >= 1.0 && cid <= (double)C ? (int)cid : 0;
+      if (ci < 1 || (double)ci != cid) *a.s.err = 1;
+      const T* b = a.s.boxes + row * a.s.box_stride;
+      PseudoRecord rec;
+      rec.image = i; rec.row = r;
+      rec.box[0] = (float)b[0]; rec.box[1] = (float)b[1]; rec.box[2] = (float)b[2]; rec.box[3] = (float)b[3];
+      rec.det_score = (float)a.s.scores[row];
+      rec.cls = ci;
+      rec.v = v;
+      a.slots[(size_t)i * a.cap + slot] = rec;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const double lo = __shfl_xor(vmin, o), hi = __shfl_xor(vmax, o);
+    vmin = lo < vmin ? lo : vmin;
+    vmax = hi > vmax ? hi : vmax;
+  }
+  if (lane == 0) { wave_min[wave] = vmin; wave_max[wave] = vmax; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double lo = wave_min[0], hi = wave_max[0];
+    for (int w = 1; w < 4; ++w) {
+      lo = wave_min[w] < lo ? wave_min[w] : lo;
+      hi = wave_max[w] > hi ? wave_max[w] : hi;
+    }
+    a.minmax[2 * (size_t)i] = lo; a.minmax[2 * (size_t)i + 1] = hi;
+    a.kept[i] = kept_base; a.cand[i] = cand_base;
+  }
+}
+
+// records of image i -> records[sum(cand[0 .. i)) ...]: one block per image; the offset is an integer sum in a fixed order
+__global__ __launch_bounds__(256) void pseudo_pack_kernel(const int32_t* cand, const PseudoRecord* slots, PseudoRecord* records, int cap) {
+  __shared__ int wave_sum[4];
+  const int i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int off = 0;
+  for (int k = threadIdx.x; k < i; k += 256) off += cand[k];
+  for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o);
+  if (lane == 0) wave_sum[wave] = off;
+  __syncthreads();
+  off = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+  const int words = (cand[i] < cap ? cand[i] : cap) * (int)(sizeof(PseudoRecord) / sizeof(int32_t));
+  const int32_t* src = (const int32_t*)(slots + (size_t)i * cap);
+  int32_t* dst = (int32_t*)(records + off);
+  for (int w = threadIdx.x; w < words; w += 256) dst[w] = src[w];
+}
+
+template <typename T>
+static void launch_pseudo_rows_t(const PseudoArgs<T>& a, hipStream_t s) {
+  if (a.s.n <= 0) return;
+  hipLaunchKernelGGL(pseudo_rows_kernel<T>, dim3((unsigned)a.s.n), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(pseudo_pack_kernel, dim3((unsigned)a.s.n), dim3(256), 0, s, a.cand, a.slots, a.records, a.cap);
+}
+void launch_pseudo_rows(const PseudoArgs<float>& a, hipStream_t s) { launch_pseudo_rows_t(a, s); }
+void launch_pseudo_rows(const PseudoArgs<double>& a, hipStream_t s) { launch_pseudo_rows_t(a, s); }
 
 // ------------------------------------------------------------------------------------ COCO matching
 // COCOeval_all.evaluateImg (custom_cocoeval.py:265-349) at maxDets[-1] = 100 for the containers EvaluationMetric.update_state

@@ -198,6 +198,14 @@ struct uda_ctx {
   std::vector<char> h_score;         // host copy of the pack (filled by the first reader of a scoring)
   int score_n = 0, score_nc = 0;     // images / components of the last scoring (0: none)
   bool score_fetched = false;
+  // pseudo-labelling rows (uda_pseudo_rows), sized for max_images x max_output_size records: a head of minmax [n, 2] float64 |
+  // kept [n] | cand [n] | error flag, then records [n, cap] x 40 bytes of which the first sum(cand) are used (PseudoPack); the
+  // host copies the head, then the used records
+  char* d_pseudo_pack = nullptr;
+  char* d_pseudo_slots = nullptr;    // [max_images, max_output_size] records: per-image staging of the packing kernel
+  std::vector<char> h_pseudo;        // host copy of the pack's head (filled by the first reader of a run)
+  int pseudo_n = 0, pseudo_cap = 0;  // images / record slots per image of the last uda_pseudo_rows (0: none)
+  bool pseudo_fetched = false;
   // COCO matching (uda_set_eval_ground_truth / uda_eval_match): ground truth [max_images, egt_cap, 7], grown when a call brings
   // more rows per image; results packed for max_images so that ONE copy brings them to the host:
   // records [n, M] x 44 bytes | npig [n, num_classes, 4] int32 | used [n] int32 (EvalPack)

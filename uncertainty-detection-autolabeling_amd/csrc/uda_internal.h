@@ -416,6 +416,30 @@ struct ScoreArgs {
 void launch_score_images(const ScoreArgs<float>& a, hipStream_t s);
 void launch_score_images(const ScoreArgs<double>& a, hipStream_t s);
 
+// pseudo-labelling rows (reference SSL_stac.py:302-642, STAC.score_image): the per-ROW form of the scores above.  `s` gives the
+// columns, min_score and the descriptor (its comp / count / class_counts / reduce_mean are not used); one record per candidate row
+struct PseudoRecord {       // uda_pseudo_record_t
+  int32_t image, row;
+  float box[4];             // as stored: y1 x1 y2 x2
+  float det_score;
+  int32_t cls;
+  double v;
+};
+static_assert(sizeof(PseudoRecord) == 40, "the record is 40 bytes");
+template <typename T>
+struct PseudoArgs {
+  ScoreArgs<T> s;
+  double tau;               // a candidate: det_score > tau (gate 0) or v > tau (gate 1), in float64
+  int invert, gate;         // invert: v = 1 / mean of the 2 or 3 components; else v = the one component
+  int max_rows, cap;        // only the first max_rows kept rows of an image take part; cap = min(M, max_rows) slots per image
+  double* minmax;           // [n, 2] over the participating rows, NaN ignored; (+inf, -inf) where none takes part
+  int32_t *kept, *cand;     // [n] rows above min_score (before the cap) / candidates
+  PseudoRecord* slots;      // [n, cap] the image's candidates in rank order (staging for the packing kernel)
+  PseudoRecord* records;    // [sum(cand)] densely packed in (image, rank) order
+};
+void launch_pseudo_rows(const PseudoArgs<float>& a, hipStream_t s);
+void launch_pseudo_rows(const PseudoArgs<double>& a, hipStream_t s);
+
 // COCO matching (reference custom_cocoeval.py:265-349 on the containers of coco_metric.py:219-283): one record per detection row
 enum { COCO_MAX_DET = 100, COCO_MAX_M = 4096, COCO_MAX_G = UDA_EVAL_MAX_GT, COCO_MAX_T = UDA_EVAL_MAX_THRS };
 struct CocoMatchArgs {

@@ -67,6 +67,32 @@ struct ScorePack {       // components [n, nc] float64 | count [n] int32 | class
   }
 };
 
+static_assert(sizeof(uda_pseudo_record_t) == sizeof(PseudoRecord), "the record is 40 bytes on both sides");
+struct PseudoPack {      // head: minmax [n, 2] float64 | kept [n] | cand [n] | error flag, padded to 8 bytes; then records [n, cap] x 40
+  char* base;            // bytes, the first sum(cand) used - the host copies the head, then only the used records
+  size_t n, cap;
+  PseudoPack(void* b, size_t n_, size_t cap_) : base((char*)b), n(n_), cap(cap_) {}
+  size_t head_bytes() const { return (n * 2 * sizeof(double) + (2 * n + 1) * sizeof(int32_t) + 7) & ~(size_t)7; }
+  size_t bytes() const { return head_bytes() + n * cap * sizeof(PseudoRecord); }
+  double* minmax() const { return (double*)base; }
+  int32_t* kept() const { return (int32_t*)(base + n * 2 * sizeof(double)); }
+  int32_t* cand() const { return kept() + n; }
+  int32_t* err() const { return cand() + n; }
+  PseudoRecord* rec() const { return (PseudoRecord*)(base + head_bytes()); }
+  int64_t total() const { return std::accumulate(cand(), cand() + n, (int64_t)0); }
+  // `base` is a host copy of the head; `recs` a host copy of the first total() records (null: none were asked for)
+  int copy_out(uda_ctx* c, const char* who, int C, const void* recs, void* records, int64_t n_records, double* minmax_out,
+               int32_t* kept_out, int32_t* cand_out) const {
+    if (*err()) return fail(c, "%s: a candidate has a class id outside 1..%d", who, C);
+    if (records && n_records != total()) return fail(c, "%s: %lld candidate records, not %lld", who, (long long)total(), (long long)n_records);
+    if (records && n_records) memcpy(records, recs, (size_t)n_records * sizeof(PseudoRecord));
+    if (minmax_out) memcpy(minmax_out, minmax(), n * 2 * sizeof(double));
+    if (kept_out) memcpy(kept_out, kept(), n * sizeof(int32_t));
+    if (cand_out) memcpy(cand_out, cand(), n * sizeof(int32_t));
+    return 0;
+  }
+};
+
 static_assert(sizeof(uda_eval_record_t) == 44, "the record is 11 words");
 struct EvalPack {        // records [n, M] x 44 bytes | npig [n, C, 4] int32 | used [n] int32
   char* base;
@@ -374,6 +400,176 @@ extern "C" int uda_score_images_np_f32(int32_t device, const uda_score_desc_t* d
                                        int32_t mcclass_cols, double* components, int32_t* count, int32_t* class_counts) {
   return score_images_np<float>("uda_score_images_np_f32", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass,
                                 n, M, num_classes, mcclass_cols, components, count, class_counts);
+}
+
+// ---- pseudo-labelling rows (reference SSL_stac.py:302-642 on the lines of infer_model.py:836-960)
+// what the five scalars must satisfy beside a well-formed descriptor; null when they do
+static const char* pseudo_args_bad(const uda_score_desc_t* d, int invert, int gate, double tau, int max_rows) {
+  if (max_rows < 1) return "max_rows must be at least 1";
+  if (!(tau >= 0.0)) return "tau must not be negative";
+  if ((invert != 0 && invert != 1) || (gate != 0 && gate != 1)) return "invert and gate are 0 or 1";
+  if (invert && d->n_comp < 2) return "invert needs 2 or 3 components";
+  if (!invert && d->n_comp != 1) return "several components need invert";
+  if (invert && gate) return "gate 1 (v > tau) belongs to the single-column branch, not to invert";
+  return nullptr;
+}
+
+extern "C" int uda_pseudo_rows(uda_ctx_t* c, const uda_score_desc_t* desc, int32_t invert, int32_t gate, float min_score, double tau,
+                               int32_t max_rows) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  const char* why = nullptr;
+  const unsigned need = score_desc_sources(desc, &why);
+  if (!why) why = pseudo_args_bad(desc, invert, gate, tau, max_rows);
+  if (why) return fail(c, "pseudo_rows: %s", why);
+  if (int rc = resident_ready(c, "pseudo_rows", "the pseudo-labels read")) return rc;
+  if ((need & (1u << UDA_SCORE_ENTROPY)) && !m.enable_softmax)
+    return fail(c, "pseudo_rows: the model emits no entropy (enable_softmax is off)");
+  if ((need & (1u << UDA_SCORE_ALBOX)) && !(m.has_uncert && m.loss_attenuation))
+    return fail(c, "pseudo_rows: the model emits no aleatoric box uncertainty (no loss attenuation)");
+  if ((need & (1u << UDA_SCORE_MCBOX)) && !(m.has_uncert && m.box_stacked))
+    return fail(c, "pseudo_rows: the model emits no epistemic box uncertainty (no MC dropout on the box head)");
+  if ((need & (1u << UDA_SCORE_MCCLASS)) && !(m.has_uncert && m.cls_stacked))
+    return fail(c, "pseudo_rows: the model emits no epistemic class uncertainty (no MC dropout on the class head)");
+  if (m.max_output_size > kScoreMaxM) return fail(c, "pseudo_rows: max_output_size %d above %d", m.max_output_size, kScoreMaxM);
+  if (m.num_classes < 1) return fail(c, "pseudo_rows: num_classes %d below 1", m.num_classes);
+  if (int rc = settle_detections(c)) return rc;
+  const int n = c->last_n, M = m.max_output_size, cap = std::min(M, max_rows);
+  if (!c->d_pseudo_pack) {
+    HIPC(c, dalloc(&c->d_pseudo_pack, PseudoPack(nullptr, (size_t)m.max_images, (size_t)M).bytes()));
+    HIPC(c, dalloc(&c->d_pseudo_slots, (size_t)m.max_images * M * sizeof(PseudoRecord)));
+  }
+  {
+    ProfScope ps(c, 21);
+    if (need & (1u << UDA_SCORE_ENTROPY))
+      if (int rc = ensure_probs(c, n * M)) return rc;
+    const int bc = box_cols_of(m, UDA_POST_GLOBAL), cc = cls_cols_of(m, UDA_POST_GLOBAL);
+    PseudoArgs<float> a{};
+    a.s.boxes = c->d_oboxes; a.s.scores = c->d_oscores; a.s.classes = c->d_oclasses; a.s.entropy = c->d_oentropy;
+    a.s.albox = c->d_oboxes + 4;                                             // box | aleatoric std | MC std, as each exists
+    a.s.mcbox = c->d_oboxes + ((m.has_uncert && m.loss_attenuation) ? 8 : 4);
+    a.s.mcclass = c->d_oclasses + 1;
+    a.s.box_stride = a.s.al_stride = a.s.mc_stride = bc; a.s.cls_stride = a.s.mcc_stride = cc; a.s.mcc_w = cc - 1;
+    const PseudoPack pack(c->d_pseudo_pack, (size_t)n, (size_t)cap);
+    a.s.err = pack.err(); a.s.n = n; a.s.M = M; a.s.C = m.num_classes; a.s.min_score = min_score; a.s.desc = *desc;
+    a.tau = tau; a.invert = invert; a.gate = gate; a.max_rows = max_rows; a.cap = cap;
+    a.minmax = pack.minmax(); a.kept = pack.kept(); a.cand = pack.cand(); a.records = pack.rec();
+    a.slots = (PseudoRecord*)c->d_pseudo_slots;
+    HIPC(c, hipMemsetAsync(a.s.err, 0, sizeof(int32_t), c->stream));
+    launch_pseudo_rows(a, c->stream);
+  }
+  HIPC(c, hipGetLastError());
+  c->pseudo_n = n; c->pseudo_cap = cap; c->pseudo_fetched = false;
+  return 0;
+}
+
+// The first reader of a run waits for it and brings the pack's head over in one copy.
+static int fetch_pseudo(uda_ctx* c, const char* who) {
+  if (c->pseudo_n < 1) return fail(c, "%s: no pseudo-label rows (uda_pseudo_rows)", who);
+  if (c->pseudo_fetched) return 0;
+  const PseudoPack h(nullptr, (size_t)c->pseudo_n, (size_t)c->pseudo_cap);
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  c->h_pseudo.resize(h.head_bytes());
+  HIPC(c, hipMemcpy(c->h_pseudo.data(), c->d_pseudo_pack, h.head_bytes(), hipMemcpyDeviceToHost));
+  c->pseudo_fetched = true;
+  return 0;
+}
+
+extern "C" int uda_pseudo_rows_shape(uda_ctx_t* c, int32_t* n, int64_t* K) {
+  if (!c || !n || !K) return 1;
+  if (int rc = fetch_pseudo(c, "pseudo_rows_shape")) return rc;
+  *n = c->pseudo_n;
+  *K = PseudoPack(c->h_pseudo.data(), (size_t)c->pseudo_n, (size_t)c->pseudo_cap).total();
+  return 0;
+}
+
+extern "C" int uda_get_pseudo_rows(uda_ctx_t* c, void* records, int64_t n_records, double* minmax, int32_t* kept, int32_t* cand) {
+  if (!c) return 1;
+  if (int rc = fetch_pseudo(c, "get_pseudo_rows")) return rc;
+  const PseudoPack h(c->h_pseudo.data(), (size_t)c->pseudo_n, (size_t)c->pseudo_cap);
+  if (int rc = h.copy_out(c, "pseudo_rows", c->model.num_classes, nullptr, nullptr, 0, minmax, kept, cand)) return rc;
+  if (!records) return 0;
+  if (n_records != h.total()) return fail(c, "pseudo_rows: %lld candidate records, not %lld", (long long)h.total(), (long long)n_records);
+  // the used records only, straight into the caller's array (the stream was waited for when the head was fetched)
+  if (n_records)
+    HIPC(c, hipMemcpy(records, PseudoPack(c->d_pseudo_pack, h.n, h.cap).rec(), (size_t)n_records * sizeof(PseudoRecord), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// score_image's first half for callers that hold detections of their own (calibrated columns, a gathered multi-GPU batch): host
+// arrays in, the same kernels, host arrays out; its own allocations
+template <typename T>
+static int pseudo_rows_np(const char* who, int32_t device, const uda_score_desc_t* desc, T min_score, const T* boxes, const T* scores,
+                          const T* classes, const T* entropy, const T* albox, const T* mcbox, const T* mcclass, int32_t n, int32_t M,
+                          int32_t C, int32_t mcw, int32_t invert, int32_t gate, double tau, int32_t max_rows, void* records,
+                          int64_t* n_records, double* minmax, int32_t* kept, int32_t* cand) {
+  const char* why = nullptr;
+  const unsigned need = score_desc_sources(desc, &why);
+  if (!why) why = pseudo_args_bad(desc, invert, gate, tau, max_rows);
+  if (why) return fail(nullptr, "%s: %s", who, why);
+  if (n < 0 || M < 0 || M > kScoreMaxM || C < 1 || ((size_t)n * M && (!boxes || !scores || !classes)) || (records && !n_records))
+    return fail(nullptr, "%s: bad argument", who);
+  const T* srcs[] = {entropy, scores, albox, mcbox, mcclass};
+  static const char* names[] = {"entropy", "scores", "albox", "mcbox", "mcclass"};
+  for (int s = 0; s < 5; ++s)
+    if ((need & (1u << s)) && (size_t)n * M && !srcs[s]) return fail(nullptr, "%s: the descriptor reads %s, which is not given", who, names[s]);
+  if ((need & (1u << UDA_SCORE_MCCLASS)) && mcw < 1) return fail(nullptr, "%s: mcclass_cols must be at least 1", who);
+  if (n_records) *n_records = 0;
+  if (n == 0) return 0;
+  const size_t nm = (size_t)n * M, cap = (size_t)std::min(M, max_rows);
+  const size_t widths[] = {4, 1, 1, 1, 4, 4, (size_t)(mcw > 0 ? mcw : 0)};
+  const T* host[] = {boxes, scores, classes, entropy, albox, mcbox, mcclass};
+  DevScratch s(device);
+  T* dev[7] = {};
+  for (int k = 0; k < 7; ++k)
+    if (nm * widths[k]) dev[k] = s.upload(host[k], nm * widths[k]);
+  PseudoPack pack(nullptr, (size_t)n, cap);
+  pack.base = s.alloc<char>(pack.bytes());
+  s.zero(pack.base, pack.bytes());
+  PseudoRecord* slots = s.alloc<PseudoRecord>((size_t)n * cap);
+  if (s.ok()) {
+    PseudoArgs<T> a{};
+    a.s.boxes = dev[0]; a.s.scores = dev[1]; a.s.classes = dev[2]; a.s.entropy = dev[3]; a.s.albox = dev[4]; a.s.mcbox = dev[5];
+    a.s.mcclass = dev[6];
+    a.s.box_stride = a.s.al_stride = a.s.mc_stride = 4; a.s.cls_stride = 1; a.s.mcc_stride = a.s.mcc_w = mcw > 0 ? mcw : 0;
+    a.s.err = pack.err(); a.s.n = n; a.s.M = M; a.s.C = C; a.s.min_score = min_score; a.s.desc = *desc;
+    a.tau = tau; a.invert = invert; a.gate = gate; a.max_rows = max_rows; a.cap = (int)cap;
+    a.minmax = pack.minmax(); a.kept = pack.kept(); a.cand = pack.cand(); a.records = pack.rec(); a.slots = slots;
+    launch_pseudo_rows(a, nullptr);
+  }
+  s.sync();
+  std::vector<char> h(pack.head_bytes());
+  s.download(h.data(), pack.base, h.size());
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  const PseudoPack hp(h.data(), pack.n, pack.cap);
+  const int64_t K = hp.total();
+  std::vector<char> recs;
+  if (records && K && !*hp.err()) {
+    recs.resize((size_t)K * sizeof(PseudoRecord));
+    s.download(recs.data(), pack.rec(), recs.size());
+    if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  }
+  if (n_records) *n_records = K;
+  return hp.copy_out(nullptr, who, C, recs.data(), records, K, minmax, kept, cand);
+}
+
+extern "C" int uda_pseudo_rows_np(int32_t device, const uda_score_desc_t* desc, double min_score, const double* boxes,
+                                  const double* scores, const double* classes, const double* entropy, const double* albox,
+                                  const double* mcbox, const double* mcclass, int32_t n, int32_t M, int32_t num_classes,
+                                  int32_t mcclass_cols, int32_t invert, int32_t gate, double tau, int32_t max_rows, void* records,
+                                  int64_t* n_records, double* minmax, int32_t* kept, int32_t* cand) {
+  return pseudo_rows_np<double>("uda_pseudo_rows_np", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass, n, M,
+                                num_classes, mcclass_cols, invert, gate, tau, max_rows, records, n_records, minmax, kept, cand);
+}
+
+extern "C" int uda_pseudo_rows_np_f32(int32_t device, const uda_score_desc_t* desc, float min_score, const float* boxes,
+                                      const float* scores, const float* classes, const float* entropy, const float* albox,
+                                      const float* mcbox, const float* mcclass, int32_t n, int32_t M, int32_t num_classes,
+                                      int32_t mcclass_cols, int32_t invert, int32_t gate, double tau, int32_t max_rows, void* records,
+                                      int64_t* n_records, double* minmax, int32_t* kept, int32_t* cand) {
+  return pseudo_rows_np<float>("uda_pseudo_rows_np_f32", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass, n,
+                               M, num_classes, mcclass_cols, invert, gate, tau, max_rows, records, n_records, minmax, kept, cand);
 }
 
 // ---- COCO matching (reference custom_cocoeval.py:265-349 on the containers of coco_metric.py:219-283)

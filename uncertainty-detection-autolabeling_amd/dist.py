@@ -299,6 +299,14 @@ class SampleShardedDriver:
     def serve_score(self, images, strategy, min_score, opt_params=None):
         return self.score_images(strategy, min_score, opt_params)
 
+    def pseudo_rows(self, strategy, tau, opt_params=None, min_score=None, max_rows=None):
+        """As for the ground-truth assignment: no single handle holds the whole batch's detections."""
+        raise ValueError("a sample-sharded serve leaves no handle that holds the whole batch's detections: run "
+                         "pseudo_labels.select_detections(columns, strategy, tau) on the gathered detections")
+
+    def serve_pseudo_labels(self, images, strategy, tau, opt_params=None, min_score=None, max_rows=None):
+        return self.pseudo_rows(strategy, tau, opt_params, min_score, max_rows)
+
     def eval_match(self, groundtruth_data, iou_thrs=None):
         """As for the ground-truth assignment: no single handle holds the whole batch's detections."""
         raise ValueError("a sample-sharded serve leaves no handle that holds the whole batch's detections: run "

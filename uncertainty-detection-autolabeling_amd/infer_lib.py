@@ -543,6 +543,49 @@ class ServingDriver:
         self.serve_resident(image_arrays, post_mode=capi.POST_GLOBAL)
         return self.score_images(st, min_score)
 
+    # ------------------------------------------------------------------ semi-supervised learning: the teacher's pseudo-labels
+    def _resolve_selection(self, strategy, opt_params):
+        from . import pseudo_labels as pl
+        sel = strategy if isinstance(strategy, pl.Selection) else pl.resolve_selection(strategy, self.params, opt_params)
+        if sel.calibrated:
+            raise ValueError("strategy %r reads calibrated columns (%s), which are host arrays: select them with "
+                             "pseudo_labels.select_detections" % (sel.name, ", ".join(sorted(sel.columns.values()))))
+        return sel
+
+    def pseudo_rows(self, strategy, tau, opt_params=None, min_score=None, max_rows=None):
+        """The first half of the teacher's selection (`STAC.score_image`, SSL_stac.py:302-541) on the detections resident in
+        the handle: of every image the first `max_rows` (99) detections with score > min_score get the strategy's value v, and
+        those with det_score > tau - in the single-column branch v > tau - come back as candidate records, with the min / max
+        of v per image.  strategy: STAC's `selection_strategy` string (`pseudo_labels.resolve_selection`) or a resolved
+        `Selection`; min_score None: 0.1, what SSL inference writes (`active_learning.default_min_score(params, ssl=True)`),
+        rounded to float32.
+
+        Returns (records [K] `pseudo_labels.RECORD_DTYPE` in (image, rank) order, minmax [n, 2] float64, kept [n] int32,
+        cand [n] int32) for the images of the last run, wherever `score_images` works; `pseudo_labels.PseudoLabelSet`
+        accumulates the batches of a dataset and does the dataset-wide part."""
+        from . import active_learning as al, pseudo_labels as pl
+        sel = self._resolve_selection(strategy, opt_params)
+        if min_score is None:
+            min_score = al.default_min_score(self.params, ssl=True)
+        desc = sel.desc()
+        self._ck(self._lib.uda_pseudo_rows(self._h, C.byref(desc), sel.invert, sel.gate, C.c_float(min_score), C.c_double(pl._check_tau(tau)),
+                                           int(pl.MAX_ROWS if max_rows is None else max_rows)), "uda_pseudo_rows")
+        n, K = C.c_int32(), C.c_int64()
+        self._ck(self._lib.uda_pseudo_rows_shape(self._h, C.byref(n), C.byref(K)), "uda_pseudo_rows_shape")
+        n = n.value
+        rec = np.zeros((K.value,), pl.RECORD_DTYPE)
+        minmax = np.zeros((n, 2), np.float64)
+        kept = np.zeros((n,), np.int32)
+        cand = np.zeros((n,), np.int32)
+        self._ck(self._lib.uda_get_pseudo_rows(self._h, _ptr(rec), K.value, _ptr(minmax), _ptr(kept), _ptr(cand)), "uda_get_pseudo_rows")
+        return rec, minmax, kept, cand
+
+    def serve_pseudo_labels(self, image_arrays, strategy, tau, opt_params=None, min_score=None, max_rows=None):
+        """serve resident + `pseudo_rows`: the batch's candidates without downloading the 100-row detection columns."""
+        sel = self._resolve_selection(strategy, opt_params)
+        self.serve_resident(image_arrays, post_mode=capi.POST_GLOBAL)
+        return self.pseudo_rows(sel, tau, min_score=min_score, max_rows=max_rows)
+
     # ------------------------------------------------------------------ COCO evaluation: matching on the resident detections
     def eval_match(self, groundtruth_data, iou_thrs=None):
         """`COCOeval_all.evaluateImg` (custom_cocoeval.py:265-349) for the detections resident in the handle after a
@@ -1079,6 +1122,14 @@ class EnsembleDriver:
     def serve_score(self, image_arrays, strategy, min_score, opt_params=None):
         self.serve(image_arrays)
         return self.score_images(strategy, min_score, opt_params=opt_params)
+
+    def pseudo_rows(self, strategy, tau, opt_params=None, min_score=None, max_rows=None):
+        """The ensemble's detections live in its aggregating handle: the candidates are that handle's."""
+        return self.post.pseudo_rows(strategy, tau, opt_params=opt_params, min_score=min_score, max_rows=max_rows)
+
+    def serve_pseudo_labels(self, image_arrays, strategy, tau, opt_params=None, min_score=None, max_rows=None):
+        self.serve(image_arrays)
+        return self.pseudo_rows(strategy, tau, opt_params=opt_params, min_score=min_score, max_rows=max_rows)
 
     def eval_match(self, groundtruth_data, iou_thrs=None):
         """The ensemble's detections live in its aggregating handle: the match is that handle's."""
