@@ -600,7 +600,14 @@ int uda_read_buffer(uda_ctx_t* ctx, int32_t buf, float* host, int64_t n_floats);
 int uda_get_preprocessed(uda_ctx_t* ctx, float* images /* [n,H,W,3] */, float* scales /* [n] */);
 
 /* Standalone NMS on host arrays (parity tests of the NonMaxSuppressionV5 kernel):
- * boxes [n_img, k, 4], scores [n_img, k] -> idx [n_img, M], out_scores [n_img, M], valid [n_img] */
+ * boxes [n_img, k, 4], scores [n_img, k] -> idx [n_img, M], out_scores [n_img, M], valid [n_img]; M <= 128.
+ * Bit-exact against the reference for finite boxes (inverted corners, zero area, identical and touching boxes included), any
+ * iou_thresh (0, negative, >= 1), and scores that are finite, +-0.0 (the two zeros tie, the smaller index first, each keeps
+ * its sign on the way out), +inf, -inf or NaN (the last two never enter the heap).  One case is REFUSED (non-zero return,
+ * uda_last_error names the first offending score, nothing is computed): soft_sigma > 0 with score_thresh < 0 and a live
+ * score below 0 (score_thresh < score < 0).  Soft weights raise such a score; the reference re-pushes it with a higher
+ * priority, which the kernels' epoch rule - a cached exact score is an upper bound - cannot follow exactly (DESIGN.md
+ * section 5).  Non-finite box coordinates are undefined (inf - inf: a NaN IoU). */
 int uda_nms(uda_ctx_t* ctx, const float* boxes, const float* scores, int32_t n_img, int32_t k,
             int32_t max_out, float iou_thresh, float score_thresh, float soft_sigma, int32_t pad,
             int32_t* idx, float* out_scores, int32_t* valid);

@@ -120,17 +120,7 @@ def test_d2_topology_matches_oracle():
     d.close()
 
 
-def _rand_boxes(rng, n, span=400.0, tied=False):
-    c = rng.uniform(0, span, (n, 2))
-    wh = rng.uniform(4, 120, (n, 2))
-    b = np.stack([c[:, 0] - wh[:, 0] / 2, c[:, 1] - wh[:, 1] / 2, c[:, 0] + wh[:, 0] / 2,
-                  c[:, 1] + wh[:, 1] / 2], 1).astype(np.float32)
-    if tied:
-        s = (0.01 + rng.normal(0, 1e-4, n)).astype(np.float32)
-        s[rng.integers(0, n, n // 8)] = s[0]            # exact ties -> index tie-break
-    else:
-        s = rng.uniform(0, 1, n).astype(np.float32)
-    return b, s
+from nms_cases import plain_boxes as _rand_boxes          # noqa: E402  (the control kind of tests/nms_cases.py)
 
 
 @pytest.mark.parametrize("n,tied,sigma,thr", [(0, False, 0.25, 0.001), (1, False, 0.25, 0.001),

@@ -1581,8 +1581,11 @@ void launch_class_mean(const AggArgs& a, float* out, hipStream_t s) {
   hipLaunchKernelGGL(class_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, out);
 }
 
+// order-preserving bits of a float; -0.0 takes +0.0's key: the reference compares floats, to which the two zeros are a tie
+// (broken by the index), so no selection may rank one above the other
 __device__ __forceinline__ uint32_t ord32(float v) {
-  const uint32_t b = __float_as_uint(v);
+  uint32_t b = __float_as_uint(v);
+  if (b == 0x80000000u) b = 0u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
@@ -1844,8 +1847,7 @@ constexpr int NMS_ITEMS = UDA_NMS_ITEMS;
 constexpr int NMS_CHUNK = 256 * NMS_ITEMS;
 
 __device__ __forceinline__ unsigned long long nms_key(float s, int idx) {
-  const uint32_t b = __float_as_uint(s);
-  const uint32_t o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  const uint32_t o = ord32(s);          // (-0.0 ties with +0.0 as in the reference's heap: the smaller index first)
   return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)idx);
 }
 

@@ -853,6 +853,18 @@ extern "C" int uda_nms(uda_ctx_t* c, const float* boxes, const float* scores, in
   if (!c || !boxes || !scores || !idx || !out_scores || !valid) return c ? fail(c, "uda_nms: NULL argument") : 1;
   if (n_img < 1 || k < 0 || max_out < 1 || max_out > 128) return fail(c, "uda_nms: bad sizes (max_out must be in [1, 128])");
   const size_t NK = (size_t)n_img * (k ? k : 1), NM = (size_t)n_img * max_out;
+  // The epoch rule of the kernels needs scores that only shrink: a cached exact score is an upper
+  // bound, a candidate below the last winner cannot be popped.  Soft NMS moves a live NEGATIVE score up (a weight below 1
+  // times a negative number), the reference re-pushes it with a higher priority and the selections differ - refused, not
+  // answered differently.  (Host arrays: the scan is free here; the serve path scores are sigmoids and never negative.)
+  if (soft_sigma > 0.0f && score_thresh < 0.0f) {
+    for (size_t i = 0; i < (size_t)n_img * (size_t)k; ++i)
+      if (scores[i] < 0.0f && scores[i] > score_thresh)
+        return fail(c, "uda_nms: soft NMS (soft_sigma %g) with score_thresh %g < 0 over a live negative score (problem %lld, "
+                       "candidate %lld: %g) is not supported: its weights raise such a score, which the kernels' epoch rule "
+                       "cannot follow exactly.  Use score_thresh >= 0, hard NMS, or non-negative scores",
+                    (double)soft_sigma, (double)score_thresh, (long long)(i / (size_t)k), (long long)(i % (size_t)k), (double)scores[i]);
+  }
   DevScratch s(c->device);
   float* d_boxes = k ? s.upload(boxes, NK * 4, c->stream) : s.alloc<float>(NK * 4);
   float* d_scores = k ? s.upload(scores, NK, c->stream) : s.alloc<float>(NK);
