@@ -218,7 +218,7 @@ void launch_consistency(const ConsArgs& a, hipStream_t s) {
 //   IoU  argmax_k calc_iou_np(gt, box_k) (iou_np above), all M rows, padded ones included
 //   MSE  argmin_k np.mean(np.square(gt - box_k)) in float32: differences, squares, ((s0 + s1) + s2) + s3 (numpy's order for a
 //        4-element inner axis), times 0.25f (= / 4 exactly); no contraction in this file
-//   else rank i itself (the reference's else branch); a kept row i >= M raises *err
+//   else rank i itself (the reference's else branch); a kept row i >= M raises *err, and so does any kept row when M == 0
 // np.argmax / np.argmin return the first occurrence: a candidate replaces the best one only when its key is strictly better, or
 // equal with a lower rank - in the lane's own sweep and in every step of the wave reduction alike, so the winner is the
 // lexicographic best of (key, rank) however the ranks were dealt to lanes.  This decides real cases: padded slots carry row
@@ -279,8 +279,8 @@ __global__ __launch_bounds__(256) void assign_gt_kernel(AssignArgs a) {
       best = g;
     }
     if (lane == 0) {
-      if (best >= M) {                                     // rank branch beyond the detections (or M == 0)
-        if (a.method != ASSIGN_IOU && a.method != ASSIGN_MSE) *a.err = 1;
+      if (best >= M) {                                     // rank branch beyond the detections, or no detection at all (M == 0)
+        *a.err = 1;
         best = 0;
       }
       a.det_index[row] = best;

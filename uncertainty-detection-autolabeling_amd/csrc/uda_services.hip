@@ -41,7 +41,9 @@ struct AssignPack {      // iou [n G] float64 | det_index [n G] int32 | count [n
   int32_t* count() const { return det_index() + n * G; }
   int32_t* err() const { return count() + n; }
   int copy_out(uda_ctx* c, const char* who, int M, int32_t* det_index_out, double* iou_out, int32_t* count_out) const {
-    if (*err()) return fail(c, "%s: the rank method met a kept ground-truth row beyond the %d detections", who, M);
+    if (*err())
+      return fail(c, M > 0 ? "%s: the rank method met a kept ground-truth row beyond the %d detections"
+                           : "%s: a kept ground-truth row and %d detections to match it with", who, M);
     if (iou_out && n * G) memcpy(iou_out, iou(), n * G * sizeof(double));
     if (det_index_out && n * G) memcpy(det_index_out, det_index(), n * G * sizeof(int32_t));
     if (count_out) memcpy(count_out, count(), n * sizeof(int32_t));
@@ -114,7 +116,8 @@ struct EvalPack {        // records [n, M] x 44 bytes | npig [n, C, 4] int32 | u
 static int assigned_row_cols_of(const uda_model_t& m) {
   return box_cols_of(m, UDA_POST_GLOBAL) + 1 + cls_cols_of(m, UDA_POST_GLOBAL) + (m.enable_softmax ? 2 * m.num_classes + 1 : 0);
 }
-// LDS of the two kernels: M boxes of 16 bytes, G row numbers of 4 bytes, each inside the 64 KiB a block may ask for
+// LDS of the two kernels: M boxes of 16 bytes, G row numbers of 4 bytes, and 4 static bytes each - 65540 at either cap, which the
+// runtime grants a gfx950 block as it is (tests/test_gpu_service_edges.py launches M = 4095 and 4096)
 static const int kAssignMaxM = 4096, kAssignMaxG = 16384;
 
 extern "C" int uda_assigned_row_cols(const uda_ctx_t* c, int32_t* cols) {

@@ -121,6 +121,8 @@ def assign_gt_boxes(method, gt_boxes, gt_classes, boxes, keep="validate", device
     n, G, M = gb.shape[0], gb.shape[1], b.shape[1]
     kc = keep_code(keep)
     check_rank_rows(method, gc, M, keep)
+    if M == 0 and keep == "validate" and (gc > 0).any():     # (calibrate keeps rows < min(G, M) only)
+        raise ValueError("a kept ground-truth row and no detection to match it with (the reference fails in np.argmax)")
     if not np.isfinite(b).all():
         raise ValueError("detection boxes must be finite")
     idx = np.full((n, G), -1, np.int32)
