@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX: quick A/B of environment switches in one job (same box, same library):
-#   tools/ab_env.sh "UDA_FUSE_IN=0" "UDA_FUSE_IN=1" "UDA_FUSE_IN=1 UDA_SEPF_ALL=1"
+#   tools/ab_env.sh "UDA_FUSE_IN=0" "UDA_FUSE_IN=1" "UDA_FUSE_IN=1 UDA_SEP_MULTI=0"
 # two rounds, alternating; prints ms/step and the per-kind kernel times of each run ("-" = no switch).
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 for ROUND in 1 2; do

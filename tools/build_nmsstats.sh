@@ -6,5 +6,5 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 C=$ROOT/uncertainty-detection-autolabeling_amd/csrc
 make -C $C -j4 > /dev/null
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -DUDA_NMS_STATS -c $C/kernels_post.hip -o /tmp/kernels_post_stats.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/tools/libuda_nmsstats.so $C/_build/uda_api.o $C/_build/kernels_conv.o $C/_build/kernels_pwb.o $C/_build/kernels_sep.o /tmp/kernels_post_stats.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/tools/libuda_nmsstats.so $C/_build/uda_api.o $C/_build/uda_services.o $C/_build/kernels_conv.o $C/_build/kernels_pwb.o $C/_build/kernels_sep.o /tmp/kernels_post_stats.o
 echo built $ROOT/tools/libuda_nmsstats.so

@@ -3,6 +3,7 @@
 
     python tools/codeobj.py resources [--lib PATH] [--match SUBSTR]     registers / spills / LDS / scratch per kernel
     python tools/codeobj.py lint [--lib PATH | --asm FILE.s]            VALU-written SGPR read by a VMEM instruction too early
+    python tools/codeobj.py diff LIB_A LIB_B [--allow SUBSTR ...]       kernels in one library only / other resources / other text
 
 Why the lint exists: on gfx9 a VMEM instruction that reads an SGPR (the `s[n:n+1]` base of
 `global_store_dword v, v, s[..]`, a buffer resource, a scalar offset) needs FIVE wait states after a VALU instruction
@@ -89,6 +90,59 @@ def demangle(names):
 
 def disassemble(elf):
     return subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", "--symbolize-operands", elf], text=True)
+
+
+# ------------------------------------------------------------------------------------------------ diff
+def kernel_texts(elf):
+    """{symbol: [instruction text]} of a code object from plain `llvm-objdump -d`: no addresses, no trailing `//` comment
+    (address and encoding).  Branch operands are printed as relative offsets, so the text of a kernel does not depend on
+    where it sits in the code object."""
+    out, cur = {}, None
+    for raw in subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", elf], text=True).splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", raw.strip())
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and raw[:1].isspace() and raw.strip() not in ("", "..."):      # ("...": skipped zero padding)
+            cur.append(" ".join(raw.split("//")[0].split()))
+    return out
+
+
+def library_kernels(lib):
+    """{mangled kernel name: (resource row without the name, [instruction text])} over all code objects of a library."""
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for elf in extract(lib, td):
+            texts = kernel_texts(elf)
+            for row in resources(elf):
+                out[row["name"]] = ({k: v for k, v in row.items() if k != "name"}, texts.get(row["name"], []))
+    return out
+
+
+def diff_libs(lib_a, lib_b, allow=()):
+    """Prints the three groups; -> the kernels whose instruction text differs and no --allow substring covers."""
+    ka, kb = library_kernels(lib_a), library_kernels(lib_b)
+    pretty = dict(zip(list(ka) + list(kb), demangle(list(ka) + list(kb))))
+    print("%d kernels in A (%s), %d in B (%s), %d in both" % (len(ka), lib_a, len(kb), lib_b, len(set(ka) & set(kb))))
+    for tag, only in (("A", set(ka) - set(kb)), ("B", set(kb) - set(ka))):
+        print("only in %s: %d" % (tag, len(only)))
+        for nm in sorted(pretty[n] for n in only):
+            print("   " + nm)
+    both = sorted(set(ka) & set(kb), key=lambda n: pretty[n])
+    res = [n for n in both if ka[n][0] != kb[n][0]]
+    print("resource rows differ: %d" % len(res))
+    for n in res:
+        print("   %s\n      A %s\n      B %s" % (pretty[n], ka[n][0], kb[n][0]))
+    txt = [n for n in both if ka[n][1] != kb[n][1]]
+    print("instruction text differs: %d" % len(txt))
+    refused = []
+    for n in txt:
+        a, b = ka[n][1], kb[n][1]
+        lines = sum(1 for x, y in zip(a, b) if x != y) + abs(len(a) - len(b))
+        ok = any(sub in pretty[n] for sub in allow)
+        print("   %s\n      %d / %d instructions, %d lines differ%s" % (pretty[n], len(a), len(b), lines, "   (allowed)" if ok else ""))
+        if not ok:
+            refused.append(n)
+    return refused
 
 
 # ------------------------------------------------------------------------------------------------ hazard lint
@@ -232,11 +286,18 @@ def lint_lib(lib=DEFAULT_LIB):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("cmd", choices=["resources", "lint"])
+    ap.add_argument("cmd", choices=["resources", "lint", "diff"])
+    ap.add_argument("libs", nargs="*", metavar="LIB", help="diff: the two libraries")
     ap.add_argument("--lib", default=DEFAULT_LIB)
     ap.add_argument("--asm", help="lint an assembly listing (hipcc -S output) instead of the library")
     ap.add_argument("--match", default="", help="resources: only kernels whose demangled name contains this")
+    ap.add_argument("--allow", action="append", default=[], metavar="SUBSTR",
+                    help="diff: accept other instruction text in kernels whose demangled name contains this (may repeat)")
     a = ap.parse_args()
+    if a.cmd == "diff":
+        if len(a.libs) != 2:
+            ap.error("diff takes two libraries")
+        sys.exit(1 if diff_libs(a.libs[0], a.libs[1], a.allow) else 0)
     if a.cmd == "lint":
         n, bad = lint_text(open(a.asm).read()) if a.asm else lint_lib(a.lib)
         for fn, st, wr, gap, regs in bad:

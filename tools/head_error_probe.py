@@ -28,4 +28,4 @@ for name, kw, hw in (("d0", dict(image_size="192x128", **FULL_MC), (128, 192)),
                 wr = max(wr, np.sqrt(np.mean((gg - rr) ** 2)) / np.sqrt(np.mean(rr * rr)))
     out[name] = "max %.2e rms %.2e" % (wm, wr)
     d.close()
-print(os.environ.get("UDA_PW_SCHEME", "default"), os.environ.get("UDA_F16_KINDS", "all"), out, flush=True)
+print(os.environ.get("UDA_PW_SCHEME", "default"), out, flush=True)

@@ -254,8 +254,7 @@ void launch_stem(const StemArgs& a, hipStream_t s) {
     }
     return;
   }
-  static const int wide = uda_env_int("UDA_STEM16", 1);
-  if (wide && (a.Co & 15) == 0 && a.act == UDA_ACT_SWISH) {     // (stem16 / stem_u8 are swish kernels; the executor keeps other activations off the uint8 route)
+  if ((a.Co & 15) == 0 && a.act == UDA_ACT_SWISH) {    // (stem16 / stem_u8 are swish kernels; the executor keeps other activations off the uint8 route)
     const int64_t total = (int64_t)a.rows * a.Ho * a.Wo * (a.Co >> 4);
     hipLaunchKernelGGL(stem16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 27 * a.Co * sizeof(float), s, a);
     return;
@@ -478,36 +477,24 @@ __global__ __launch_bounds__(NW * 64) void pw_kernel(PwArgs a) {
   }
 }
 
-template <int NW>
 static void launch_pw_nw(const PwArgs& a, int rows, int nt, hipStream_t s) {
-  const int gx = (a.HW + 32 * NW - 1) / (32 * NW);
-  const dim3 grid(gx, (a.Cout + 32 * nt - 1) / (32 * nt), rows), block(NW * 64);
+  const int gx = (a.HW + 32 * 4 - 1) / (32 * 4);
+  const dim3 grid(gx, (a.Cout + 32 * nt - 1) / (32 * nt), rows), block(4 * 64);
   switch (nt) {
-    case 1: hipLaunchKernelGGL((pw_kernel<1, NW>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((pw_kernel<2, NW>), grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((pw_kernel<3, NW>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((pw_kernel<4, NW>), grid, block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((pw_kernel<1, 4>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((pw_kernel<2, 4>), grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((pw_kernel<3, 4>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((pw_kernel<4, 4>), grid, block, 0, s, a); break;
   }
 }
 
 void launch_pw(const PwArgs& a, int rows, hipStream_t s) {
-  // one pass over the columns when Cout <= 192, else the fewest passes of <= 6 column tiles
-  static int maxnt = -1, maxnt_small = -1;
-  if (maxnt < 0) {
-    const char* e = getenv("UDA_PW_MAXNT");
-    maxnt = e ? atoi(e) : 4;
-    const char* e2 = getenv("UDA_PW_MAXNT_SMALLK");
-    maxnt_small = e2 ? atoi(e2) : maxnt;
-  }
-  const int cap = 32 * (a.Cin <= 48 ? maxnt_small : maxnt);
+  // the fewest passes of <= 4 column tiles (128 output channels), the columns spread evenly over them
+  const int cap = 32 * 4;
   const int passes = (a.Cout + cap - 1) / cap;
   const int per = (a.Cout + passes - 1) / passes;
-  int nt = (per + 31) / 32;
-  if (nt > 4) nt = 4;
-  static const int big = uda_env_int("UDA_PW_BIG", 0);
-  // 256-pixel blocks (8 waves) halve the weight-tile traffic per pixel; measured 6 % slower on the deep layers (off)
-  if (big && a.Cin >= 80 && a.HW >= 256) launch_pw_nw<8>(a, rows, nt, s);
-  else launch_pw_nw<4>(a, rows, nt, s);
+  const int nt = (per + 31) / 32;
+  launch_pw_nw(a, rows, nt, s);
 }
 
 // ------------------------------------------------------------------------------------ depthwise
@@ -880,7 +867,7 @@ __host__ __device__ constexpr MbxCfg mbx_cfg(int k, int s) {
 }
 }  // namespace
 
-template <int K, int S, int KS, int NW>   // KS = Cin / 2 MFMA k-steps; NW = waves per block (4 or 8)
+template <int K, int S, int KS, int NW>   // KS = Cin / 2 MFMA k-steps; NW = waves per block (4 in every instance)
 __global__ __launch_bounds__(NW * 64) void mbx_kernel(MbxArgs a) {
   constexpr int TH = mbx_cfg(K, S).th, TW = mbx_cfg(K, S).tw;
   constexpr int IH = (TH - 1) * S + K, IW = (TW - 1) * S + K;
@@ -903,13 +890,6 @@ __global__ __launch_bounds__(NW * 64) void mbx_kernel(MbxArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int b = blockIdx.z, b_in = b / a.in_div;
-  // diagnostic build only: wave-0 / wave-3 phase stamps of a few blocks (never set in production)
-  unsigned long long* stp = nullptr;
-  int stn = 0;
-  if (a.stamps && (lane == 0) && (wave == 0 || wave == NW - 1) && blockIdx.x == 3 && blockIdx.y == 5 && blockIdx.z < 8)
-    stp = a.stamps + ((size_t)blockIdx.z * 2 + (wave != 0)) * 64;
-#define MBX_STAMP() do { if (stp && stn < 64) stp[stn++] = clock64(); } while (0)
-  MBX_STAMP();
   const int oy0 = blockIdx.y * TH, ox0 = blockIdx.x * TW;
   const int iy0 = oy0 * S - a.pad_t, ix0 = ox0 * S - a.pad_l;
   const float* xin = a.in + (size_t)b_in * a.H * a.W * a.Cin;
@@ -948,9 +928,7 @@ __global__ __launch_bounds__(NW * 64) void mbx_kernel(MbxArgs a) {
     X[(size_t)a.Cin * XS + p] = (p < NP && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) ? 1.f : 0.f;
     X[(size_t)(a.Cin + 1) * XS + p] = 0.f;
   }
-  MBX_STAMP();
   __syncthreads();
-  MBX_STAMP();
 
   const int c = tid & 31, g = tid >> 5;       // depthwise stage: channel within the chunk, thread group
   const int orow = g / GPR, oxs = (g % GPR) * XW;
@@ -1013,9 +991,7 @@ __global__ __launch_bounds__(NW * 64) void mbx_kernel(MbxArgs a) {
     }
     // operands of the NEXT chunk: in flight during the depthwise phase, older than its stores
     if (c0 + 32 < a.Cmid) load_params(c0 + 32, nxt);
-    MBX_STAMP();
     __syncthreads();
-    MBX_STAMP();
     // ---- depthwise on E for channel c0 + c
     float ssum = 0.f;
     if (dcol && oy < a.Ho) {
@@ -1044,7 +1020,6 @@ __global__ __launch_bounds__(NW * 64) void mbx_kernel(MbxArgs a) {
         }
       }
     }
-    MBX_STAMP();
     if (a.se_partial) {
       red[g * 32 + c] = ssum;
       __syncthreads();
@@ -1056,10 +1031,8 @@ __global__ __launch_bounds__(NW * 64) void mbx_kernel(MbxArgs a) {
       }
     }
     __syncthreads();   // E (and red) are rewritten by the next channel chunk
-    MBX_STAMP();
     cur = nxt;
   }
-#undef MBX_STAMP
 }
 
 bool mbx_supported(int Cin, int Cmid, int k, int stride) {
@@ -1071,8 +1044,9 @@ int mbx_tiles(int Ho, int Wo, int k, int stride) {
   return ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw);
 }
 
-template <int K, int S, int KS, int NW>
+template <int K, int S, int KS>
 static void launch_mbx_t(const MbxArgs& a, int rows, hipStream_t s) {
+  constexpr int NW = 4;
   constexpr int TH = mbx_cfg(K, S).th, TW = mbx_cfg(K, S).tw;
   constexpr int IH = (TH - 1) * S + K, IW = (TW - 1) * S + K;
   constexpr int NPP = (IH * IW + 31) / 32 * 32;
@@ -1086,45 +1060,18 @@ static void launch_mbx_t(const MbxArgs& a, int rows, hipStream_t s) {
   hipLaunchKernelGGL((mbx_kernel<K, S, KS, NW>), grid, dim3(NW * 64), lds, s, a);
 }
 
-template <int K, int S, int NW>
-static void launch_mbx_nw(const MbxArgs& a, int rows, hipStream_t s) {
-  switch (a.Cin) {
-    case 16: launch_mbx_t<K, S, 8, NW>(a, rows, s); break;
-    case 24: launch_mbx_t<K, S, 12, NW>(a, rows, s); break;
-    case 32: launch_mbx_t<K, S, 16, NW>(a, rows, s); break;
-    case 40: launch_mbx_t<K, S, 20, NW>(a, rows, s); break;
-    default: launch_mbx_t<K, S, 24, NW>(a, rows, s); break;   // 48
-  }
-}
-
 template <int K, int S>
 static void launch_mbx_ks(const MbxArgs& a, int rows, hipStream_t s) {
-  static const int nw = uda_env_int("UDA_MBX_WAVES", 4);
-  if (nw == 4) launch_mbx_nw<K, S, 4>(a, rows, s);
-  else launch_mbx_nw<K, S, 8>(a, rows, s);
+  switch (a.Cin) {
+    case 16: launch_mbx_t<K, S, 8>(a, rows, s); break;
+    case 24: launch_mbx_t<K, S, 12>(a, rows, s); break;
+    case 32: launch_mbx_t<K, S, 16>(a, rows, s); break;
+    case 40: launch_mbx_t<K, S, 20>(a, rows, s); break;
+    default: launch_mbx_t<K, S, 24>(a, rows, s); break;   // 48
+  }
 }
 
-void launch_mbx(const MbxArgs& a0, int rows, int k, int stride, hipStream_t s) {
-  MbxArgs a = a0;
-  static unsigned long long* d_stamps = nullptr;
-  static const int want = uda_env_int("UDA_MBX_STAMPS", 0);
-  if (want) {   // diagnostic: dump the stamps of the previous launch, then arm this one
-    static unsigned long long h[8 * 2 * 64];
-    if (!d_stamps) { hipMalloc((void**)&d_stamps, sizeof(h)); hipMemset(d_stamps, 0, sizeof(h)); }
-    else {
-      hipStreamSynchronize(s);
-      hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
-      for (int bz = 0; bz < 2; ++bz)
-        for (int w = 0; w < 2; ++w) {
-          fprintf(stderr, "[mbx stamps z=%d wave%d]", bz, w ? 3 : 0);
-          for (int i = 1; i < 64 && h[(bz * 2 + w) * 64 + i]; ++i)
-            fprintf(stderr, " %llu", h[(bz * 2 + w) * 64 + i] - h[(bz * 2 + w) * 64 + i - 1]);
-          fprintf(stderr, "\n");
-        }
-      hipMemset(d_stamps, 0, sizeof(h));
-    }
-    a.stamps = d_stamps;
-  }
+void launch_mbx(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
   if (k == 3 && stride == 1) launch_mbx_ks<3, 1>(a, rows, s);
   else if (k == 3 && stride == 2) launch_mbx_ks<3, 2>(a, rows, s);
   else if (k == 5 && stride == 1) launch_mbx_ks<5, 1>(a, rows, s);

@@ -589,9 +589,8 @@ static void launch_pwb_cfg(const PwArgs& a, int rows, hipStream_t s) {
   }
   else if (a.wparts == UDA_SPLIT_F16X2) {
     // (K-heavy projections on the big tiles - two blocks per CU by registers anyway: two chunks in flight per block)
-    static const bool deep_on = (uda_env_int("UDA_PWB_DEEP", 1) != 0);
     if constexpr (MT * NT > 4) {
-      if (deep_on && a.Cin >= 384 && a.Cin % PWB_BK == 0 && a.Cout % BN == 0 && (2 * NT * WN * 2 * 64) % 256 == 0) { hipLaunchKernelGGL((pwb_kernel<MT, NT, WM, WN, 4, 2, true>), grid, block, 0, s, a); return; }
+      if (a.Cin >= 384 && a.Cin % PWB_BK == 0 && a.Cout % BN == 0 && (2 * NT * WN * 2 * 64) % 256 == 0) { hipLaunchKernelGGL((pwb_kernel<MT, NT, WM, WN, 4, 2, true>), grid, block, 0, s, a); return; }
     }
     hipLaunchKernelGGL((pwb_kernel<MT, NT, WM, WN, 4, (MT * NT > 4 ? 2 : 3)>), grid, block, 0, s, a);
   }
@@ -608,21 +607,16 @@ void launch_pwb(const PwArgs& a, int rows, hipStream_t s) {
     return;
   }
   if (launch_pws(a, rows, s)) return;
-  static const int force = uda_env_int("UDA_PWB_CFG", 0);
-  static const int wide = uda_env_int("UDA_PWB_WIDE", 1);
-  int cfg = force;
-  if (cfg == 0) {
-    cfg = a.Cout <= 32 ? 1 : (a.Cout <= 64 ? 2 : (a.Cout <= 96 ? 3 : 4));
-    if (wide && a.Cout > 128) {
-      // wide outputs: the column tile (128 / 160 / 192) that leaves the fewest idle columns in the last column block, the
-      // wider one on a tie - 192 channels: one block of 192 instead of 128 + 64 (a quarter of the MFMAs idle, the input
-      // tile read and split twice); 320: 2 x 160; 672: 4 x 192 instead of 6 x 128
-      const int bn[3] = {128, 160, 192}, id[3] = {4, 6, 5};
-      int best = 1 << 30;
-      for (int i = 0; i < 3; ++i) {
-        const int waste = (a.Cout + bn[i] - 1) / bn[i] * bn[i] - a.Cout;
-        if (waste <= best) { best = waste; cfg = id[i]; }
-      }
+  int cfg = a.Cout <= 32 ? 1 : (a.Cout <= 64 ? 2 : (a.Cout <= 96 ? 3 : 4));
+  if (a.Cout > 128) {
+    // wide outputs: the column tile (128 / 160 / 192) that leaves the fewest idle columns in the last column block, the
+    // wider one on a tie - 192 channels: one block of 192 instead of 128 + 64 (a quarter of the MFMAs idle, the input
+    // tile read and split twice); 320: 2 x 160; 672: 4 x 192 instead of 6 x 128
+    const int bn[3] = {128, 160, 192}, id[3] = {4, 6, 5};
+    int best = 1 << 30;
+    for (int i = 0; i < 3; ++i) {
+      const int waste = (a.Cout + bn[i] - 1) / bn[i] * bn[i] - a.Cout;
+      if (waste <= best) { best = waste; cfg = id[i]; }
     }
   }
   switch (cfg) {
@@ -1145,9 +1139,8 @@ static void launch_mbxb_t(const MbxArgs& a, int rows, hipStream_t s) {
                      (size_t)KSF * split_np(PARTS) * 64 * sizeof(uint4);
   dim3 grid((a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH, rows);
   MbxArgs b = a;
-  static const int remap = uda_env_int("UDA_MBX_REMAP", 1);
   b.remap_T = 0;
-  if (remap && a.in_div > 1 && rows % a.in_div == 0) {      // input shared by the samples of an image: XCD-grouped 1-D grid
+  if (a.in_div > 1 && rows % a.in_div == 0) {      // input shared by the samples of an image: XCD-grouped 1-D grid
     const long long nt = (long long)grid.x * grid.y, ntp = (nt + 7) / 8 * 8;
     const long long total = ntp * rows;
     if (total < (1ll << 31)) {
@@ -1832,20 +1825,17 @@ __global__ __launch_bounds__(512, 2) void mbxp_kernel(MbxArgs a) {
 // split along the channels until it fills the device (at most 16 ways, at least 2 slabs per block: every group re-reads and re-splits
 // the input tile, which is what bounds the split).  A batch of 32 images never splits; one image with T = 10 has 60-90 blocks of 36
 // slabs each in the last blocks (4 groups), one image under head-only MC 9 blocks (16 groups: fused MBConv time of a one-image serve
-// 0.47 -> 0.37 ms against the 4-way limit of round 4; UDA_MBX_SPLIT_MAX / UDA_MBX_SPLIT_SLABS, A/B in one job).  UDA_MBX_SPLIT=0: never.
+// 0.47 -> 0.37 ms against the 4-way limit of round 4, A/B in one job).
 // The slabs of a tile are independent: the result does not depend on the split.
 static int mbx_ch_groups(long long blocks, int per_cu, int n_slabs) {
-  static int on = -1, n_cu = 0, gmax = 16, smin = 2;
-  if (on < 0) {
-    const char* e = getenv("UDA_MBX_SPLIT");
-    on = e ? atoi(e) : 1;
-    if (const char* m = getenv("UDA_MBX_SPLIT_MAX")) gmax = atoi(m) > 0 ? atoi(m) : 16;
-    if (const char* m = getenv("UDA_MBX_SPLIT_SLABS")) smin = atoi(m) > 0 ? atoi(m) : 2;
+  constexpr int gmax = 16, smin = 2;
+  static int n_cu = -1;
+  if (n_cu < 0) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 0;
     (void)hipGetLastError();
   }
-  if (!on || n_cu <= 0 || blocks <= 0) return 1;
+  if (n_cu <= 0 || blocks <= 0) return 1;
   long long g = (long long)n_cu * per_cu / blocks;
   if (g > gmax) g = gmax;
   if (g > n_slabs / smin) g = n_slabs / smin;
@@ -1880,7 +1870,7 @@ static void launch_mbxp_ts(const MbxArgs& a, int rows, hipStream_t s) {
   if (mbxd_wide(a.Ho, a.Wo, K, 1)) launch_mbxp_tw<K, KSF, true, SCH>(a, rows, s);
   else launch_mbxp_tw<K, KSF, false, SCH>(a, rows, s);
 }
-template <int K, int KSF, int PARTS, int S> static void launch_mbxd_t(const MbxArgs& a, int rows, hipStream_t s);
+template <int K, int KSF, int PARTS, int S, bool WIDE> static void launch_mbxd_tw(const MbxArgs& a, int rows, hipStream_t s);
 template <int K, int KSF>
 static void launch_mbxp_t(const MbxArgs& a, int rows, hipStream_t s) {
   if (a.wparts == UDA_SPLIT_F16X2) {
@@ -1888,7 +1878,7 @@ static void launch_mbxp_t(const MbxArgs& a, int rows, hipStream_t s) {
       // (the fp16 instances of the 3x3 variant on 16-column tiles do not build: hipcc forms the "uniform" store bases of their
       // stores with vector arithmetic and hands the scalar-base store of store_uniform_base a vector register pair; those maps
       // - none at 1280 x 768, where blocks 12-15 take 20-column tiles - run the two-phase kernel)
-      if (!mbxd_wide(a.Ho, a.Wo, K, 1)) { launch_mbxd_t<K, KSF, UDA_SPLIT_F16X2, 1>(a, rows, s); return; }
+      if (!mbxd_wide(a.Ho, a.Wo, K, 1)) { launch_mbxd_tw<K, KSF, UDA_SPLIT_F16X2, 1, false>(a, rows, s); return; }
       launch_mbxp_tw<K, KSF, true, UDA_SPLIT_F16X2>(a, rows, s);
     } else {
       launch_mbxp_ts<K, KSF, UDA_SPLIT_F16X2>(a, rows, s);
@@ -1910,9 +1900,8 @@ size_t mbx_lds_bytes(int Cin, int Cmid, int k, int stride, int scheme, int Ho, i
     const int etw = mbx_et_w(k, stride);
     return ((etw ? (size_t)32 * mbx_et_pitch(etw) : (size_t)npp * 32) + 8 * 32 + 2 * par) * sizeof(float) + (size_t)ksf * npc * 64 * sizeof(uint4);
   }
-  static const int pipe = uda_env_int("UDA_MBXP", 1);
   const bool wide = mbxd_wide(Ho, Wo, k, stride);
-  const bool p2 = pipe && stride == 1 && ksf >= 13 && npc == 2 && !(scheme == UDA_SPLIT_F16X2 && k == 3 && !wide);      // mbxp_kernel
+  const bool p2 = stride == 1 && ksf >= 13 && npc == 2 && !(scheme == UDA_SPLIT_F16X2 && k == 3 && !wide);      // mbxp_kernel
   if (p2) return ((size_t)2 * 256 * 33 + 2 * 16 * 32 + 3 * par + 2 * 32 * nch) * sizeof(float) + (size_t)2 * ksf * 2 * 64 * sizeof(uint4);
   return ((size_t)256 * 33 + 16 * 32 + 2 * par + 2 * 32 * nch) * sizeof(float) + (size_t)ksf * npc * 64 * sizeof(uint4);
 }
@@ -1958,23 +1947,22 @@ static void launch_mbxd_t(const MbxArgs& a, int rows, hipStream_t s) {
   launch_mbxd_tw<K, KSF, PARTS, S, false>(a, rows, s);
 }
 
+template <int K, int PARTS, int S>
+static void launch_mbxd_k(const MbxArgs& a, int rows, int ksf, hipStream_t s) {
+  // the two-piece schemes at stride 1 take mbxp_kernel from 13 k-steps on (launch_mbxd): no instance of this kernel for them
+  constexpr bool PIPED = S == 1 && (PARTS == UDA_SPLIT_BF16X2 || PARTS == UDA_SPLIT_F16X2);
+  if (ksf == 6) launch_mbxd_t<K, 6, PARTS, S>(a, rows, s);
+  else if (ksf == 8) launch_mbxd_t<K, 8, PARTS, S>(a, rows, s);
+  else if constexpr (!PIPED) {
+    if (ksf == 13) launch_mbxd_t<K, 13, PARTS, S>(a, rows, s);
+    else launch_mbxd_t<K, 14, PARTS, S>(a, rows, s);
+  }
+}
+
 template <int PARTS, int S>
 static void launch_mbxd_p(const MbxArgs& a, int rows, int k, int ksf, hipStream_t s) {
-  if (k == 3) {
-    switch (ksf) {
-      case 6: launch_mbxd_t<3, 6, PARTS, S>(a, rows, s); break;
-      case 8: launch_mbxd_t<3, 8, PARTS, S>(a, rows, s); break;
-      case 13: launch_mbxd_t<3, 13, PARTS, S>(a, rows, s); break;
-      default: launch_mbxd_t<3, 14, PARTS, S>(a, rows, s); break;
-    }
-  } else {
-    switch (ksf) {
-      case 6: launch_mbxd_t<5, 6, PARTS, S>(a, rows, s); break;
-      case 8: launch_mbxd_t<5, 8, PARTS, S>(a, rows, s); break;
-      case 13: launch_mbxd_t<5, 13, PARTS, S>(a, rows, s); break;
-      default: launch_mbxd_t<5, 14, PARTS, S>(a, rows, s); break;
-    }
-  }
+  if (k == 3) launch_mbxd_k<3, PARTS, S>(a, rows, ksf, s);
+  else launch_mbxd_k<5, PARTS, S>(a, rows, ksf, s);
 }
 
 void launch_mbxd(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
@@ -1986,7 +1974,6 @@ void launch_mbxd(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
     else launch_mbxd_p<2, 2>(a, rows, k, ksf, s);
     return;
   }
-  static const int pipe = uda_env_int("UDA_MBXP", 1);
   if (a.wparts == UDA_SPLIT_BF16X3) {     // six cross terms: three pieces per operand, the two-phase kernel
     launch_mbxd_p<3, 1>(a, rows, k, ksf, s);
     return;
@@ -1995,7 +1982,7 @@ void launch_mbxd(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
     launch_mbxd_p<5, 1>(a, rows, k, ksf, s);
     return;
   }
-  if (pipe && ksf >= 13) {          // one block per CU anyway: the self-overlapping variant
+  if (ksf >= 13) {                  // one block per CU anyway: the self-overlapping variant
     if (k == 3) { if (ksf == 13) launch_mbxp_t<3, 13>(a, rows, s); else launch_mbxp_t<3, 14>(a, rows, s); }
     else { if (ksf == 13) launch_mbxp_t<5, 13>(a, rows, s); else launch_mbxp_t<5, 14>(a, rows, s); }
     return;

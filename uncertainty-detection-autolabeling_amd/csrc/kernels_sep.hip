@@ -353,14 +353,13 @@ __global__ __launch_bounds__(256, OCC) void sep_kernel(SepMulti m) {
 }
 
 // ---------------------------------------------------------------- separable convolution on an LDS-staged input tile
-// sepf_kernel: the same arithmetic as sep_kernel (same depthwise FMA order, same split, same MFMA order: bit-identical
-// outputs), organised around an input tile in LDS instead of a depthwise image in LDS, so that the INPUT can be something
+// sepf_kernel: the same arithmetic as sep_kernel (same depthwise FMA order, same split, same MFMA order), organised around an input tile in LDS instead of a depthwise image in LDS, so that the INPUT can be something
 // that is computed rather than read - the BiFPN fusion act(sum_i w_i resample_i(in_i)) of the node the separable conv
 // belongs to (FIN; efficientdet_keras.py:90-136 + 207-227): the fused tensor never goes to HBM, fuse_kernel's launch, its
 // write and this kernel's read of it disappear.
 //   tile      16 x 16 outputs per block of four waves (halo 18 x 18: 1.27x instead of 1.41x for 8 x 16), staged PC = 16 or 32
 //             channels at a time as [324 pixels][PC + 4] float32 (26 / 47 KB; the k-steps of a pass accumulate into the same
-//             accumulators).  16-channel passes (three blocks per CU) for plain and identity + nearest-up inputs; pooled inputs
+//             accumulators).  16-channel passes (three blocks per CU) for identity + nearest-up inputs; pooled inputs
 //             read a 2x larger map, where 64-byte pieces of a pixel doubled the traffic: 32-channel passes (sepf_cfg)
 //   staging   U elements (pixel, channel quad) per thread with ALL their loads in flight before the first use: branch-free
 //             samplers per mode signature (sepf_stage); a generic one-element-at-a-time loop for anything else
@@ -446,15 +445,14 @@ __device__ __forceinline__ float4 fuse_value_t(const FuseArgs& a, int b, int y, 
 }
 
 // mode signatures with a batched staging path (everything else: the generic, one-element-at-a-time loop)
-enum { SF_SIG_GENERIC = 0, SF_SIG_PLAIN = 1, SF_SIG_NU = 2, SF_SIG_NNP = 3, SF_SIG_NP = 4 };
+enum { SF_SIG_GENERIC = 0, SF_SIG_NU = 2, SF_SIG_NNP = 3, SF_SIG_NP = 4 };
 
 // Stage one 32-channel pass of the 18 x 18 input tile: U elements (pixel, channel quad) per thread and round with ALL their
 // loads in flight before the first use - the block has one memory latency per round, not one per element.
 template <int SIG, int U, int PC>
-__device__ __forceinline__ void sepf_stage(const SepArgs& a, const FuseArgs& f, float* T, const float* inb, int b, int oy0, int ox0,
-                                           int c0, int pc4, int tid) {
+__device__ __forceinline__ void sepf_stage(const SepArgs& a, const FuseArgs& f, float* T, int b, int oy0, int ox0, int c0, int pc4, int tid) {
   constexpr int SF_PITCH = PC + 4, FULL4 = PC / 4;
-  const int H = a.H, W = a.W, C = a.C;
+  const int H = a.H, W = a.W;
   const int ne = SF_NPX * pc4;
   for (int e0 = tid; e0 < ne; e0 += 256 * U) {
     float4 v[U];
@@ -468,8 +466,7 @@ __device__ __forceinline__ void sepf_stage(const SepArgs& a, const FuseArgs& f, 
       const int yc = min(max(y, 0), H - 1), xc = min(max(x, 0), W - 1);
       const int c4 = (c0 >> 2) + q;
       float4 t;
-      if constexpr (SIG == SF_SIG_PLAIN) t = *(const float4*)(inb + ((size_t)yc * W + xc) * C + 4 * c4);
-      else if constexpr (SIG == SF_SIG_NU) t = fuse_value_t<UDA_RS_NONE, UDA_RS_NEAREST_UP, -1>(f, b, yc, xc, c4);
+      if constexpr (SIG == SF_SIG_NU) t = fuse_value_t<UDA_RS_NONE, UDA_RS_NEAREST_UP, -1>(f, b, yc, xc, c4);
       else if constexpr (SIG == SF_SIG_NNP) t = fuse_value_t<UDA_RS_NONE, UDA_RS_NONE, UDA_RS_MAXPOOL>(f, b, yc, xc, c4);
       else t = fuse_value_t<UDA_RS_NONE, UDA_RS_MAXPOOL, -1>(f, b, yc, xc, c4);
       v[u] = inside ? t : make_float4(0.f, 0.f, 0.f, 0.f);     // SAME padding of the depthwise conv: zeros outside the map
@@ -512,8 +509,11 @@ static void sepf_stamp_dump() {
 // D1 ... D3) hold 96 / 128 accumulator registers per lane: at the 168 registers of three blocks per CU the compiler spilled
 // 50-150 of them and the scratch traffic was 3.4-4.5x the kernel's algorithmic bytes (profiles/r05_d2_per_op.txt, round 5:
 // the D2 BiFPN nodes at 1.2 TB/s algorithmic with 5.4 TB/s on the counters) - those shapes take two blocks per CU.
+// (FIN: the input is a fusion.  Every instance has it set; it stays in the signature so that the kernels keep the names the
+// recorded profiles know them by.)
 template <int NT, int PARTS, bool FIN, int PC>
 __global__ __launch_bounds__(256, (PC == 16 && NT <= 2) ? 3 : 2) void sepf_kernel(SepArgs a, FuseArgs f, int sig, int rows) {
+  static_assert(FIN, "sepf_kernel stages a fusion; a plain input takes sep_kernel");
   extern __shared__ __attribute__((aligned(16))) unsigned char slds[];
   constexpr int NPC = split_np(PARTS);
   constexpr int SF_PC = PC, SF_PITCH = PC + 4;
@@ -547,7 +547,6 @@ __global__ __launch_bounds__(256, (PC == 16 && NT <= 2) ? 3 : 2) void sepf_kerne
   const int pr = 4 * wave + 2 * lh + (li >> 4), pcx = li & 15;
   const float* tbase = T + (pr * SF_TP + pcx) * SF_PITCH;
   const uint4* Wp = (const uint4*)a.wsplit;
-  const float* inb = FIN ? nullptr : a.in + (size_t)(b / a.in_div) * H * W * C;
 
   f32x16 acc[2][NT];
 #pragma unroll
@@ -577,17 +576,15 @@ __global__ __launch_bounds__(256, (PC == 16 && NT <= 2) ? 3 : 2) void sepf_kerne
       const int nt = q % NT, ksl = q / NT;
       Bs[i] = nt < NTL ? Wp[(((size_t)(ps * (PC / 16) + ksl) * NTL + nt) * NPC + part) * 64 + (i & 63)] : make_uint4(0u, 0u, 0u, 0u);
     }
-    if constexpr (!FIN) {
-      sepf_stage<SF_SIG_PLAIN, PC == 16 ? 6 : 11, PC>(a, f, T, inb, b, oy0, ox0, c0, pc4, tid);
-    } else if (sig == SF_SIG_NU) {
-      // (identity + nearest-up nodes run 16-channel passes, sepf_pc: the 32-channel instance of this branch only exists for
-      // UDA_SEPF_PC=32 A/B runs and must not set the register count of the kernel the pooled nodes use - 11 elements of two
-      // inputs in flight were 88 registers, the pooled nodes' kernel spilled 50-115 of them)
-      sepf_stage<SF_SIG_NU, PC == 16 ? 6 : 2, PC>(a, f, T, inb, b, oy0, ox0, c0, pc4, tid);
+    if (sig == SF_SIG_NU) {
+      // (identity + nearest-up nodes run 16-channel passes, sepf_pc: the 32-channel instance of this branch is never taken
+      // and must not set the register count of the kernel the pooled nodes use - 11 elements of two inputs in flight were
+      // 88 registers, the pooled nodes' kernel spilled 50-115 of them)
+      sepf_stage<SF_SIG_NU, PC == 16 ? 6 : 2, PC>(a, f, T, b, oy0, ox0, c0, pc4, tid);
     } else if (sig == SF_SIG_NNP) {
-      sepf_stage<SF_SIG_NNP, (PC == 16 || NT > 2) ? 1 : 3, PC>(a, f, T, inb, b, oy0, ox0, c0, pc4, tid);      // (11 loads per element: one element in flight beside 96+ accumulators)
+      sepf_stage<SF_SIG_NNP, (PC == 16 || NT > 2) ? 1 : 3, PC>(a, f, T, b, oy0, ox0, c0, pc4, tid);      // (11 loads per element: one element in flight beside 96+ accumulators)
     } else if (sig == SF_SIG_NP) {
-      sepf_stage<SF_SIG_NP, (PC == 16 || NT > 2) ? 1 : 3, PC>(a, f, T, inb, b, oy0, ox0, c0, pc4, tid);
+      sepf_stage<SF_SIG_NP, (PC == 16 || NT > 2) ? 1 : 3, PC>(a, f, T, b, oy0, ox0, c0, pc4, tid);
     } else {
       for (int e = tid; e < SF_NPX * pc4; e += 256) {
         const int px = e / pc4, q = e - px * pc4;
@@ -709,13 +706,9 @@ __global__ __launch_bounds__(256, (PC == 16 && NT <= 2) ? 3 : 2) void sepf_kerne
 #endif
 }
 
-// channels per pass per staging signature: plain and identity + nearest-up inputs run 16-channel passes; pooled inputs read a
+// channels per pass per staging signature: identity + nearest-up inputs run 16-channel passes; pooled inputs read a
 // 2x larger map, where 64-byte pieces of a pixel doubled the traffic (half-used 128-byte lines): 32-channel passes.
-// UDA_SEPF_PC = 16 | 32 forces one (A/B).
-static int sepf_pc(int sig) {
-  static const int epc = uda_env_int("UDA_SEPF_PC", 0);
-  return epc == 16 || epc == 32 ? epc : ((sig == SF_SIG_PLAIN || sig == SF_SIG_NU) ? 16 : 32);
-}
+static int sepf_pc(int sig) { return sig == SF_SIG_NU ? 16 : 32; }
 
 size_t sepf_lds_bytes(int C, int Cout, int scheme) {      // (the larger of the configurations)
   const int nt = (Cout + 31) / 32, npc = uda_split_pieces(scheme);
@@ -729,13 +722,12 @@ bool sepf_supported(int C, int Cout, int scheme) {
          sepf_lds_bytes(C, Cout, scheme) <= 80 * 1024;
 }
 
-template <int NT, bool FIN>
+template <int NT>
 static void launch_sepf_nt(const SepArgs& a, const FuseArgs& f, int rows, hipStream_t s) {
   const dim3 grid(((a.W + SF_T - 1) / SF_T) * ((a.H + SF_T - 1) / SF_T) * rows);
   // which batched staging path fits the fusion (uniform switch inside the kernel)
   int sig = SF_SIG_GENERIC;
-  if (!FIN) sig = SF_SIG_PLAIN;
-  else if (f.act == UDA_ACT_SWISH && !getenv("UDA_SEPF_GENERIC")) {
+  if (f.act == UDA_ACT_SWISH) {
     auto pool_ok = [&](int i) { return f.mode[i] == UDA_RS_MAXPOOL && f.pk[i] == 3 && f.ps[i] == 2; };
     if (f.n_in == 2 && f.mode[0] == UDA_RS_NONE && f.mode[1] == UDA_RS_NEAREST_UP) sig = SF_SIG_NU;
     else if (f.n_in == 3 && f.mode[0] == UDA_RS_NONE && f.mode[1] == UDA_RS_NONE && pool_ok(2)) sig = SF_SIG_NNP;
@@ -760,28 +752,22 @@ static void launch_sepf_nt(const SepArgs& a, const FuseArgs& f, int rows, hipStr
   };
   auto by_scheme = [&](auto pcv) {
     constexpr int PC = decltype(pcv)::value;
-    if (a.wparts == UDA_SPLIT_BF16X3) go(sepf_kernel<NT, 3, FIN, PC>);
-    else if (a.wparts == UDA_SPLIT_F16X2) go(sepf_kernel<NT, 4, FIN, PC>);
-    else if (a.wparts == UDA_SPLIT_F16X1) go(sepf_kernel<NT, 5, FIN, PC>);
-    else go(sepf_kernel<NT, 2, FIN, PC>);
+    if (a.wparts == UDA_SPLIT_BF16X3) go(sepf_kernel<NT, 3, true, PC>);
+    else if (a.wparts == UDA_SPLIT_F16X2) go(sepf_kernel<NT, 4, true, PC>);
+    else if (a.wparts == UDA_SPLIT_F16X1) go(sepf_kernel<NT, 5, true, PC>);
+    else go(sepf_kernel<NT, 2, true, PC>);
   };
   if (pc == 16) by_scheme(std::integral_constant<int, 16>{});
   else by_scheme(std::integral_constant<int, 32>{});
 }
 
-// fused != nullptr: the conv's input is the BiFPN fusion described by *fused (a.in unused)
-void launch_sepf(const SepArgs& a, const FuseArgs* fused, int rows, hipStream_t s) {
+// the conv's input is the BiFPN fusion described by f (a.in unused)
+void launch_sepf(const SepArgs& a, const FuseArgs& f, int rows, hipStream_t s) {
   const int ntl = (a.Cout + 31) / 32;
-  FuseArgs f{};
-  if (fused) f = *fused;
-  auto pick = [&](auto fin) {
-    constexpr bool FIN = decltype(fin)::value;
-    if (ntl == 1) launch_sepf_nt<1, FIN>(a, f, rows, s);
-    else if (ntl == 2) launch_sepf_nt<2, FIN>(a, f, rows, s);
-    else if (ntl == 3) launch_sepf_nt<3, FIN>(a, f, rows, s);
-    else launch_sepf_nt<4, FIN>(a, f, rows, s);
-  };
-  if (fused) pick(std::true_type{}); else pick(std::false_type{});
+  if (ntl == 1) launch_sepf_nt<1>(a, f, rows, s);
+  else if (ntl == 2) launch_sepf_nt<2>(a, f, rows, s);
+  else if (ntl == 3) launch_sepf_nt<3>(a, f, rows, s);
+  else launch_sepf_nt<4>(a, f, rows, s);
 }
 
 bool sep_supported(int C, int Cout) { return C % 8 == 0 && C >= 16 && C <= 128 && Cout >= 1; }
@@ -813,9 +799,8 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
   if (lds < stg) lds = stg;
   SepMulti mm = m;
   mm.tiles = m.n_lv > 0 ? m.tile0[m.n_lv] : sep_tiles(a.H, a.W);
-  static const bool remap = (uda_env_int("UDA_SEP_REMAP", 1) != 0);     // (0: plain block order, A/B)
   if (tin) rows /= a.in_div;
-  mm.rows = remap ? rows : 0;
+  mm.rows = rows;
   const dim3 grid(mm.tiles * rows, gy);
   auto go = [&](auto kern) {
     static size_t attr_lds = 64 * 1024;
@@ -825,7 +810,6 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
     }
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, mm);
   };
-  static const int occ = uda_env_int("UDA_SEP_OCC", 3);   // 3 blocks per CU: measured 14 % faster than 2
   if (tin) {
     // (head layers: C = F, Cout = F | 9 C | 36 / 72: two to four column tiles; 32 / 64 more registers than the plain kernel)
     if constexpr (NT >= 2) {
@@ -844,11 +828,12 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
     }
     return;
   }
-  if (a.wparts == UDA_SPLIT_BF16X3) { if (occ >= 3 && NT <= 2) go(sep_kernel<NT, 3, 3>); else go(sep_kernel<NT, 3, 2>); }
-  else if (a.wparts == UDA_SPLIT_F16X2) { if (occ >= 3 && NT <= 2) go(sep_kernel<NT, 4, 3>); else go(sep_kernel<NT, 4, 2>); }
-  else if (a.wparts == UDA_SPLIT_F16X1) { if (occ >= 3 && NT <= 2) go(sep_kernel<NT, 5, 3>); else go(sep_kernel<NT, 5, 2>); }
-  else if (occ >= 3 && NT <= 2) go(sep_kernel<NT, 2, 3>);
-  else go(sep_kernel<NT, 2, 2>);
+  // 3 blocks per CU for one or two column tiles: measured 14 % faster than 2
+  constexpr int OCC = NT <= 2 ? 3 : 2;
+  if (a.wparts == UDA_SPLIT_BF16X3) go(sep_kernel<NT, 3, OCC>);
+  else if (a.wparts == UDA_SPLIT_F16X2) go(sep_kernel<NT, 4, OCC>);
+  else if (a.wparts == UDA_SPLIT_F16X1) go(sep_kernel<NT, 5, OCC>);
+  else go(sep_kernel<NT, 2, OCC>);
 }
 
 // Dynamic LDS of the launch launch_sep_any will make for a C -> Cout separable conv (see launch_sep_nt): checked by uda_create

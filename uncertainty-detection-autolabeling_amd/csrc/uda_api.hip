@@ -342,15 +342,11 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
         if (o.w_off < 0) continue;
         const int K = bufs[o.in[0]].C, Nn = bufs[o.out].C;
         const size_t at = packed.size();
-        // diagnostic: UDA_F16_KINDS=pw,sep,mbx (any subset) keeps fp16 pieces for those op kinds only, three bf16 pieces elsewhere
-        static const char* f16_kinds = getenv("UDA_F16_KINDS");
-        const bool kind_f16 = !f16_kinds || strstr(f16_kinds, o.kind == UDA_OP_PW ? "pw" : (o.kind == UDA_OP_SEP ? "sep" : "mbx")) != nullptr;
         if (o.kind == UDA_OP_PW || o.kind == UDA_OP_SEP) {
           // fp16 pieces: the kernel times a power of two that puts its largest entry in [2^13, 2^14) - every low piece of a
           // weight that matters is then a normal fp16 number; the epilogue multiplies the accumulator by the inverse (exact)
           float scale = 1.0f;
-          int sch = c->pw_parts;
-          if (uda_split_f16(sch) && !kind_f16) sch = UDA_SPLIT_BF16X3;
+          const int sch = c->pw_parts;
           if (uda_split_f16(sch)) {
             scale = split_weight_scale(weights + o.w_off, (size_t)K * Nn);
             c->wunscale[i] = 1.0f / scale;
@@ -362,14 +358,14 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
           // BiFPN / head feature times nine small taps: rms 0.01-0.1 under the reference initialisers - its low pieces would
           // all be subnormal, 2^-25 absolute instead of 2^-22 relative: measured 3.2e-6 / 6.2e-6 relative rms on the heads of
           // D0 / D2, all of it from these ops; with the shift 2.4e-7 / 3.1e-7, the float32 floor of 2.3e-7 / 3.3e-7 that three
-          // bf16 pieces reach).  The depthwise kernel is therefore applied times 2^UDA_F16_SEP_SHIFT (default 6; a host-side copy
+          // bf16 pieces reach).  The depthwise kernel is therefore applied times 2^SEP_F16_TAP_SHIFT (a host-side copy
           // of the 9 x C taps behind the packed 1x1 kernel, no device cost) and the epilogue's factor carries the inverse;
           // the range flag watches the scaled values (65504 / 64 = 1023 for the depthwise result itself).
           size_t dw_fl = 0;
           float ascale = 1.0f;
           if (o.kind == UDA_OP_SEP && uda_split_f16(sch) && o.w2_off >= 0) {
-            static const int shift = uda_env_int("UDA_F16_SEP_SHIFT", 6);
-            ascale = ldexpf(1.0f, shift < 0 ? 0 : (shift > 12 ? 12 : shift));
+            constexpr int SEP_F16_TAP_SHIFT = 6;
+            ascale = ldexpf(1.0f, SEP_F16_TAP_SHIFT);
             dw_fl = (size_t)9 * K;
           }
           packed.resize(at + w_elems + 2 * dw_fl);
@@ -401,7 +397,7 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
             mbxb_pack_weights(weights + o.w_off, weights + o.bn_scale_off, weights + o.bn_shift_off, Ke, Nn, probe.data(), fuse0, sch, st);
             static const float min_rms = getenv("UDA_F16_MIN_RMS") ? (float)atof(getenv("UDA_F16_MIN_RMS")) : 0.015625f;
             const bool rms_ok = sch == UDA_SPLIT_F16X1 || st[1] >= min_rms;
-            if (!(st[0] < 32768.0f) || !rms_ok || !kind_f16) { sch = UDA_SPLIT_BF16X3; ++c->n_f16_demoted; }
+            if (!(st[0] < 32768.0f) || !rms_ok) { sch = UDA_SPLIT_BF16X3; ++c->n_f16_demoted; }
             else ++c->n_f16_ops;
           }
           c->wscheme[i] = sch;
@@ -1015,8 +1011,7 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
           a.c0 = ib.C;
           a.w0t = a.wpar + mbx_par_floats(ob.C, o.k);
           a.sh0f = a.w0t + 32 * 32;
-          static const bool pre = (uda_env_int("UDA_W0GATE", 1) != 0);   // 0: every block redoes the prep
-          if (pre && ib.C == 32) {
+          if (ib.C == 32) {      // (other widths: every block does the prep itself)
             // one buffer per chunk lane: with UDA_LANES=2 consecutive chunks run concurrently on two streams, each with its
             // own gates - lane 1's prep must not overwrite the fragments lane 0's block-1 kernel is still reading
             const int gate_rows = v.rows(gb);
@@ -1070,13 +1065,11 @@ static int run_op(uda_ctx* c, const ChunkView& v, int oi) {
         f.act = o.fuse_act;
         if (!sepf_supported(a.C, a.Cout, a.wparts)) return fail(c, "op %d: fused-input separable conv %d -> %d not supported", oi, a.C, a.Cout);
         a.in = nullptr;
-        launch_sepf(a, &f, rows, v.stream());
+        launch_sepf(a, f, rows, v.stream());
         break;
       }
       if (ib.H != ob.H || ib.W != ob.W) return fail(c, "op %d: separable conv changes the map size", oi);
-      static const int sepf_all = uda_env_int("UDA_SEPF_ALL", 0);     // A/B: the tile kernel for every conv
-      if (sepf_all && sepf_supported(a.C, a.Cout, a.wparts)) launch_sepf(a, nullptr, rows, v.stream());
-      else launch_sep(a, rows, v.stream());
+      launch_sep(a, rows, v.stream());
       break;
     }
     case UDA_OP_SE: {
@@ -1264,8 +1257,7 @@ static int run_network(uda_ctx* c, int post_mode = 0, bool chunk_post = false, h
         gated = true;
       }
       const int grp = c->ops[oi].launch_group;
-      static const bool sepf_all_ = (uda_env_int("UDA_SEPF_ALL", 0) != 0);     // A/B: per-level tile-kernel launches
-      if (grp > 1 && !sepf_all_) {
+      if (grp > 1) {
         const int rg = run_sep_group(c, v, oi, grp);
         if (rg > 0) return rg;
         if (rg == 0) {

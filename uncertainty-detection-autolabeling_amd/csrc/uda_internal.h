@@ -172,9 +172,9 @@ void launch_sep_multi(const SepArgs& common, const SepLevel* lv, int n_lv, int r
 bool sep_supported(int C, int Cout);
 size_t sep_lds_bytes(int C, int Cout, int scheme, bool tin = false);      // dynamic LDS of the launch an op of this shape gets
 struct FuseArgs;
-// The same conv on an LDS-staged 16 x 16 tile (kernels_sep.hip: sepf_kernel); with `fused` the input is the BiFPN fusion
-// described there, computed on the fly (a.in unused).  Outputs are bit-identical to launch_sep's.
-void launch_sepf(const SepArgs& a, const FuseArgs* fused, int rows, hipStream_t s);
+// The same conv on an LDS-staged 16 x 16 tile (kernels_sep.hip: sepf_kernel) whose input is the BiFPN fusion described by
+// `fused`, computed on the fly (a.in unused).
+void launch_sepf(const SepArgs& a, const FuseArgs& fused, int rows, hipStream_t s);
 bool sepf_supported(int C, int Cout, int scheme);
 size_t sepf_lds_bytes(int C, int Cout, int scheme);
 
@@ -213,7 +213,6 @@ struct MbxArgs {
   int pad_t, pad_l;
   int in_div;
   int n_tiles;
-  unsigned long long* stamps;  // diagnostic phase stamps (UDA_MBX_STAMPS); null in production
   const void* wsplit;     // expand kernel * BN scale (+ BN shift row) as split fragments (kernels_pwb.hip) or null
   int wparts;             // split scheme of wsplit (UDA_SPLIT_*)
   unsigned* oor;          // fp16 pieces: out-of-range flag word (see PwArgs) or null

@@ -58,8 +58,7 @@ PW_SCHEME_CODES = {"f32": 0, "bf16x2": 2, "bf16x3": 3, "f16x2": 4, "f16": 5}    
 # The planner's on/off switches (environment, read once per Plan into Plan.sw) and their defaults; "0" turns a fusion off.  The
 # library reads none of them: an op the planner does not emit / a launch_group it does not set is what turns a fusion off.
 PLAN_SWITCHES = {"UDA_DEFER_DROPOUT": 1, "UDA_FUSE_SEP": 1, "UDA_FUSE_PROJ": 1, "UDA_FUSE_MBX": 1, "UDA_FUSE_MBX6": 1,
-                 "UDA_FUSE_MBXD": 1, "UDA_FUSE_MBXD_S2": 1, "UDA_MBXD_MAXKSF": 14, "UDA_FUSE_IN": 1, "UDA_DEFER_HEAD": 1,
-                 "UDA_SEP_MULTI": 1}
+                 "UDA_FUSE_MBXD": 1, "UDA_FUSE_IN": 1, "UDA_SEP_MULTI": 1}
 
 
 def pw_scheme():
@@ -314,7 +313,7 @@ class Plan:
         self.fuse_sep = bool(sw["UDA_FUSE_SEP"]) and split
         self.fuse_proj = bool(sw["UDA_FUSE_PROJ"]) and split and bool(sw["UDA_FUSE_MBX"])
         self.fuse_in = self.fuse_sep and bool(sw["UDA_FUSE_IN"])          # BiFPN fusion inside the node's separable conv
-        self.defer_head = self.fuse_sep and bool(sw["UDA_DEFER_HEAD"])    # head dropout site handed to the next layer
+        self.defer_head = self.fuse_sep                                    # head dropout site handed to the next layer
         if self.post_only:
             self._post_only_layout()
             return
@@ -484,12 +483,12 @@ class Plan:
 
     def _fuse_mbx(self, cin, cmid, k, stride):
         """The block's expand + depthwise are lowered to one fused op: a kernel exists and no switch turns it off."""
-        sw, ksf = self.sw, (cin + 1 + 15) // 16
+        sw = self.sw
         if not sw["UDA_FUSE_MBX"] or (self.pw_scheme == "bf16x3" and not sw["UDA_FUSE_MBX6"]):
             # (six cross terms: the fused kernels have three-piece variants and stay fused; UDA_FUSE_MBX6=0 restores the
             # round-2 behaviour - stand-alone six-term 1x1 convs + depthwise - for A/B runs)
             return False
-        if mbx_deep(cin) and not (sw["UDA_FUSE_MBXD"] and (stride == 1 or sw["UDA_FUSE_MBXD_S2"]) and ksf <= sw["UDA_MBXD_MAXKSF"]):
+        if mbx_deep(cin) and not sw["UDA_FUSE_MBXD"]:
             return False
         return mbx_supported(cin, cmid, k, stride, self.pw_scheme)
 
