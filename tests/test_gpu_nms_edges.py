@@ -102,7 +102,7 @@ d.close()
 
 
 def _nms_chunk():
-    """NMS_CHUNK of the build: 256 * UDA_NMS_ITEMS (csrc/kernels_post.hip, unless the Makefile defines it)."""
+    """NMS_CHUNK of the build: 256 * UDA_NMS_ITEMS (csrc/kernels_nms.hip, unless the Makefile defines it)."""
     csrc = os.path.join(ROOT, "uncertainty-detection-autolabeling_amd", "csrc")
     items = None
     with open(os.path.join(csrc, "Makefile")) as f:
@@ -110,7 +110,7 @@ def _nms_chunk():
         if m:
             items = int(m.group(1))
     if items is None:
-        with open(os.path.join(csrc, "kernels_post.hip")) as f:
+        with open(os.path.join(csrc, "kernels_nms.hip")) as f:
             items = int(re.search(r"#define UDA_NMS_ITEMS (\d+)", f.read()).group(1))
     return 256 * items
 

@@ -1,4 +1,4 @@
-"""CPU model of the epoch-synchronous NMS of csrc/kernels_post.hip WITH several winners per grid-wide step
+"""CPU model of the epoch-synchronous NMS of csrc/kernels_nms.hip WITH several winners per grid-wide step
 (nms_coop_kernel, round 5), checked bit for bit against the oracle's plain-C NonMaxSuppressionV5 twin.
 
 The model states the rule the kernel implements, in the kernel's own terms (stale score / begin per candidate, cached

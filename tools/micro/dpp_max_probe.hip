@@ -1,4 +1,4 @@
-// Probe (GPU box): the DPP wave reduction of kernels_post.hip (wave_max_key) against a shuffle reduction on random keys.
+// Probe (GPU box): the DPP wave reduction of kernels_nms.hip (wave_max_key) against a shuffle reduction on random keys.
 //   hipcc --offload-arch=gfx950 -O2 tools/micro/dpp_max_probe.hip -o /tmp/dpp_probe && /tmp/dpp_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -1,5 +1,5 @@
 // Probe (GPU box): what ONE grid-wide exchange of the cooperative NMS costs when nothing else happens - the protocol of
-// coop_exchange_top (kernels_post.hip): every block stores one 64-bit word (relaxed, agent scope), wave 0 of every block polls
+// coop_exchange_top (kernels_nms.hip): every block stores one 64-bit word (relaxed, agent scope), wave 0 of every block polls
 // the problem's words until none is 0.  STEPS exchanges back to back on fresh slots, `bpi` blocks of 1024 threads.
 //   spread : blocks 0 .. bpi-1 of the grid (dealt round-robin over the 8 XCDs)
 //   one XCD: a grid of 8 x bpi blocks in which only the blocks with blockIdx % 8 == 0 take part (the others leave at once)

@@ -295,7 +295,7 @@ void launch_philox_masks(float* masks, const int64_t* site_off_dev, const int32_
                          const float* site_rate_dev, int n_sites, int rows, uint32_t row_base, int max_c4,
                          uint64_t seed, int t_local, int t_total, int t_first, int t_stride, hipStream_t s);
 
-// ---------------------------------------------------------------- post-process (kernels_post.hip)
+// ---------------------------------------------------------------- post-process (kernels_post.hip, NMS: kernels_nms.hip)
 struct LevelTable {
   int num_levels;
   int hw[UDA_MAX_LEVELS];
@@ -500,8 +500,7 @@ struct NmsArgs {
 };
 void launch_nms_init(const NmsArgs& a, const float* scores, hipStream_t s);
 void launch_nms_epoch(const NmsArgs& a, int epoch, hipStream_t s);
-void launch_nms_finish(const NmsArgs& a, int pad, hipStream_t s);
-// all epochs in one launch, one block per problem (kernels_post.hip "NMS, one launch")
+// all epochs in one launch, one block per problem (kernels_nms.hip "NMS, one launch")
 bool nms_solo_supported(const NmsArgs& a);
 void launch_nms_solo(const NmsArgs& a, const float* scores, hipStream_t s);
 // the same with the per-candidate state in registers, problems of up to 8192 candidates
@@ -512,7 +511,7 @@ void launch_nms_reg(const NmsArgs& a, const float* scores, hipStream_t s);
 size_t nms_coop_slot_words(int M);
 int launch_nms_coop(const NmsArgs& a, const float* scores, unsigned long long* slots, int* err, hipStream_t s);   // 1 launched, 0 not its domain, -1 wanted but not launched
 
-// NMS on the top-scoring prefix of a large candidate set (kernels_post.hip "NMS on a score prefix")
+// NMS on the top-scoring prefix of a large candidate set (kernels_nms.hip "NMS on a score prefix")
 struct PrefixArgs {
   const float* scores;   // [n, K]
   const float* boxes;    // [n, K, 4]
