@@ -26,6 +26,8 @@
  *                            collects (custom_cocoeval.py:265-349; coco_metric.py:219-283)
  *   uda_thr_objective_np  <- roc_metrics for the candidates of UncertOptimal._extract_optimal_params
  *                            (uncertainty_analysis.py:44-152)
+ *   uda_hash_neighbors_np <- the distance matrix, its maximum and the rows of near-duplicates of
+ *                            ActiveLearning.extract_hash_matrix (active_learning_loop.py:240-270)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -531,6 +533,29 @@ int uda_eval_match_np(int32_t device, const float* det_rows, const float* gt, in
 int uda_thr_objective_np(int32_t device, const double* uncerts, const double* ious, const uint8_t* tp_class, const int32_t* group,
                          int32_t N, int32_t U, int32_t G, const double* iou_thrs, int32_t K, const double* params, int32_t P,
                          int32_t fix_cd, double budget, double* thr, double* rate, double* auc);
+
+/* Dataset pruning: the quadratic part of the active-learning loop's `prune` strategies (ActiveLearning.extract_hash_matrix,
+ * active_learning_loop.py:198-316) - for N image hashes the maximum Hamming distance over all pairs and, per image, the images
+ * within a limit of it - without a handle and without the N x N matrix the reference builds (:240-245).  The draws, the removal
+ * and the budget (:281-314) are the caller's (dataset_pruning.py).
+ *   hashes     [N, W] uint64, W = 1..4 words of 64 hash bits (imagehash's hash_size 8 is W = 1, 16 is W = 4); any packing order,
+ *              as long as every hash uses the same one.  1 <= N <= UDA_PRUNE_MAX_N
+ *   distance   d(i, j) = sum over the W words of popcount(a ^ b) (ImageHash.__sub__); *max_dist = max over all i, j (:264)
+ *   limit      max_distance >= 0: that many bits, prune_thr is not read; else the float64 product (double)*max_dist * prune_thr
+ *              (:267), prune_thr >= 0 and finite.  Column j is in row i iff (double)d(i, j) <= limit: inclusive, i itself included
+ *   result     CSR: row i is idx[row_off[i] .. row_off[i + 1]), ascending (np.where(...)[0]); row_off [N + 1] int64,
+ *              *total = row_off[N].  max_dist, row_off and total are always written; idx is written only when it is not NULL and
+ *              *total <= cap (its capacity in entries): NULL is a count-only call, a short cap leaves idx untouched and the
+ *              caller comes back with cap = *total.  Integer-exact: the result does not depend on how the device cuts the work.
+ *   scratch    allocated and freed inside the call: the hashes, 8 * N * W bytes, counts and cursors of 12 bytes per (row, column
+ *              span) - at most 262144 + N of those - and 8 * (N + 1) for row_off; the index array, 4 * *total bytes, only after
+ *              the total is known, and refused with both sizes in the message when the device does not have them free.
+ * UDA_PRUNE_ROWS rows make a block, one per thread; UDA_PRUNE_COLS column hashes are staged in LDS at a time. */
+#define UDA_PRUNE_ROWS 256
+#define UDA_PRUNE_COLS 512
+#define UDA_PRUNE_MAX_N 1048576
+int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int32_t N, int32_t W, double prune_thr, int32_t max_distance,
+                          int64_t cap, int32_t* max_dist, int64_t* row_off, int32_t* idx, int64_t* total);
 
 /* serve = set_images_u8 + run + get_detections */
 int uda_serve(uda_ctx_t* ctx, const uint8_t* images, int32_t n, int32_t h, int32_t w,

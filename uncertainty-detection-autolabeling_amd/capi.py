@@ -33,6 +33,7 @@ SCORE_MAX_COMP = 3
 PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS, PROF_SCORE, PROF_EVAL, PROF_PSEUDO = 16, 17, 18, 19, 20, 21
 EVAL_MAX_GT, EVAL_MAX_THRS = 256, 32
 THR_MAX_N, THR_MAX_U, THR_MAX_THRS, THR_MAX_P, THR_MAX_G = 262144, 4, 32, 65536, 8192
+PRUNE_ROWS, PRUNE_COLS, PRUNE_MAX_N, PRUNE_MAX_W = 256, 512, 1048576, 4
 
 
 class BufDesc(C.Structure):
@@ -149,6 +150,8 @@ _SIGNATURES = {
     "uda_eval_match_np": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "uda_thr_objective_np": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32,
                                        C.c_int32, C.c_double, _P, _P, _P]),
+    "uda_hash_neighbors_np": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
+                                        _P, _P, C.POINTER(C.c_int64)]),
     "uda_calibrate_box": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "uda_calibrate_class": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, _P]),
     "uda_serve": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),

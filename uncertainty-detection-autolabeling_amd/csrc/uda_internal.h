@@ -478,6 +478,28 @@ struct ThrArgs {
 void launch_thr_mask(const ThrArgs& a, hipStream_t s);
 void launch_thr_objective(const ThrArgs& a, hipStream_t s);
 
+// dataset pruning: the neighbour rows of extract_hash_matrix (reference active_learning_loop.py:240-270) as four passes with a
+// launch boundary between them: max -> (host: limit) -> count -> scan -> (host: total, idx allocated) -> fill.  A block is
+// PRUNE_ROWS rows and walks the chunks_per_span chunks of PRUNE_COLS columns of its span (grid.y = spans); a slot is one
+// (row, span), in that order.  Every buffer is the caller's.
+enum { PRUNE_ROWS = UDA_PRUNE_ROWS, PRUNE_COLS = UDA_PRUNE_COLS, PRUNE_MAX_W = 4, PRUNE_SCAN_TILE = 2048, PRUNE_SCAN_MAX_TILES = 1024 };
+struct PruneArgs {
+  const uint64_t* hashes;   // [N, W]
+  int32_t* max_dist;        // [1], zeroed by the caller
+  int32_t* counts;          // [n_slots] columns within the limit
+  int64_t* tile_sums;       // [n_tiles + 1] scratch of the scan; the total ends up behind the tiles
+  int64_t* cursor;          // [n_slots] first entry of the slot in idx
+  int64_t* row_off;         // [N + 1]
+  int32_t* idx;             // [total]
+  int N, W, n_chunks, spans, chunks_per_span, n_tiles;
+  int64_t n_slots;          // N * spans
+  double limit;             // a column is a neighbour iff (double)d <= limit
+};
+void launch_prune_max(const PruneArgs& a, hipStream_t s);
+void launch_prune_count(const PruneArgs& a, hipStream_t s);
+void launch_prune_scan(const PruneArgs& a, hipStream_t s);
+void launch_prune_fill(const PruneArgs& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

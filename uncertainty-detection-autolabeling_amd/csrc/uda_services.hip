@@ -1,6 +1,7 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
 // COCO matching and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
-// on scratch device memory of their own (the *_np twins, the thresholding objective, uda_nms, uda_debug_pw, the numpy NMS family).
+// on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, uda_nms, uda_debug_pw,
+// the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
 #include <stdio.h>
 #include <string.h>
@@ -736,6 +737,68 @@ extern "C" int uda_thr_objective_np(int32_t device, const double* uncerts, const
       if (auc) auc[o] = h[3 * q + 2];
     }
   }
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  return 0;
+}
+
+// the neighbour rows of the pruning step: host hashes in, four passes with a launch boundary between them (max, count, scan,
+// fill), CSR rows out; its own allocations, the index array only once the total is known.  A grid of about kPruneBlocks blocks:
+// the columns are cut into as many spans as that takes, which decides who counts a hit and nothing about the result.
+static const int kPruneBlocks = 1024;
+extern "C" int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int32_t N, int32_t W, double prune_thr,
+                                     int32_t max_distance, int64_t cap, int32_t* max_dist, int64_t* row_off, int32_t* idx,
+                                     int64_t* total) {
+  const char* who = "uda_hash_neighbors_np";
+  if (N < 1 || N > UDA_PRUNE_MAX_N) return fail(nullptr, "%s: %d hashes, 1..%d are taken", who, N, (int)UDA_PRUNE_MAX_N);
+  if (W < 1 || W > PRUNE_MAX_W) return fail(nullptr, "%s: %d words per hash, 1..%d are taken", who, W, (int)PRUNE_MAX_W);
+  if (!hashes || !max_dist || !row_off || !total) return fail(nullptr, "%s: NULL input", who);
+  if (cap < 0) return fail(nullptr, "%s: cap %lld is negative", who, (long long)cap);
+  if (max_distance < 0 && !(prune_thr >= 0.0 && prune_thr <= 1.79769313486231570e308))
+    return fail(nullptr, "%s: prune_thr %g is negative or not finite", who, prune_thr);
+  PruneArgs a{};
+  a.N = N; a.W = W;
+  a.n_chunks = (N + PRUNE_COLS - 1) / PRUNE_COLS;
+  const int row_blocks = (N + PRUNE_ROWS - 1) / PRUNE_ROWS;
+  const int want_spans = std::min(a.n_chunks, std::max(1, (kPruneBlocks + row_blocks - 1) / row_blocks));
+  a.chunks_per_span = (a.n_chunks + want_spans - 1) / want_spans;
+  a.spans = (a.n_chunks + a.chunks_per_span - 1) / a.chunks_per_span;      // no empty span
+  a.n_slots = (int64_t)N * a.spans;
+  a.n_tiles = (int)((a.n_slots + PRUNE_SCAN_TILE - 1) / PRUNE_SCAN_TILE);
+  if (a.n_tiles > PRUNE_SCAN_MAX_TILES) return fail(nullptr, "%s: %d scan tiles, at most %d (internal)", who, a.n_tiles, (int)PRUNE_SCAN_MAX_TILES);
+  DevScratch s(device);
+  a.hashes = s.upload(hashes, (size_t)N * W);
+  a.max_dist = s.alloc<int32_t>(1);
+  a.counts = s.alloc<int32_t>((size_t)a.n_slots);
+  a.tile_sums = s.alloc<int64_t>((size_t)a.n_tiles + 1);
+  a.cursor = s.alloc<int64_t>((size_t)a.n_slots);
+  a.row_off = s.alloc<int64_t>((size_t)N + 1);
+  s.zero(a.max_dist, sizeof(int32_t));
+  if (s.ok()) launch_prune_max(a, nullptr);
+  s.sync();
+  int32_t md = 0;
+  s.download(&md, a.max_dist, sizeof md);
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  a.limit = max_distance >= 0 ? (double)max_distance : (double)md * prune_thr;
+  launch_prune_count(a, nullptr);
+  launch_prune_scan(a, nullptr);
+  s.sync();
+  int64_t tot = 0;
+  s.download(&tot, a.tile_sums + a.n_tiles, sizeof tot);
+  s.download(row_off, a.row_off, ((size_t)N + 1) * sizeof(int64_t));
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  *max_dist = md;
+  *total = tot;
+  if (!idx || tot > cap) return 0;
+  size_t free_b = 0, all_b = 0;
+  s.err = hipMemGetInfo(&free_b, &all_b);
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  if ((size_t)tot * sizeof(int32_t) > free_b)
+    return fail(nullptr, "%s: %lld neighbour entries take %zu bytes of device memory, %zu of %zu are free", who, (long long)tot,
+                (size_t)tot * sizeof(int32_t), free_b, all_b);
+  a.idx = s.alloc<int32_t>((size_t)tot);
+  if (s.ok()) launch_prune_fill(a, nullptr);
+  s.sync();
+  s.download(idx, a.idx, (size_t)tot * sizeof(int32_t));
   if (!s.ok()) return hip_failed(nullptr, who, s.err);
   return 0;
 }
