@@ -557,6 +557,67 @@ int uda_thr_objective_np(int32_t device, const double* uncerts, const double* io
 int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int32_t N, int32_t W, double prune_thr, int32_t max_distance,
                           int64_t cap, int32_t* max_dist, int64_t* row_off, int32_t* idx, int64_t* total);
 
+/* Label correction (GLC): the verdicts of the reference's ground-truth label correction (AdvancedLabels, src/ssl_utils/glc.py) -
+ * which ground-truth boxes are mistakes, which detections are missing labels, which noisy boxes are replaced by their detection -
+ * done on the detections RESIDENT in the handle: the originals of the last uda_run_consistency (their cons_iou stays on the
+ * device) against the ground truth of uda_set_ground_truth.  The label files are the caller's (writers.py).
+ *   kept          detection k of an image is kept iff score > min_score, in float32 (the rows Infer.iterate_infer writes,
+ *                 infer_model.py:842); only kept detections take part, in rank order
+ *   counted       a ground-truth row counts iff its class is > 0 (padding rows carry -1, as in the validate mode)
+ *   iou / match   iou[g] = max over the kept k of calc_iou_np(gt_g, box_k) (utils_box.py:56-89: float32 differences, float64
+ *                 products, (areaA + areaB) - inter, 0 where the union is 0; never fused); det_rank[g] = the first kept k that
+ *                 reaches it (np.argmax, glc.py:182-187).  A row that touches nothing is matched to the FIRST KEPT detection
+ *   mistakes      UDA_LC_GT_MISTAKE: iou[g] == 0 (:551)
+ *   md            UDA_LC_DET_MISSING: a kept detection whose maximum IoU over the counted rows == md_max_inter (np.equal,
+ *                 :432-436; md_rule UDA_LC_MD_LE: <=, the synthetic branch :468-472) and cons_iou >= iou_consist
+ *   noisy         UDA_LC_GT_NOISY: cons_iou[det_rank[g]] > iou_consist (strict), iou[g] <= correct_max_inter and
+ *                 score[det_rank[g]] >= correct_score (float32) (:813-824).  For every detection matched by such a row the
+ *                 FIRST counted row matched to it gets the detection's box and UDA_LC_GT_REPLACED - whether or not that row met
+ *                 the conditions itself; a later row that did keeps its box (np.where(matched == k)[0][0], :828-833)
+ * Two cases the reference does not reach: an image without a kept detection never appears in its file - all its rows get
+ * det_rank -1, IoU 0 and no flag; an image without a counted row makes it raise (np.argmax of an empty list) - here every
+ * detection's maximum IoU is 0 and the md rule is applied to that.  Every output is exact and does not depend on how the device
+ * cuts rows and ranks into waves.  Values must be finite (the Python layer checks). */
+#define UDA_LC_MD 1             /* methods: a bit set */
+#define UDA_LC_MISTAKES 2
+#define UDA_LC_NOISY 4
+#define UDA_LC_MD_EQ 0          /* md_rule */
+#define UDA_LC_MD_LE 1
+#define UDA_LC_GT_MISTAKE 1     /* gt_flags */
+#define UDA_LC_GT_NOISY 2
+#define UDA_LC_GT_REPLACED 4
+#define UDA_LC_DET_KEPT 1       /* det_flags */
+#define UDA_LC_DET_MISSING 2
+/*   uda_label_check      queues the kernel on the handle's stream; forces the deferred fix-ups every reader of detections forces.
+ *                        Refuses: no ground truth set, the last post-process ran per class, a pipelined run still in flight, n
+ *                        different from the run's originals, md or noisy asked for when the resident run was not a consistency
+ *                        run (mistakes alone needs none), methods outside 1..7, an unknown md_rule, max_output_size above 4096.
+ *                        The result buffers belong to the handle and grow only when G grows.
+ *   uda_get_label_check  the first reader of a check waits for it and brings the results over in one copy; any pointer may be
+ *                        NULL.  det_rank [n, G] int32 resident rank of the matched detection, -1: row not counted or no kept
+ *                        detection; iou [n, G] float64; gt_flags [n, G] uint8; gt_boxes_out [n, G, 4] float32 the row's own box,
+ *                        or the detection's where replaced; det_flags [n, M] uint8; det_max_iou [n, M] float64 (0: not kept);
+ *                        counts [n, 5] int32 kept detections, counted rows, mistakes, replaced rows, missing labels. */
+int uda_label_check(uda_ctx_t* ctx, float min_score, double iou_consist, double md_max_inter, int32_t md_rule,
+                    double correct_max_inter, float correct_score, int32_t methods);
+int uda_get_label_check(uda_ctx_t* ctx, int32_t* det_rank, double* iou, uint8_t* gt_flags, float* gt_boxes_out, uint8_t* det_flags,
+                        double* det_max_iou, int32_t* counts);
+/* The same without a handle, in the manner of uda_assign_gt_np / uda_score_images_np[_f32]: host arrays boxes [n, M, 4], scores
+ * [n, M], cons_iou [n, M] (float64 in both; may be NULL for mistakes alone), gt_boxes [n, G, 4], gt_classes [n, G]; the same
+ * kernel, the same outputs.  _np: float64 arrays and all-float64 arithmetic - fed with the values read back from a
+ * prediction_data.txt it is the reference's arithmetic bit for bit; _np_f32: float32 arrays, the handle's arithmetic.
+ * M <= 4096, G <= 16384, n >= 1; anything else is refused, never truncated, and the outputs stay untouched. */
+int uda_label_check_np(int32_t device, const double* boxes, const double* scores, const double* cons_iou, const double* gt_boxes,
+                       const double* gt_classes, int32_t n, int32_t M, int32_t G, double min_score, double iou_consist,
+                       double md_max_inter, int32_t md_rule, double correct_max_inter, double correct_score, int32_t methods,
+                       int32_t* det_rank, double* iou, uint8_t* gt_flags, float* gt_boxes_out, uint8_t* det_flags,
+                       double* det_max_iou, int32_t* counts);
+int uda_label_check_np_f32(int32_t device, const float* boxes, const float* scores, const double* cons_iou, const float* gt_boxes,
+                           const float* gt_classes, int32_t n, int32_t M, int32_t G, float min_score, double iou_consist,
+                           double md_max_inter, int32_t md_rule, double correct_max_inter, float correct_score, int32_t methods,
+                           int32_t* det_rank, double* iou, uint8_t* gt_flags, float* gt_boxes_out, uint8_t* det_flags,
+                           double* det_max_iou, int32_t* counts);
+
 /* serve = set_images_u8 + run + get_detections */
 int uda_serve(uda_ctx_t* ctx, const uint8_t* images, int32_t n, int32_t h, int32_t w,
               float* boxes, float* scores, float* classes, int32_t* valid, float* logits);

@@ -206,6 +206,12 @@ struct uda_ctx {
   std::vector<char> h_pseudo;        // host copy of the pack's head (filled by the first reader of a run)
   int pseudo_n = 0, pseudo_cap = 0;  // images / record slots per image of the last uda_pseudo_rows (0: none)
   bool pseudo_fetched = false;
+  // label correction (uda_label_check): the verdicts for n images x G rows and M detections, packed so that ONE copy brings them
+  // to the host (LabelPack, uda_services.hip); the buffer holds max_images x lc_cap rows and grows when a check brings more
+  char* d_lc_pack = nullptr;
+  std::vector<char> h_lc;            // host copy of the pack (filled by the first reader of a check)
+  int lc_cap = 0, lc_n = 0, lc_G = 0; // rows per image the buffer holds; images / rows per image of the last check (0: none)
+  bool lc_fetched = false;
   // COCO matching (uda_set_eval_ground_truth / uda_eval_match): ground truth [max_images, egt_cap, 7], grown when a call brings
   // more rows per image; results packed for max_images so that ONE copy brings them to the host:
   // records [n, M] x 44 bytes | npig [n, num_classes, 4] int32 | used [n] int32 (EvalPack)

@@ -500,6 +500,34 @@ void launch_prune_count(const PruneArgs& a, hipStream_t s);
 void launch_prune_scan(const PruneArgs& a, hipStream_t s);
 void launch_prune_fill(const PruneArgs& a, hipStream_t s);
 
+// label correction (reference ssl_utils/glc.py): the three verdicts on one image's kept detections and counted ground-truth rows
+// (kernels_glc.hip).  T = float for the columns resident in a handle, double for host arrays (uda_label_check_np)
+enum { LC_MD = UDA_LC_MD, LC_MISTAKES = UDA_LC_MISTAKES, LC_NOISY = UDA_LC_NOISY };
+enum { LC_MD_EQ = UDA_LC_MD_EQ, LC_MD_LE = UDA_LC_MD_LE };
+enum { LC_GT_MISTAKE = UDA_LC_GT_MISTAKE, LC_GT_NOISY = UDA_LC_GT_NOISY, LC_GT_REPLACED = UDA_LC_GT_REPLACED };
+enum { LC_DET_KEPT = UDA_LC_DET_KEPT, LC_DET_MISSING = UDA_LC_DET_MISSING };
+template <typename T>
+struct LabelCheckArgs {
+  const T* det_boxes;       // [n, M, det_stride] y1 x1 y2 x2 in the first four columns
+  const T* scores;          // [n, M]
+  const double* cons_iou;   // [n, M]; null when neither md nor noisy is asked for
+  const T* gt_boxes;        // [n, G, 4]
+  const T* gt_classes;      // [n, G] a row counts iff class > 0 (-1 rows: padding)
+  int32_t* det_rank;        // [n, G] rank of the matched detection, -1: row not counted / no kept detection
+  double* iou;              // [n, G] the row's best IoU over the kept detections
+  uint8_t* gt_flags;        // [n, G] LC_GT_*
+  float* gt_boxes_out;      // [n, G, 4] the row's own box, or the detection's where replaced
+  uint8_t* det_flags;       // [n, M] LC_DET_*
+  double* det_max_iou;      // [n, M] the detection's best IoU over the counted rows (0: not kept)
+  int32_t* counts;          // [n, 5] kept detections, counted rows, mistakes, replaced rows, missing labels
+  int32_t* first_row;       // [n, M] scratch: first row matched to a packed detection
+  int n, M, G, det_stride, methods, md_rule;
+  T min_score, correct_score;   // kept: score > min_score; noisy: score >= correct_score - in the scores' own type
+  double iou_consist, md_max_inter, correct_max_inter;
+};
+void launch_label_check(const LabelCheckArgs<float>& a, hipStream_t s);
+void launch_label_check(const LabelCheckArgs<double>& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

@@ -1,5 +1,5 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
-// COCO matching and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
+// COCO matching, the label check and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
 // on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
@@ -109,6 +109,37 @@ struct EvalPack {        // records [n, M] x 44 bytes | npig [n, C, 4] int32 | u
     if (records) memcpy(records, rec(), n * M * sizeof(uda_eval_record_t));
     if (npig_out) memcpy(npig_out, npig(), n * C * 4 * sizeof(int32_t));
     if (used_out) memcpy(used_out, used(), n * sizeof(int32_t));
+  }
+};
+
+struct LabelPack {       // iou [n G] float64 | det_max_iou [n M] float64 | det_rank [n G] int32 | counts [n 5] int32 | gt_boxes_out
+  char* base;            // [n G 4] float32 | gt_flags [n G] uint8 | det_flags [n M] uint8; behind what is copied, from the next
+  size_t n, G, M;        // multiple of 4 bytes: the kernel's first-row words [n M] int32
+  LabelPack(void* b, size_t n_, size_t G_, size_t M_) : base((char*)b), n(n_), G(G_), M(M_) {}
+  double* iou() const { return (double*)base; }
+  double* det_max() const { return iou() + n * G; }
+  int32_t* det_rank() const { return (int32_t*)(det_max() + n * M); }
+  int32_t* counts() const { return det_rank() + n * G; }
+  float* gt_boxes() const { return (float*)(counts() + n * 5); }
+  uint8_t* gt_flags() const { return (uint8_t*)(gt_boxes() + n * G * 4); }
+  uint8_t* det_flags() const { return gt_flags() + n * G; }
+  size_t copy_bytes() const { return (size_t)(det_flags() + n * M - (uint8_t*)base); }
+  int32_t* first_row() const { return (int32_t*)(base + ((copy_bytes() + 3) & ~(size_t)3)); }
+  size_t bytes() const { return ((copy_bytes() + 3) & ~(size_t)3) + n * M * sizeof(int32_t); }
+  template <typename T>
+  void fill(LabelCheckArgs<T>& a) const {
+    a.iou = iou(); a.det_max_iou = det_max(); a.det_rank = det_rank(); a.counts = counts(); a.gt_boxes_out = gt_boxes();
+    a.gt_flags = gt_flags(); a.det_flags = det_flags(); a.first_row = first_row();
+  }
+  void copy_out(int32_t* det_rank_out, double* iou_out, uint8_t* gt_flags_out, float* gt_boxes_out, uint8_t* det_flags_out,
+                double* det_max_out, int32_t* counts_out) const {
+    if (det_rank_out && n * G) memcpy(det_rank_out, det_rank(), n * G * sizeof(int32_t));
+    if (iou_out && n * G) memcpy(iou_out, iou(), n * G * sizeof(double));
+    if (gt_flags_out && n * G) memcpy(gt_flags_out, gt_flags(), n * G);
+    if (gt_boxes_out && n * G) memcpy(gt_boxes_out, gt_boxes(), n * G * 4 * sizeof(float));
+    if (det_flags_out && n * M) memcpy(det_flags_out, det_flags(), n * M);
+    if (det_max_out && n * M) memcpy(det_max_out, det_max(), n * M * sizeof(double));
+    if (counts_out) memcpy(counts_out, counts(), n * 5 * sizeof(int32_t));
   }
 };
 
@@ -574,6 +605,123 @@ extern "C" int uda_pseudo_rows_np_f32(int32_t device, const uda_score_desc_t* de
                                       int64_t* n_records, double* minmax, int32_t* kept, int32_t* cand) {
   return pseudo_rows_np<float>("uda_pseudo_rows_np_f32", device, desc, min_score, boxes, scores, classes, entropy, albox, mcbox, mcclass, n,
                                M, num_classes, mcclass_cols, invert, gate, tau, max_rows, records, n_records, minmax, kept, cand);
+}
+
+// ---- label correction (reference ssl_utils/glc.py:182-187, 432-436, 551, 813-834)
+// what the scalars must satisfy; null when they do
+static const char* label_check_args_bad(int methods, int md_rule) {
+  if (methods < 1 || methods > (LC_MD | LC_MISTAKES | LC_NOISY)) return "methods is a bit set of md (1), mistakes (2) and noisy (4), at least one";
+  if (md_rule != LC_MD_EQ && md_rule != LC_MD_LE) return "md_rule is 0 (==) or 1 (<=)";
+  return nullptr;
+}
+
+extern "C" int uda_label_check(uda_ctx_t* c, float min_score, double iou_consist, double md_max_inter, int32_t md_rule,
+                               double correct_max_inter, float correct_score, int32_t methods) {
+  if (!c) return 1;
+  const uda_model_t& m = c->model;
+  if (const char* why = label_check_args_bad(methods, md_rule)) return fail(c, "label_check: %s", why);
+  if (c->gt_n < 1) return fail(c, "label_check: no ground truth is set (uda_set_ground_truth)");
+  if (int rc = resident_ready(c, "label_check", "the label check reads")) return rc;
+  // after a consistency run the handle holds 4n images, the n originals first: the ground truth belongs to those
+  const bool cons = c->noise_from >= 0 && c->cons_n > 0 && c->last_n == 4 * c->cons_n;
+  if (c->gt_n != (cons ? c->cons_n : c->last_n))
+    return fail(c, "label_check: ground truth of %d images, the last post-process holds %d", c->gt_n, cons ? c->cons_n : c->last_n);
+  if ((methods & (LC_MD | LC_NOISY)) && !cons)
+    return fail(c, "label_check: md and noisy read cons_iou, and the resident run is not a consistency run (uda_run_consistency)");
+  if (m.max_output_size > kAssignMaxM) return fail(c, "label_check: max_output_size %d above %d", m.max_output_size, kAssignMaxM);
+  if (int rc = settle_detections(c)) return rc;
+  const int n = c->gt_n, M = m.max_output_size, G = c->gt_G;
+  if (!c->d_lc_pack || G > c->lc_cap) {
+    HIPC(c, hipStreamSynchronize(c->stream));              // (growing is rare: nothing may still read the old buffer)
+    if (c->d_lc_pack) hipFree(c->d_lc_pack);
+    c->d_lc_pack = nullptr; c->lc_cap = 0; c->lc_n = 0;
+    const size_t cap = (size_t)std::max(G, 1);
+    HIPC(c, dalloc(&c->d_lc_pack, LabelPack(nullptr, (size_t)m.max_images, cap, (size_t)M).bytes()));
+    c->lc_cap = (int)cap;
+  }
+  LabelCheckArgs<float> a{};
+  a.det_boxes = c->d_oboxes; a.det_stride = box_cols_of(m, UDA_POST_GLOBAL); a.scores = c->d_oscores;
+  a.cons_iou = cons ? c->d_cons_iou : nullptr;
+  a.gt_boxes = c->d_gt_boxes; a.gt_classes = c->d_gt_classes;
+  LabelPack(c->d_lc_pack, (size_t)n, (size_t)G, (size_t)M).fill(a);
+  a.n = n; a.M = M; a.G = G; a.methods = methods; a.md_rule = md_rule;
+  a.min_score = min_score; a.correct_score = correct_score;
+  a.iou_consist = iou_consist; a.md_max_inter = md_max_inter; a.correct_max_inter = correct_max_inter;
+  launch_label_check(a, c->stream);
+  HIPC(c, hipGetLastError());
+  c->lc_n = n; c->lc_G = G; c->lc_fetched = false;
+  return 0;
+}
+
+extern "C" int uda_get_label_check(uda_ctx_t* c, int32_t* det_rank, double* iou, uint8_t* gt_flags, float* gt_boxes_out,
+                                   uint8_t* det_flags, double* det_max_iou, int32_t* counts) {
+  if (!c) return 1;
+  if (c->lc_n < 1) return fail(c, "get_label_check: no label check (uda_label_check)");
+  LabelPack h(nullptr, (size_t)c->lc_n, (size_t)c->lc_G, (size_t)c->model.max_output_size);
+  if (!c->lc_fetched) {          // the first reader of a check waits for it and brings the pack over in one copy
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->h_lc.resize(h.copy_bytes());
+    HIPC(c, hipMemcpy(c->h_lc.data(), c->d_lc_pack, h.copy_bytes(), hipMemcpyDeviceToHost));
+    c->lc_fetched = true;
+  }
+  h.base = c->h_lc.data();
+  h.copy_out(det_rank, iou, gt_flags, gt_boxes_out, det_flags, det_max_iou, counts);
+  return 0;
+}
+
+// the label check for callers that hold detections of their own (a parsed prediction_data.txt, a gathered multi-GPU batch): host
+// arrays in, the same kernel, host arrays out; its own allocations
+template <typename T>
+static int label_check_np(const char* who, int32_t device, const T* boxes, const T* scores, const double* cons_iou, const T* gt_boxes,
+                          const T* gt_classes, int32_t n, int32_t M, int32_t G, T min_score, double iou_consist, double md_max_inter,
+                          int32_t md_rule, double correct_max_inter, T correct_score, int32_t methods, int32_t* det_rank, double* iou,
+                          uint8_t* gt_flags, float* gt_boxes_out, uint8_t* det_flags, double* det_max_iou, int32_t* counts) {
+  if (const char* why = label_check_args_bad(methods, md_rule)) return fail(nullptr, "%s: %s", who, why);
+  if (n < 1) return fail(nullptr, "%s: %d images, at least 1", who, n);
+  if (M < 0 || M > kAssignMaxM) return fail(nullptr, "%s: %d detection rows per image, at most %d", who, M, kAssignMaxM);
+  if (G < 0 || G > kAssignMaxG) return fail(nullptr, "%s: %d ground-truth rows per image, at most %d", who, G, kAssignMaxG);
+  const size_t nm = (size_t)n * M, ng = (size_t)n * G;
+  if ((nm && (!boxes || !scores)) || (ng && (!gt_boxes || !gt_classes))) return fail(nullptr, "%s: NULL input", who);
+  if ((methods & (LC_MD | LC_NOISY)) && nm && !cons_iou) return fail(nullptr, "%s: md and noisy read cons_iou, which is not given", who);
+  DevScratch s(device);
+  LabelCheckArgs<T> a{};
+  a.det_boxes = s.upload(boxes, nm * 4); a.det_stride = 4; a.scores = s.upload(scores, nm);
+  a.cons_iou = (methods & (LC_MD | LC_NOISY)) ? s.upload(cons_iou, nm) : nullptr;
+  a.gt_boxes = s.upload(gt_boxes, ng * 4); a.gt_classes = s.upload(gt_classes, ng);
+  LabelPack pack(nullptr, (size_t)n, (size_t)G, (size_t)M);
+  pack.base = s.alloc<char>(pack.bytes());
+  LabelPack(pack.base, pack.n, pack.G, pack.M).fill(a);
+  a.n = n; a.M = M; a.G = G; a.methods = methods; a.md_rule = md_rule;
+  a.min_score = min_score; a.correct_score = correct_score;
+  a.iou_consist = iou_consist; a.md_max_inter = md_max_inter; a.correct_max_inter = correct_max_inter;
+  if (s.ok()) launch_label_check(a, nullptr);
+  s.sync();
+  std::vector<char> h(pack.copy_bytes());
+  s.download(h.data(), pack.base, h.size());
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  LabelPack(h.data(), pack.n, pack.G, pack.M).copy_out(det_rank, iou, gt_flags, gt_boxes_out, det_flags, det_max_iou, counts);
+  return 0;
+}
+
+extern "C" int uda_label_check_np(int32_t device, const double* boxes, const double* scores, const double* cons_iou,
+                                  const double* gt_boxes, const double* gt_classes, int32_t n, int32_t M, int32_t G, double min_score,
+                                  double iou_consist, double md_max_inter, int32_t md_rule, double correct_max_inter,
+                                  double correct_score, int32_t methods, int32_t* det_rank, double* iou, uint8_t* gt_flags,
+                                  float* gt_boxes_out, uint8_t* det_flags, double* det_max_iou, int32_t* counts) {
+  return label_check_np<double>("uda_label_check_np", device, boxes, scores, cons_iou, gt_boxes, gt_classes, n, M, G, min_score,
+                                iou_consist, md_max_inter, md_rule, correct_max_inter, correct_score, methods, det_rank, iou, gt_flags,
+                                gt_boxes_out, det_flags, det_max_iou, counts);
+}
+
+extern "C" int uda_label_check_np_f32(int32_t device, const float* boxes, const float* scores, const double* cons_iou,
+                                      const float* gt_boxes, const float* gt_classes, int32_t n, int32_t M, int32_t G, float min_score,
+                                      double iou_consist, double md_max_inter, int32_t md_rule, double correct_max_inter,
+                                      float correct_score, int32_t methods, int32_t* det_rank, double* iou, uint8_t* gt_flags,
+                                      float* gt_boxes_out, uint8_t* det_flags, double* det_max_iou, int32_t* counts) {
+  return label_check_np<float>("uda_label_check_np_f32", device, boxes, scores, cons_iou, gt_boxes, gt_classes, n, M, G, min_score,
+                               iou_consist, md_max_inter, md_rule, correct_max_inter, correct_score, methods, det_rank, iou, gt_flags,
+                               gt_boxes_out, det_flags, det_max_iou, counts);
 }
 
 // ---- COCO matching (reference custom_cocoeval.py:265-349 on the containers of coco_metric.py:219-283)

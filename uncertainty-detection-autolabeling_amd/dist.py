@@ -307,6 +307,14 @@ class SampleShardedDriver:
     def serve_pseudo_labels(self, images, strategy, tau, opt_params=None, min_score=None, max_rows=None):
         return self.pseudo_rows(strategy, tau, opt_params, min_score, max_rows)
 
+    def label_check(self, gt_boxes, gt_classes, methods=("mistakes",), **kwargs):
+        """As for the ground-truth assignment: no single handle holds the whole batch's detections (nor a consistency run)."""
+        raise ValueError("a sample-sharded serve leaves no handle that holds the whole batch's detections: run "
+                         "label_correction.check_labels(boxes, scores, cons_iou, gt_boxes, gt_classes) on the gathered detections")
+
+    def serve_label_check(self, images, gt_boxes, gt_classes, methods=("mistakes",), **kwargs):
+        return self.label_check(gt_boxes, gt_classes, methods, **kwargs)
+
     def eval_match(self, groundtruth_data, iou_thrs=None):
         """As for the ground-truth assignment: no single handle holds the whole batch's detections."""
         raise ValueError("a sample-sharded serve leaves no handle that holds the whole batch's detections: run "

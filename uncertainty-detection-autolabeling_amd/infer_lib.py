@@ -586,6 +586,77 @@ class ServingDriver:
         self.serve_resident(image_arrays, post_mode=capi.POST_GLOBAL)
         return self.pseudo_rows(sel, tau, min_score=min_score, max_rows=max_rows)
 
+    # ------------------------------------------------------------------ label correction: ground-truth verdicts (GLC)
+    def _label_check_args(self, methods, min_score, iou_consist, md_max_inter, md_rule, correct_max_inter, correct_score):
+        from . import label_correction as lc
+        thr = lc.check_thresholds(iou_consist, md_max_inter, correct_max_inter, correct_score)
+        return (lc.method_mask(methods), lc.md_rule_code(md_rule), lc.resolve_min_score(self.params, min_score)) + thr
+
+    def _queue_label_check(self, args):
+        mask, rule, min_score, ic, md, cmi, cs = args
+        self._ck(self._lib.uda_label_check(self._h, C.c_float(min_score), ic, md, rule, cmi, C.c_float(cs), mask), "uda_label_check")
+
+    def _fetch_label_check(self, gb, gc, methods, missing_boxes, names):
+        from . import label_correction as lc
+        n, G = gc.shape
+        res = lc.empty_result(n, self.M, G)
+        self._ck(self._lib.uda_get_label_check(self._h, *[_ptr(res[k]) for k in lc.RESULT_ORDER]), "uda_get_label_check")
+        boxes = classes = None
+        if missing_boxes and res["counts"][:, 4].any():
+            # the box and class columns only (uda_get_detections copies them for every image of the run: 4n after a consistency run)
+            bc, cc = C.c_int32(), C.c_int32()
+            self._ck(self._lib.uda_detection_cols(self._h, capi.POST_GLOBAL, C.byref(bc), C.byref(cc)), "uda_detection_cols")
+            boxes = np.empty((self._last_n, self.M, bc.value), np.float32)
+            classes = np.empty((self._last_n, self.M, cc.value), np.float32)
+            self._ck(self._lib.uda_get_detections(self._h, _ptr(boxes), None, _ptr(classes), None, None), "uda_get_detections")
+            boxes, classes = boxes[:n], classes[:n]
+        return lc.LabelCheck.from_arrays(res, boxes, gb, gc, classes, methods, names)
+
+    def label_check(self, gt_boxes, gt_classes, methods=("md", "mistakes", "noisy"), min_score=None, iou_consist=0.90, md_max_inter=0,
+                    md_rule="eq", correct_max_inter=1.0, correct_score=0.40, missing_boxes=True, names=None):
+        """The verdicts of the reference's ground-truth label correction (`AdvancedLabels`, src/ssl_utils/glc.py) on the run
+        resident in the handle - the originals of the last `serve_consistency`, whose cons_iou stayed on the device - against
+        gt_boxes [n, G, 4] / gt_classes [n, G] (as `assign_ground_truth` takes them; a row counts iff its class is > 0):
+        which ground-truth rows are mistakes (touch no detection), which detections are missing labels (`md`), which noisy
+        rows are replaced by their detection (`label_correction`).  Only detections with score > min_score take
+        part (None: `label_correction.resolve_min_score`, 0.1 as GLC's own inference writes); the thresholds are
+        `AdvancedLabels`' constructor arguments with its defaults; md_rule "le" is the synthetic branch's <=.  "mistakes" alone
+        works after any global run (`serve_resident`); md and noisy need the consistency run.
+
+        Returns a `label_correction.LabelCheck`.  The host receives the verdicts only; with missing_boxes the originals'
+        detection columns are fetched as well, once, and only when a missing label is flagged (the writer of missing boxes
+        needs their boxes and classes)."""
+        from . import utils_extra
+        gb, gc = utils_extra.check_ground_truth(gt_boxes, gt_classes)
+        args = self._label_check_args(methods, min_score, iou_consist, md_max_inter, md_rule, correct_max_inter, correct_score)
+        self._ck(self._lib.uda_set_ground_truth(self._h, _ptr(gb), _ptr(gc), gb.shape[0], gb.shape[1]), "uda_set_ground_truth")
+        self._queue_label_check(args)
+        return self._fetch_label_check(gb, gc, methods, missing_boxes, names)
+
+    def serve_label_check(self, image_arrays, gt_boxes, gt_classes, methods=("md", "mistakes", "noisy"), min_score=None,
+                          iou_consist=0.90, md_max_inter=0, md_rule="eq", correct_max_inter=1.0, correct_score=0.40, missing_boxes=True,
+                          names=None):
+        """`serve_consistency` + ground truth + `label_check` as one device pass, without downloading the 100-row columns of the
+        4N served images: the upload of the ground truth is queued before the network, the check behind the consistency
+        scores, and the host waits once.  -> `label_correction.LabelCheck`; `serve_consistency`'s own outputs stay readable
+        (`label_check` again with other thresholds, `assign_ground_truth`, `score_images`)."""
+        from . import utils_extra
+        if not self.params.get("consistency_ssl"):
+            raise ValueError("serve_label_check needs a driver created with model_params consistency_ssl=True "
+                             "(its handle is planned for the 3 variants of every image)")
+        gb, gc = utils_extra.check_ground_truth(gt_boxes, gt_classes)
+        args = self._label_check_args(methods, min_score, iou_consist, md_max_inter, md_rule, correct_max_inter, correct_score)
+        n = self._feed(image_arrays)
+        if gb.shape[0] != n:
+            raise ValueError("ground truth of %d images for a batch of %d" % (gb.shape[0], n))
+        self._ck(self._lib.uda_set_ground_truth(self._h, _ptr(gb), _ptr(gc), n, gb.shape[1]), "uda_set_ground_truth")
+        self._next_seed()
+        self._run_id += 1
+        self._ck(self._lib.uda_run_consistency(self._h, capi.POST_GLOBAL), "uda_run_consistency")
+        self._last_n = 4 * n
+        self._queue_label_check(args)
+        return self._fetch_label_check(gb, gc, methods, missing_boxes, names)
+
     # ------------------------------------------------------------------ COCO evaluation: matching on the resident detections
     def eval_match(self, groundtruth_data, iou_thrs=None):
         """`COCOeval_all.evaluateImg` (custom_cocoeval.py:265-349) for the detections resident in the handle after a
@@ -1130,6 +1201,15 @@ class EnsembleDriver:
     def serve_pseudo_labels(self, image_arrays, strategy, tau, opt_params=None, min_score=None, max_rows=None):
         self.serve(image_arrays)
         return self.pseudo_rows(strategy, tau, opt_params=opt_params, min_score=min_score, max_rows=max_rows)
+
+    def label_check(self, gt_boxes, gt_classes, methods=("mistakes",), **kwargs):
+        """The ensemble's detections live in its aggregating handle: the check is that handle's.  An ensemble serves no
+        consistency run, so only "mistakes" can be asked for (md and noisy read cons_iou and are refused by the handle)."""
+        return self.post.label_check(gt_boxes, gt_classes, methods=methods, **kwargs)
+
+    def serve_label_check(self, image_arrays, gt_boxes, gt_classes, methods=("mistakes",), **kwargs):
+        self.serve(image_arrays)
+        return self.label_check(gt_boxes, gt_classes, methods=methods, **kwargs)
 
     def eval_match(self, groundtruth_data, iou_thrs=None):
         """The ensemble's detections live in its aggregating handle: the match is that handle's."""

@@ -6,6 +6,8 @@
                         (src/validate_model.py:524-681), plus the runtime summary of validationstep_runtime.txt
                         (:685-704), average_score.txt (:683-684) and model_performance.txt (:706-735):
                         `validate_to_file` is that whole loop
+  corrected ground truth the KITTI label files and the BDD100K json of `AdvancedLabels.corrected_gt` (src/ssl_utils/glc.py:231-406)
+                        for the verdicts of a `label_correction.LabelCheck`: `write_kitti_corrected_gt`, `write_bdd_corrected_gt`
 
 Both are read back with `ast.literal_eval(line.replace("inf", "2e308"))` (active_learning_loop.py:532,
 SSL_stac.py:345, uncertainty_analysis.py).  The reference prints numpy-1 float32 scalars, whose repr is the shortest
@@ -314,3 +316,124 @@ def validate_to_file(driver, batches, gts, names, out_dir, box_calibrator=None, 
             f.writelines(model_performance(filtered))
     filtered["calibrated"] = cal
     return filtered
+
+
+# ---------------------------------------------------------------------------------- corrected ground truth (label correction)
+def _verdicts(check, wrong_gt, corrected_gt_boxes, missing_gt_boxes, pred_boxes, pred_classes):
+    """The lists `AdvancedLabels.corrected_gt` takes, each from `check` (a `label_correction.LabelCheck`) unless given."""
+    if check is not None:
+        wrong_gt = check.wrong_gt if wrong_gt is None else wrong_gt
+        corrected_gt_boxes = check.corrected_gt_boxes if corrected_gt_boxes is None else corrected_gt_boxes
+        missing_gt_boxes = check.extra_correct_dets if missing_gt_boxes is None else missing_gt_boxes
+        pred_boxes = check.pred_boxes if pred_boxes is None else pred_boxes
+        pred_classes = check.pred_classes if pred_classes is None else pred_classes
+    return wrong_gt, corrected_gt_boxes, missing_gt_boxes, pred_boxes, pred_classes
+
+
+def _need(flag, what, **lists):
+    for name, v in lists.items():
+        if flag and v is None:
+            raise ValueError("%s needs %s (or a LabelCheck)" % (what, name))
+
+
+def write_kitti_corrected_gt(gt_labels_dir, out_dir, file_names, used_classes, check=None, remove_mistakes=False, wrong_gt=None,
+                             correct_boxes=False, corrected_gt_boxes=None, add_missingboxes=False, missing_gt_boxes=None,
+                             pred_boxes=None, pred_classes=None):
+    """The KITTI label files of `AdvancedLabels.corrected_gt` (glc.py:231-306): for image i the lines of
+    gt_labels_dir/file_names[i] whose class is one of `used_classes`, in order, row j counting over those lines -
+    remove_mistakes drops the rows in wrong_gt[i]; correct_boxes rewrites fields 4-7 of the rows that stay with
+    corrected_gt_boxes[i][j] (x1 y1 x2 y2, `str` of the python float: an untouched box loses its file's formatting, as in the
+    reference); add_missingboxes appends one 15-field line per detection b with missing_gt_boxes[i][b], class
+    used_classes[int(pred_classes[i][b]) - 1], box pred_boxes[i][b].  A float32 coordinate must be given as the number the
+    reference reads back from its file (the shortest decimal; `LabelCheck` does that).  The lists come from `check` unless
+    given.  Writes out_dir/file_names[i]; returns the number of lines written.  (TFRecords are not written.)"""
+    import os
+    wrong_gt, corrected_gt_boxes, missing_gt_boxes, pred_boxes, pred_classes = _verdicts(
+        check, wrong_gt, corrected_gt_boxes, missing_gt_boxes, pred_boxes, pred_classes)
+    _need(remove_mistakes, "remove_mistakes", wrong_gt=wrong_gt)
+    _need(correct_boxes, "correct_boxes", corrected_gt_boxes=corrected_gt_boxes)
+    _need(add_missingboxes, "add_missingboxes", missing_gt_boxes=missing_gt_boxes, pred_boxes=pred_boxes, pred_classes=pred_classes)
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for i, fname in enumerate(file_names):
+        out_lines = []
+        with open(os.path.join(gt_labels_dir, fname), "r") as f:
+            j = 0
+            for line in f.readlines():
+                parts = line.strip().split(" ")
+                if len(parts) > 0 and parts[0] in used_classes:
+                    keep = not (remove_mistakes and j in wrong_gt[i])
+                    if correct_boxes and keep:
+                        box = corrected_gt_boxes[i][j]
+                        parts[4], parts[5], parts[6], parts[7] = str(box[1]), str(box[0]), str(box[3]), str(box[2])
+                    if keep:
+                        out_lines.append(parts)
+                    j += 1
+        if add_missingboxes:
+            for b in range(len(pred_boxes[i])):
+                if missing_gt_boxes[i][b]:
+                    box = pred_boxes[i][b]
+                    out_lines.append([used_classes[int(pred_classes[i][b]) - 1], "-1", "-1", "-10", str(box[1]), str(box[0]),
+                                      str(box[3]), str(box[2]), "-1", "-1", "-1", "-1000", "-1000", "-1000", "-10"])
+        with open(os.path.join(out_dir, fname), "w") as f:
+            f.writelines([" ".join(item) + "\n" for item in out_lines])
+        written += len(out_lines)
+    return written
+
+
+def write_bdd_corrected_gt(bdd_data, out_dir, image_names, used_classes, check=None, remove_mistakes=False, wrong_gt=None,
+                           correct_boxes=False, corrected_gt_boxes=None, add_missingboxes=False, missing_gt_boxes=None,
+                           pred_boxes=None, pred_classes=None):
+    """The BDD100K json of `AdvancedLabels.corrected_gt` (glc.py:327-406): bdd_data is the loaded label json (a list of items) or
+    its path; the items that carry a "labels" list and whose name is in `image_names` are written, in the JSON's order, with
+    the objects whose category is one of `used_classes` (row j counting over those) - the three modes as in
+    `write_kitti_corrected_gt`; an added object gets id str(j + b), the reference's attributes and the detection's box.  The
+    reference applies verdict i to the i-th written item: the items must therefore come in the order of `image_names`, and an
+    order that would pair an item with another image's verdicts is refused (the reference mislabels it silently).  The input
+    is not modified.  Writes out_dir/bdd100k_labels_images_train.json (json.dump, indent=4); returns the number of objects."""
+    import copy
+    import json
+    import os
+    wrong_gt, corrected_gt_boxes, missing_gt_boxes, pred_boxes, pred_classes = _verdicts(
+        check, wrong_gt, corrected_gt_boxes, missing_gt_boxes, pred_boxes, pred_classes)
+    _need(remove_mistakes, "remove_mistakes", wrong_gt=wrong_gt)
+    _need(correct_boxes, "correct_boxes", corrected_gt_boxes=corrected_gt_boxes)
+    _need(add_missingboxes, "add_missingboxes", missing_gt_boxes=missing_gt_boxes, pred_boxes=pred_boxes, pred_classes=pred_classes)
+    if isinstance(bdd_data, str):
+        with open(bdd_data, "r") as f:
+            bdd_data = json.load(f)
+    image_names = [str(nm) for nm in image_names]
+    wanted = set(image_names)
+    filtered_data, written, i = [], 0, 0
+    for item in bdd_data:
+        if "labels" in item and isinstance(item["labels"], list) and item["name"] in wanted:
+            if i >= len(image_names) or image_names[i] != item["name"]:
+                raise ValueError("write_bdd_corrected_gt: item %d of the json that is written is %r, the verdicts at that place belong "
+                                 "to %r: order image_names like the json" % (i, item["name"], image_names[min(i, len(image_names) - 1)]))
+            filtered_item = dict(item)
+            objs, j = [], 0
+            for obj in item["labels"]:
+                obj = copy.deepcopy(obj)
+                if obj["category"] in used_classes:
+                    keep = not (remove_mistakes and j in wrong_gt[i])
+                    if correct_boxes and keep:
+                        box = corrected_gt_boxes[i][j]
+                        obj["box2d"]["x1"], obj["box2d"]["y1"], obj["box2d"]["x2"], obj["box2d"]["y2"] = box[1], box[0], box[3], box[2]
+                    if keep:
+                        objs.append(obj)
+                    j += 1
+            if add_missingboxes:
+                for b in range(len(pred_boxes[i])):
+                    if missing_gt_boxes[i][b]:
+                        box = pred_boxes[i][b]
+                        objs.append({"id": str(j + b), "attributes": {"occluded": False, "truncated": False, "trafficLightColor": "G"},
+                                     "category": used_classes[int(pred_classes[i][b] - 1)],
+                                     "box2d": {"x1": box[1], "y1": box[0], "x2": box[3], "y2": box[2]}})
+            filtered_item["labels"] = objs
+            filtered_data.append(filtered_item)
+            written += len(objs)
+            i += 1
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "bdd100k_labels_images_train.json"), "w") as f:
+        json.dump(filtered_data, f, indent=4)
+    return written
