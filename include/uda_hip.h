@@ -28,6 +28,8 @@
  *                            (uncertainty_analysis.py:44-152)
  *   uda_hash_neighbors_np <- the distance matrix, its maximum and the rows of near-duplicates of
  *                            ActiveLearning.extract_hash_matrix (active_learning_loop.py:240-270)
+ *   uda_nn_dist2_np       <- the four KD-tree queries of emp_KL_divergence for every (class, method) of
+ *                            Similarity.calculate_set_similarity (active_learning_eval.py:481-487, 946-1029)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -556,6 +558,37 @@ int uda_thr_objective_np(int32_t device, const double* uncerts, const double* io
 #define UDA_PRUNE_MAX_N 1048576
 int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int32_t N, int32_t W, double prune_thr, int32_t max_distance,
                           int64_t cap, int32_t* max_dist, int64_t* row_off, int32_t* idx, int64_t* total);
+
+/* Set similarity: the neighbour search of the active-learning evaluation's set-similarity analysis (emp_KL_divergence,
+ * active_learning_eval.py:458-492, called twice per (class, method) by empirical_jensen_shannon_divergence :495-583 under
+ * Similarity.calculate_set_similarity :946-1029) - for B independent problems in one call, the squared Euclidean distance from
+ * every query point to its nearest reference point, in float64, without a handle and without the reference's KD-trees.  The KDE,
+ * the resampling, the square root, the logarithms and the sums are the caller's (set_similarity.py).
+ *   problems   problem b has n_b = q_off[b + 1] - q_off[b] query points, rows q_off[b].. of queries [q_off[B], D], and m_b =
+ *              r_off[b + 1] - r_off[b] reference points, rows r_off[b].. of refs [r_off[B], D]; q_off[0] = r_off[0] = 0
+ *   distance   d2(i, j) = ((x0 - y0)^2 + (x1 - y1)^2) + ... over the D coordinates in ascending order; every subtraction,
+ *              product and sum is rounded on its own (never fused).  d2[q_off[b] + i] = min over j of d2(i, j); no square root
+ *   self       self[b] != 0: the references ARE the queries (the caller passes the same points, m_b = n_b is not checked) and
+ *              reference row j == query row i is left out - an exact copy elsewhere is not, and gives 0.  A self problem with
+ *              m_b == 1 has no neighbour and yields +inf (KDTree.query(k=2)[:, 1]).  self == NULL: no problem is one
+ *   result     a minimum does not depend on the order it is taken in: d2 does not depend on how the device cuts the work, and
+ *              equals a sequential numpy sum with np.min bit for bit - for D <= 4 also scipy's cKDTree queried with eps=0
+ *              (squared).  Differences whose squares overflow give +inf, as numpy does
+ *   limits     1 <= D <= UDA_KNN_MAX_D, 1 <= B <= UDA_KNN_MAX_B, offsets ascending with 1 <= n_b, m_b <= UDA_KNN_MAX_N, and the
+ *              sum of n_b * m_b at most UDA_KNN_MAX_PAIRS; anything else is refused, never truncated, and d2 stays untouched.
+ *              UDA_KNN_MAX_PAIRS is there so that one call does not occupy a shared card for long; the time it corresponds to
+ *              has NOT been measured.  Values must be finite (the Python layer checks)
+ *   scratch    allocated and freed inside the call: the points, 8 * D * (q_off[B] + r_off[B]) bytes, the result, 8 * q_off[B],
+ *              the tables, 16 * (B + 1) + B, and 16 bytes per work item - at most max(2047, the row blocks of all problems).
+ * UDA_KNN_ROWS queries make a block, one per thread; UDA_KNN_COLS reference points are staged in LDS at a time. */
+#define UDA_KNN_ROWS 256
+#define UDA_KNN_COLS 512
+#define UDA_KNN_MAX_D 4
+#define UDA_KNN_MAX_N 1048576          /* points per set */
+#define UDA_KNN_MAX_B 4096             /* problems per call */
+#define UDA_KNN_MAX_PAIRS (1ll << 38)  /* sum of n_b * m_b per call */
+int uda_nn_dist2_np(int32_t device, int32_t D, int32_t B, const double* queries, const int64_t* q_off, const double* refs,
+                    const int64_t* r_off, const uint8_t* self, double* d2);
 
 /* Label correction (GLC): the verdicts of the reference's ground-truth label correction (AdvancedLabels, src/ssl_utils/glc.py) -
  * which ground-truth boxes are mistakes, which detections are missing labels, which noisy boxes are replaced by their detection -

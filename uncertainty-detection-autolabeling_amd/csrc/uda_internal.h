@@ -500,6 +500,26 @@ void launch_prune_count(const PruneArgs& a, hipStream_t s);
 void launch_prune_scan(const PruneArgs& a, hipStream_t s);
 void launch_prune_fill(const PruneArgs& a, hipStream_t s);
 
+// set similarity: the nearest-neighbour squared distances of emp_KL_divergence (reference active_learning_eval.py:481-487) for B
+// ragged problems in one launch (kernels_knn.hip).  The host cuts every problem into work items: KNN_ROWS queries x the chunks
+// [c0, c1) of KNN_COLS reference points; items of one row block that cover different spans meet in d2_bits by atomicMin.
+enum { KNN_ROWS = UDA_KNN_ROWS, KNN_COLS = UDA_KNN_COLS, KNN_MAX_D = UDA_KNN_MAX_D, KNN_MAX_ITEMS = 1 << 23 };
+struct KnnItem {
+  int32_t problem, row0, c0, c1;   // queries [row0, row0 + KNN_ROWS) of the problem against its reference chunks [c0, c1)
+};
+struct KnnArgs {
+  const double* queries;    // [q_off[B], D]
+  const double* refs;       // [r_off[B], D]
+  const int64_t* q_off;     // [B + 1]
+  const int64_t* r_off;     // [B + 1]
+  const uint8_t* self;      // [B] reference row j is the query row j itself and is left out; null: no problem is one
+  const KnnItem* items;     // [n_items]
+  unsigned long long* d2_bits;   // [total] the bit patterns of the minima; filled with +inf by the launch itself
+  int64_t total;            // q_off[B]
+  int D, n_items;
+};
+void launch_knn_min(const KnnArgs& a, hipStream_t s);
+
 // label correction (reference ssl_utils/glc.py): the three verdicts on one image's kept detections and counted ground-truth rows
 // (kernels_glc.hip).  T = float for the columns resident in a handle, double for host arrays (uda_label_check_np)
 enum { LC_MD = UDA_LC_MD, LC_MISTAKES = UDA_LC_MISTAKES, LC_NOISY = UDA_LC_NOISY };

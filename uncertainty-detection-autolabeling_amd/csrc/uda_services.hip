@@ -951,6 +951,57 @@ extern "C" int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int
   return 0;
 }
 
+// the neighbour search of the set-similarity analysis: B ragged problems in, one launch over a table of (problem, row block,
+// column span) work items, the squared distances out; its own allocations.  A call with fewer row blocks than kKnnBlocks cuts
+// every problem's reference chunks into as many spans as fill that many blocks, as the pruning step does; the spans meet by an
+// integer atomicMin, so the cut decides who finds a minimum and nothing about its value.
+static const int kKnnBlocks = 1024;
+extern "C" int uda_nn_dist2_np(int32_t device, int32_t D, int32_t B, const double* queries, const int64_t* q_off, const double* refs,
+                               const int64_t* r_off, const uint8_t* self, double* d2) {
+  const char* who = "uda_nn_dist2_np";
+  if (D < 1 || D > KNN_MAX_D) return fail(nullptr, "%s: %d coordinates, 1..%d are taken", who, D, (int)KNN_MAX_D);
+  if (B < 1 || B > UDA_KNN_MAX_B) return fail(nullptr, "%s: %d problems, 1..%d are taken", who, B, (int)UDA_KNN_MAX_B);
+  if (!queries || !q_off || !refs || !r_off || !d2) return fail(nullptr, "%s: NULL input", who);
+  if (q_off[0] != 0 || r_off[0] != 0) return fail(nullptr, "%s: offsets start at %lld and %lld, not at 0", who, (long long)q_off[0], (long long)r_off[0]);
+  int64_t pairs = 0, row_blocks = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = q_off[b + 1] - q_off[b], m = r_off[b + 1] - r_off[b];
+    if (n < 0 || m < 0) return fail(nullptr, "%s: the offsets of problem %d descend", who, b);
+    if (n == 0 || m == 0) return fail(nullptr, "%s: problem %d has an empty set (%lld queries, %lld references)", who, b, (long long)n, (long long)m);
+    if (n > UDA_KNN_MAX_N || m > UDA_KNN_MAX_N)
+      return fail(nullptr, "%s: problem %d has %lld queries and %lld references, at most %d each", who, b, (long long)n, (long long)m, (int)UDA_KNN_MAX_N);
+    pairs += n * m;                                            // at most 2^40 a problem, 2^52 a call
+    row_blocks += (n + KNN_ROWS - 1) / KNN_ROWS;
+  }
+  if (pairs > UDA_KNN_MAX_PAIRS)
+    return fail(nullptr, "%s: %lld pairs of points in one call, at most %lld", who, (long long)pairs, (long long)UDA_KNN_MAX_PAIRS);
+  const int64_t want_spans = std::max<int64_t>(1, (kKnnBlocks + row_blocks - 1) / row_blocks);
+  if (row_blocks > KNN_MAX_ITEMS) return fail(nullptr, "%s: %lld row blocks, at most %d (internal)", who, (long long)row_blocks, (int)KNN_MAX_ITEMS);
+  std::vector<KnnItem> items;
+  items.reserve((size_t)std::max<int64_t>(row_blocks, 2 * kKnnBlocks));
+  for (int b = 0; b < B; ++b) {
+    const int n = (int)(q_off[b + 1] - q_off[b]), m = (int)(r_off[b + 1] - r_off[b]);
+    const int n_chunks = (m + KNN_COLS - 1) / KNN_COLS;
+    const int spans = (int)std::min<int64_t>(n_chunks, want_spans);
+    const int per = (n_chunks + spans - 1) / spans;            // chunks per span; no empty span below
+    for (int row0 = 0; row0 < n; row0 += KNN_ROWS)
+      for (int c0 = 0; c0 < n_chunks; c0 += per) items.push_back(KnnItem{b, row0, c0, std::min(n_chunks, c0 + per)});
+  }
+  DevScratch s(device);
+  KnnArgs a{};
+  a.D = D; a.n_items = (int)items.size(); a.total = q_off[B];
+  a.queries = s.upload(queries, (size_t)q_off[B] * D); a.refs = s.upload(refs, (size_t)r_off[B] * D);
+  a.q_off = s.upload(q_off, (size_t)B + 1); a.r_off = s.upload(r_off, (size_t)B + 1);
+  a.self = s.upload(self, (size_t)B);
+  a.items = s.upload(items.data(), items.size());
+  a.d2_bits = s.alloc<unsigned long long>((size_t)a.total);
+  if (s.ok()) launch_knn_min(a, nullptr);
+  s.sync();
+  s.download(d2, a.d2_bits, (size_t)a.total * sizeof(double));
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  return 0;
+}
+
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,
                                  const int32_t* tab_off, const double* xs, const double* ys, const float* temps, float* out) {
   if (!c || !out) return c ? fail(c, "calibrate_box: NULL out") : 1;
