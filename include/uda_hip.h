@@ -30,6 +30,8 @@
  *                            ActiveLearning.extract_hash_matrix (active_learning_loop.py:240-270)
  *   uda_nn_dist2_np       <- the four KD-tree queries of emp_KL_divergence for every (class, method) of
  *                            Similarity.calculate_set_similarity (active_learning_eval.py:481-487, 946-1029)
+ *   uda_pseudo_audit_np   <- the matching, allocation and by-value tallies of Parent_SSL.extract_pseudo_gt_data and
+ *                            _percls_analysis (ssl_utils/parent.py:1567-1813), read by ThreeDproblem.corrected_pseudo (3d.py:80-255)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -589,6 +591,49 @@ int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int32_t N, int
 #define UDA_KNN_MAX_PAIRS (1ll << 38)  /* sum of n_b * m_b per call */
 int uda_nn_dist2_np(int32_t device, int32_t D, int32_t B, const double* queries, const int64_t* q_off, const double* refs,
                     const int64_t* r_off, const uint8_t* self, double* d2);
+
+/* Pseudo-label audit: how the STAC teacher's pseudo labels compare with the ground truth (Parent_SSL.extract_pseudo_gt_data and
+ * _percls_analysis, ssl_utils/parent.py:1567-1813; its members feed ThreeDproblem.corrected_pseudo, 3d.py:80-255, and
+ * Advanced_Pseudo_Labels._pls, pls.py:102-282) - for B ragged images in one call, without a handle.  Classes, the tallies per
+ * class, the label files and the PLS scores are the caller's (pseudo_audit.py, writers.py).
+ *   images     image b has G_b = gt_off[b + 1] - gt_off[b] ground-truth rows, rows gt_off[b].. of gt_boxes [gt_off[B], 4], and D_b =
+ *              det_off[b + 1] - det_off[b] pseudo labels, rows det_off[b].. of det_boxes [det_off[B], 4]; gt_off[0] = det_off[0] = 0.
+ *              Boxes are float64 in the order the reference's readers give (the IoU is symmetric in the two axes)
+ *   iou        calc_iou_np (utils_box.py:56-89) in float64: (areaA + areaB) - inter, 0 where the union is 0; never fused
+ *   per row    gt_max_iou[g] = max over the image's labels, gt_best_det[g] = the first label that reaches it (np.argmax,
+ *              :1736-1737; index within the image).  The MATCHED PREDICTIONS of an image are the distinct gt_best_det of its
+ *              rows with gt_max_iou >= gt_iou_thr (np.unique, :1736-1738), in ascending order; n_matches[b] counts them
+ *   per label  det_max_iou[d] = max over the image's rows, det_best_gt[d] = the first row that reaches it (3d.py:150-152)
+ *   allocation every matched prediction, in ascending order, takes the row of the best (IoU, lower row) among the rows not
+ *              yet taken (:1744-1752): det_alloc_gt[d] is that row (-1: d is not a matched prediction), gt_alloc_det[g] the
+ *              prediction that took row g (-1: none).  A prediction may take a row that did not choose it
+ *   ious       det_alloc_pair_iou[d] = IoU of the allocated pair (_percls_analysis :1572-1581; 0 where not allocated);
+ *              det_alloc_miou[d] = np.max of the row in the reference's MUTATED matrix (:1763-1765): the maximum over the
+ *              labels e of IoU(row, e), where an entry counts as -1 iff e is a matched prediction after d, and (IoU(row, e),
+ *              lower row) beats the row e took.  It may be below gt_max_iou of the row, and it may be -1
+ *   flags      det_flags[d] & UDA_AUDIT_DET_EXTRA: the label's box equals no allocated label's box in all four coordinates
+ *              (`pb[i] not in ab`, :1614-1619: the duplicate of an allocated box is not extra); gt_flags[g] &
+ *              UDA_AUDIT_GT_NOMATCH: the row's box equals no allocated row's box (:1629-1636)
+ *   empty      the reference raises on an image without a row or without a label.  Here such an image has no match: every
+ *              label is extra, every row unmatched, the maxima are 0 and the best indices -1
+ *   outputs    caller-allocated, length gt_off[B] per row, det_off[B] per label, B per image; any of them may be NULL.  Every
+ *              output is exact and does not depend on how the device deals rows to waves
+ *   limits     1 <= B <= UDA_AUDIT_MAX_B, offsets ascending from 0, at most UDA_AUDIT_MAX_G rows and UDA_AUDIT_MAX_D labels per
+ *              image, gt_iou_thr finite; anything else is refused, never truncated, and the outputs stay untouched.  The
+ *              allocation is sequential within an image (one wave, about G * D IoUs at worst); the caps bound it at about a
+ *              million IoUs per image so that one call does not occupy a shared card for long - the time this corresponds to
+ *              has NOT been measured.  Values must be finite (the Python layer checks); an IoU that is NaN orders as -1
+ *   scratch    allocated and freed inside the call: the boxes, 32 * (gt_off[B] + det_off[B]) bytes, the offsets, 16 * (B + 1), and
+ *              the results, 17 bytes per row, 33 per label and 4 per image. */
+#define UDA_AUDIT_DET_EXTRA 1    /* det_flags */
+#define UDA_AUDIT_GT_NOMATCH 1   /* gt_flags */
+#define UDA_AUDIT_MAX_G 1024     /* ground-truth rows per image */
+#define UDA_AUDIT_MAX_D 1024     /* pseudo labels per image */
+#define UDA_AUDIT_MAX_B 1048576  /* images per call */
+int uda_pseudo_audit_np(int32_t device, int32_t B, const double* gt_boxes, const int64_t* gt_off, const double* det_boxes,
+                        const int64_t* det_off, double gt_iou_thr, double* gt_max_iou, int32_t* gt_best_det, int32_t* gt_alloc_det,
+                        uint8_t* gt_flags, double* det_max_iou, int32_t* det_best_gt, int32_t* det_alloc_gt, double* det_alloc_miou,
+                        double* det_alloc_pair_iou, uint8_t* det_flags, int32_t* n_matches);
 
 /* Label correction (GLC): the verdicts of the reference's ground-truth label correction (AdvancedLabels, src/ssl_utils/glc.py) -
  * which ground-truth boxes are mistakes, which detections are missing labels, which noisy boxes are replaced by their detection -

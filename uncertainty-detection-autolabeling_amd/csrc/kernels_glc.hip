@@ -27,31 +27,12 @@
 // Two cases the reference does not reach are defined here: an image without a kept detection gives every row det_rank -1,
 // IoU 0 and no flag; an image without a counted row (the reference raises on np.argmax of an empty list) leaves every
 // detection's maximum at 0, and the missing-label rule is applied to that.
+#include "box_iou.h"
 #include "uda_internal.h"
 
 namespace uda {
 
-// calc_iou_np (utils_box.py:56-89) on float32 boxes: float32 coordinate differences, float64 products, union = (areaA + areaB)
-// - inter, 0 where the union is 0 - the arithmetic of iou_np in kernels_post.hip
-__device__ __forceinline__ double glc_iou(const float* a, const float* b) {
-  const float yA = fmaxf(a[0], b[0]), xA = fmaxf(a[1], b[1]);
-  const float yB = fminf(a[2], b[2]), xB = fminf(a[3], b[3]);
-  const double inter = (double)fmaxf(0.0f, xB - xA) * (double)fmaxf(0.0f, yB - yA);
-  const double areaA = (double)fabsf(a[3] - a[1]) * (double)fabsf(a[2] - a[0]);
-  const double areaB = (double)fabsf(b[3] - b[1]) * (double)fabsf(b[2] - b[0]);
-  const double uni = (areaA + areaB) - inter;
-  return uni != 0.0 ? inter / uni : 0.0;
-}
-// the same on float64 boxes (the literals read back from a prediction_data.txt): everything float64
-__device__ __forceinline__ double glc_iou(const double* a, const double* b) {
-  const double yA = fmax(a[0], b[0]), xA = fmax(a[1], b[1]);
-  const double yB = fmin(a[2], b[2]), xB = fmin(a[3], b[3]);
-  const double inter = fmax(0.0, xB - xA) * fmax(0.0, yB - yA);
-  const double areaA = fabs(a[3] - a[1]) * fabs(a[2] - a[0]);
-  const double areaB = fabs(b[3] - b[1]) * fabs(b[2] - b[0]);
-  const double uni = (areaA + areaB) - inter;
-  return uni != 0.0 ? inter / uni : 0.0;
-}
+// (glc_iou, the reference's calc_iou_np on float32 and on float64 boxes, is in box_iou.h)
 
 // dynamic LDS of a block: boxes [M][4] of T | packed ranks [M] int32 | `better` bits [(M + 31) / 32] uint32
 template <typename T>

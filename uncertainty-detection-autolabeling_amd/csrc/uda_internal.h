@@ -548,6 +548,29 @@ struct LabelCheckArgs {
 void launch_label_check(const LabelCheckArgs<float>& a, hipStream_t s);
 void launch_label_check(const LabelCheckArgs<double>& a, hipStream_t s);
 
+// pseudo-label audit (reference ssl_utils/parent.py:1567-1813): B ragged images, one block each (kernels_audit.hip).  Every output
+// is a device buffer of the call's own; rows and labels are addressed by the offsets, indices are within the image.
+struct AuditArgs {
+  const double* gt_boxes;       // [gt_off[B], 4]
+  const double* det_boxes;      // [det_off[B], 4]
+  const int64_t* gt_off;        // [B + 1]
+  const int64_t* det_off;       // [B + 1]
+  double* gt_max_iou;           // per row: the best IoU over the image's labels
+  int32_t* gt_best_det;         //          the first label that reaches it
+  int32_t* gt_alloc_det;        //          the matched prediction that took the row, -1: none
+  uint8_t* gt_flags;            //          UDA_AUDIT_GT_*
+  double* det_max_iou;          // per label: the best IoU over the image's rows
+  int32_t* det_best_gt;         //            the first row that reaches it
+  int32_t* det_alloc_gt;        //            the row a matched prediction took, -1: not a matched prediction
+  double* det_alloc_miou;       //            np.max of that row in the reference's mutated matrix
+  double* det_alloc_pair_iou;   //            IoU of the allocated pair, 0 where not allocated
+  uint8_t* det_flags;           //            UDA_AUDIT_DET_*
+  int32_t* n_matches;           // [B] matched predictions of the image
+  int B, max_g, max_d;          // max_g / max_d: the call's largest image, they size the block's LDS
+  double gt_iou_thr;
+};
+void launch_pseudo_audit(const AuditArgs& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

@@ -1,6 +1,6 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
 // COCO matching, the label check and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
-// on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, uda_nms, uda_debug_pw,
+// on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, the pseudo-label audit, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
 #include <stdio.h>
@@ -998,6 +998,74 @@ extern "C" int uda_nn_dist2_np(int32_t device, int32_t D, int32_t B, const doubl
   if (s.ok()) launch_knn_min(a, nullptr);
   s.sync();
   s.download(d2, a.d2_bits, (size_t)a.total * sizeof(double));
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  return 0;
+}
+
+// the pseudo-label audit: B ragged images in, one block each, the results in ONE device allocation, each array the caller asked
+// for copied out of it; its own allocations
+extern "C" int uda_pseudo_audit_np(int32_t device, int32_t B, const double* gt_boxes, const int64_t* gt_off, const double* det_boxes,
+                                   const int64_t* det_off, double gt_iou_thr, double* gt_max_iou, int32_t* gt_best_det,
+                                   int32_t* gt_alloc_det, uint8_t* gt_flags, double* det_max_iou, int32_t* det_best_gt,
+                                   int32_t* det_alloc_gt, double* det_alloc_miou, double* det_alloc_pair_iou, uint8_t* det_flags,
+                                   int32_t* n_matches) {
+  const char* who = "uda_pseudo_audit_np";
+  if (B < 1 || B > UDA_AUDIT_MAX_B) return fail(nullptr, "%s: %d images, 1..%d are taken", who, B, (int)UDA_AUDIT_MAX_B);
+  if (!gt_off || !det_off) return fail(nullptr, "%s: NULL offsets", who);
+  if (!(gt_iou_thr - gt_iou_thr == 0.0)) return fail(nullptr, "%s: gt_iou_thr %g is not finite", who, gt_iou_thr);
+  if (gt_off[0] != 0 || det_off[0] != 0)
+    return fail(nullptr, "%s: offsets start at %lld and %lld, not at 0", who, (long long)gt_off[0], (long long)det_off[0]);
+  int64_t max_g = 0, max_d = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t g = gt_off[b + 1] - gt_off[b], d = det_off[b + 1] - det_off[b];
+    if (g < 0 || d < 0) return fail(nullptr, "%s: the offsets of image %d do not ascend", who, b);
+    if (g > UDA_AUDIT_MAX_G || d > UDA_AUDIT_MAX_D)
+      return fail(nullptr, "%s: image %d has %lld ground-truth rows and %lld pseudo labels, at most %d and %d", who, b, (long long)g,
+                  (long long)d, (int)UDA_AUDIT_MAX_G, (int)UDA_AUDIT_MAX_D);
+    max_g = std::max(max_g, g); max_d = std::max(max_d, d);
+  }
+  const size_t NG = (size_t)gt_off[B], ND = (size_t)det_off[B];
+  if ((NG && !gt_boxes) || (ND && !det_boxes)) return fail(nullptr, "%s: NULL boxes", who);
+  // the pack: float64 [NG | ND | ND | ND], int32 [NG | NG | ND | ND | B], uint8 [NG | ND]
+  const size_t n64 = NG + 3 * ND, n32 = 2 * NG + 2 * ND + (size_t)B, n8 = NG + ND;
+  const size_t bytes = n64 * sizeof(double) + n32 * sizeof(int32_t) + n8;
+  DevScratch s(device);
+  AuditArgs a{};
+  a.B = B; a.max_g = (int)max_g; a.max_d = (int)max_d; a.gt_iou_thr = gt_iou_thr;
+  a.gt_boxes = s.upload(gt_boxes, NG * 4); a.det_boxes = s.upload(det_boxes, ND * 4);
+  a.gt_off = s.upload(gt_off, (size_t)B + 1); a.det_off = s.upload(det_off, (size_t)B + 1);
+  char* pack = s.alloc<char>(bytes);
+  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  auto lay = [&](char* base) {
+    double* f = (double*)base;
+    int32_t* i = (int32_t*)(f + n64);
+    uint8_t* u = (uint8_t*)(i + n32);
+    AuditArgs o{};
+    o.gt_max_iou = f; o.det_max_iou = f + NG; o.det_alloc_miou = f + NG + ND; o.det_alloc_pair_iou = f + NG + 2 * ND;
+    o.gt_best_det = i; o.gt_alloc_det = i + NG; o.det_best_gt = i + 2 * NG; o.det_alloc_gt = i + 2 * NG + ND;
+    o.n_matches = i + 2 * NG + 2 * ND;
+    o.gt_flags = u; o.det_flags = u + NG;
+    return o;
+  };
+  const AuditArgs dv = lay(pack);
+  a.gt_max_iou = dv.gt_max_iou; a.det_max_iou = dv.det_max_iou; a.det_alloc_miou = dv.det_alloc_miou;
+  a.det_alloc_pair_iou = dv.det_alloc_pair_iou; a.gt_best_det = dv.gt_best_det; a.gt_alloc_det = dv.gt_alloc_det;
+  a.det_best_gt = dv.det_best_gt; a.det_alloc_gt = dv.det_alloc_gt; a.n_matches = dv.n_matches; a.gt_flags = dv.gt_flags;
+  a.det_flags = dv.det_flags;
+  launch_pseudo_audit(a, nullptr);
+  s.sync();
+  // every array the caller asked for, straight from its place in the pack (no staging copy on the host)
+  s.download(gt_max_iou, dv.gt_max_iou, gt_max_iou ? NG * sizeof(double) : 0);
+  s.download(gt_best_det, dv.gt_best_det, gt_best_det ? NG * sizeof(int32_t) : 0);
+  s.download(gt_alloc_det, dv.gt_alloc_det, gt_alloc_det ? NG * sizeof(int32_t) : 0);
+  s.download(gt_flags, dv.gt_flags, gt_flags ? NG : 0);
+  s.download(det_max_iou, dv.det_max_iou, det_max_iou ? ND * sizeof(double) : 0);
+  s.download(det_best_gt, dv.det_best_gt, det_best_gt ? ND * sizeof(int32_t) : 0);
+  s.download(det_alloc_gt, dv.det_alloc_gt, det_alloc_gt ? ND * sizeof(int32_t) : 0);
+  s.download(det_alloc_miou, dv.det_alloc_miou, det_alloc_miou ? ND * sizeof(double) : 0);
+  s.download(det_alloc_pair_iou, dv.det_alloc_pair_iou, det_alloc_pair_iou ? ND * sizeof(double) : 0);
+  s.download(det_flags, dv.det_flags, det_flags ? ND : 0);
+  s.download(n_matches, dv.n_matches, n_matches ? (size_t)B * sizeof(int32_t) : 0);
   if (!s.ok()) return hip_failed(nullptr, who, s.err);
   return 0;
 }

@@ -8,6 +8,8 @@
                         `validate_to_file` is that whole loop
   corrected ground truth the KITTI label files and the BDD100K json of `AdvancedLabels.corrected_gt` (src/ssl_utils/glc.py:231-406)
                         for the verdicts of a `label_correction.LabelCheck`: `write_kitti_corrected_gt`, `write_bdd_corrected_gt`
+  corrected pseudo labels the KITTI label files and the BDD100K json of `ThreeDproblem.corrected_pseudo` (src/ssl_utils/3d.py:80-255)
+                        for a `pseudo_audit.PseudoCorrection`: `write_kitti_corrected_pseudo`, `write_bdd_corrected_pseudo`
 
 Both are read back with `ast.literal_eval(line.replace("inf", "2e308"))` (active_learning_loop.py:532,
 SSL_stac.py:345, uncertainty_analysis.py).  The reference prints numpy-1 float32 scalars, whose repr is the shortest
@@ -437,3 +439,99 @@ def write_bdd_corrected_gt(bdd_data, out_dir, image_names, used_classes, check=N
     with open(os.path.join(out_dir, "bdd100k_labels_images_train.json"), "w") as f:
         json.dump(filtered_data, f, indent=4)
     return written
+
+
+# ---------------------------------------------------------------------------------- corrected pseudo labels (pseudo-label audit)
+def _audit_sizes(who, name, n_pred, n_gt, audit, i):
+    if n_pred != audit.n_pred_perim[i] or n_gt != audit.n_gts_perim[i]:
+        raise ValueError("%s: image %r has %d pseudo labels and %d ground-truth rows of the used classes, the audit saw %d and %d"
+                         % (who, name, n_pred, n_gt, audit.n_pred_perim[i], audit.n_gts_perim[i]))
+
+
+def write_kitti_corrected_pseudo(det_folder, gt_labels_folder, out_dir, used_classes, audit, correction):
+    """The KITTI files of `ThreeDproblem.corrected_pseudo` (3d.py:115-164) for a `pseudo_audit.PseudoAudit` whose names are the
+    file names and a `PseudoCorrection` of it: per image the lines of det_folder/name, with the ground-truth lines of the used
+    classes of gt_labels_folder/name where the correction replaces or appends.  As in the reference, the `nonoise` branch cuts
+    EVERY line to 83 characters (dtype "<U83", :148-149), a dropped image and an image left without a line get no file, and the
+    lines are written as they were read.  A pseudo-label line outside `used_classes` would make the reference's line indices
+    and the audit's object indices disagree silently: it is refused.  Returns the number of files written."""
+    import os
+    f = correction.flags
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for i, name in enumerate(audit.names):
+        with open(os.path.join(det_folder, name), "r") as fh:
+            pred_lines = fh.readlines()
+        for k, line in enumerate(pred_lines):
+            if line.strip().split(" ")[0] not in used_classes:
+                raise ValueError("write_kitti_corrected_pseudo: line %d of %r is not of a used class; the reference would pair "
+                                 "the audit's object indices with other lines" % (k, name))
+        with open(os.path.join(gt_labels_folder, name), "r") as fh:
+            gt_lines = [line for line in fh.readlines() if line.strip().split(" ")[0] in used_classes]
+        _audit_sizes("write_kitti_corrected_pseudo", name, len(pred_lines), len(gt_lines), audit, i)
+        if correction.dropped[i]:
+            continue
+        new_lines = pred_lines
+        if f["remove_noise"]:
+            new_lines = np.asarray(new_lines, dtype="<U83")
+            repl = correction.replacements[i]
+            if len(repl):
+                new_lines[repl[:, 0]] = np.asarray(gt_lines, dtype="<U83")[repl[:, 1]]
+            new_lines = list(new_lines)
+        if f["remove_fds"] or f["high_precision"]:
+            new_lines = list(np.asarray(pred_lines)[correction.kept[i]]) if len(correction.kept[i]) else []
+        if len(correction.appended[i]):
+            new_lines = new_lines + list(np.asarray(gt_lines)[correction.appended[i]])
+        if len(new_lines) > 0:
+            with open(os.path.join(out_dir, name), "w") as fh:
+                fh.writelines(new_lines)
+            written += 1
+    return written
+
+
+def write_bdd_corrected_pseudo(pred_items, bdd_data, out_dir, used_classes, audit, correction):
+    """The pseudo_labels.json of `ThreeDproblem.corrected_pseudo` (3d.py:167-233): pred_items is the loaded pseudo-label json (or
+    its path), bdd_data the loaded ground-truth json (or its path); the audit's images are pred_items, in order.  Per item the
+    labels are kept, replaced by the ground-truth objects of the used classes, or appended to, as the correction says; a
+    dropped image loses its entry.  As in the reference, an item whose selector is empty stays as it was, whatever the
+    correction (:189).  A pseudo label outside `used_classes`, or an item order other than the audit's, would pair indices
+    with other objects silently: both are refused.  The inputs are not modified.  Writes out_dir/pseudo_labels.json
+    (json.dump, indent=4); returns the number of items written."""
+    import copy
+    import json
+    import os
+    if isinstance(pred_items, str):
+        with open(pred_items, "r") as fh:
+            pred_items = json.load(fh)
+    if isinstance(bdd_data, str):
+        with open(bdd_data, "r") as fh:
+            bdd_data = json.load(fh)
+    pred_items = copy.deepcopy(pred_items)
+    f = correction.flags
+    if [item["name"] for item in pred_items] != [str(nm) for nm in audit.names]:
+        raise ValueError("write_bdd_corrected_pseudo: the items of the pseudo-label json are not the audit's images in its order")
+    gt_im_names = np.asarray([item["name"] for item in bdd_data])
+    for i, item in enumerate(pred_items):
+        gt_i = np.where(item["name"] == gt_im_names)[0][0]
+        for k, obj in enumerate(item["labels"]):
+            if obj["category"] not in used_classes:
+                raise ValueError("write_bdd_corrected_pseudo: label %d of %r is not of a used class; the reference would pair the "
+                                 "audit's object indices with other labels" % (k, item["name"]))
+        gt_objs = [copy.deepcopy(g) for g in bdd_data[gt_i]["labels"] if g["category"] in used_classes]
+        _audit_sizes("write_bdd_corrected_pseudo", item["name"], len(item["labels"]), len(gt_objs), audit, i)
+        if len(correction.selector[i]) > 0:
+            if correction.dropped[i]:
+                del pred_items[i]["labels"]
+                continue
+            new_items = list(item["labels"])
+            for d, r in correction.replacements[i]:
+                new_items[d] = gt_objs[r]
+            if f["remove_fds"] or f["high_precision"]:
+                new_items = [item["labels"][d] for d in correction.kept[i]]
+            new_items += [gt_objs[r] for r in correction.appended[i]]
+            pred_items[i]["labels"] = new_items
+    out = [item for item in pred_items if "labels" in item]
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "pseudo_labels.json"), "w") as fh:
+        json.dump(out, fh, indent=4)
+    return len(out)
