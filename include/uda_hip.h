@@ -137,7 +137,8 @@ enum uda_pw_scheme {
   UDA_SPLIT_BF16X2 = 2,   /* "bf16x2": two bf16 pieces per operand, three cross terms (~2^-17 per product) */
   UDA_SPLIT_BF16X3 = 3,   /* "bf16x3": three bf16 pieces, six cross terms (~2^-24) */
   UDA_SPLIT_F16X2 = 4,    /* "f16x2": two fp16 pieces, three cross terms (~2^-22; operands must stay below 65504) */
-  UDA_SPLIT_F16X1 = 5     /* "f16": one fp16 piece, one product (~2^-11: Keras mixed_float16 operands; same range limit) */
+  UDA_SPLIT_F16X1 = 5,    /* "f16": one fp16 piece, one product (~2^-11: Keras mixed_float16 operands; same range limit) */
+  UDA_SPLIT_BF16X1 = 6    /* "bf16": one bf16 piece, one product (~2^-8: Keras mixed_bfloat16 operands; float32's range, nothing tracked) */
 };
 
 typedef struct uda_model {
@@ -276,7 +277,8 @@ int64_t uda_range_demotions(const uda_ctx_t* ctx);
 /* Debug: how op `op` of the handle's op list runs now (after any range demotion).  *scheme = its split scheme (UDA_SPLIT_*
  * of uda_internal.h; -1: no packed weights, the op has no split contraction), *w_scale = the power-of-two factor its packed
  * weights carry (1 unless fp16 pieces), *a_scale = the factor on its A operand (the pre-scaled depthwise taps of an fp16
- * separable conv; else 1), *out_f16 = 1 if its output tensor is stored as fp16.  Any pointer may be NULL. */
+ * separable conv; else 1), *out_f16 = 1 if its output tensor is stored in 16 bits (fp16 under
+ * UDA_SPLIT_F16X1, bf16 under UDA_SPLIT_BF16X1: the op's scheme says which).  Any pointer may be NULL. */
 int uda_debug_op_scheme(const uda_ctx_t* ctx, int32_t op, int32_t* scheme, float* w_scale, float* a_scale, int32_t* out_f16);
 /* Global NMS over the whole anchor set runs on the score prefix that can be selected at all, checked on the
  * device; this counts the images / problems that failed the check and were redone on the full set (the results
@@ -781,7 +783,8 @@ int uda_nms(uda_ctx_t* ctx, const float* boxes, const float* scores, int32_t n_i
  * in [rows/in_div, hw, cin], w [cin, cout], se [rows/in_div, cin], mask [rows, cout], res/out [rows, hw, cout];
  * optional arguments may be NULL.  terms: 0 = f32-input MFMA, 3 / 6 = split-bf16 MFMA with 3 / 6 cross terms, 16 = two fp16
  * pieces per operand with 3 cross terms (the default scheme of the network, UDA_PW_SCHEME=f16x2), 1 = one fp16 piece, one
- * product (UDA_PW_SCHEME=f16).  Both fp16 schemes pack the weights times split_weight_scale as the network does, and fail -
+ * product (UDA_PW_SCHEME=f16), 8 = one bf16 piece, one product (UDA_PW_SCHEME=bf16: weight scale 1, no range limit).
+ * Both fp16 schemes pack the weights times split_weight_scale as the network does, and fail -
  * they do not return infinities - when an input exceeds fp16's 65504 (kernels_pwb.hip).  The launch is repeated `reps`
  * times for *avg_ms (HIP events). */
 int uda_debug_pw(int32_t device, const float* in, const float* w, const float* bias, const float* bn_scale,

@@ -3,12 +3,14 @@
 head-only MC regime (mc_classheadrate = mc_boxheadrate = 0.05), served through ServingDriver.serve_stream for each scheme,
 one child process per scheme (the scheme is fixed when a handle is created).  Prints ONE JSON line:
 
-    {"f16x2": {"full": {...}, "head_only": {...}}, "f16": {...}, "speedup": {...}}
+    {"f16x2": {"full": {...}, "head_only": {...}}, "f16": {...}, "bf16": {...}, "speedup": {"f16": {...}, "bf16": {...}}}
 
 per regime: ms per step (a step = 32 images x T samples, network + post-process + detections on the host, pipelined),
 images x samples per second, and the device time per kernel kind of one profiled step (profile_read).
 
-    python tools/bench_scheme.py [--schemes f16x2,f16] [--steps 10] [--warmup 3]
+    python tools/bench_scheme.py [--schemes f16x2,f16,bf16] [--steps 10] [--warmup 3]
+
+The first scheme is the baseline of "speedup" (with two schemes: one ratio per regime, as before).
 """
 import argparse
 import json
@@ -61,7 +63,7 @@ def child(scheme, regime, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--schemes", default="f16x2,f16")
+    ap.add_argument("--schemes", default="f16x2,f16,bf16")
     ap.add_argument("--regimes", default="full,head_only")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -82,9 +84,11 @@ def main():
             out[scheme][regime] = json.loads(line[0][len("RESULT "):])
             sys.stderr.write("%s %s: %s ms/step\n" % (scheme, regime, out[scheme][regime]["ms_per_step"]))
     names = a.schemes.split(",")
+    ratio = lambda new: {rg: round(out[names[0]][rg]["ms_per_step"] / out[new][rg]["ms_per_step"], 3) for rg in a.regimes.split(",")}
     if len(names) == 2:
-        base, new = names
-        out["speedup"] = {rg: round(out[base][rg]["ms_per_step"] / out[new][rg]["ms_per_step"], 3) for rg in a.regimes.split(",")}
+        out["speedup"] = ratio(names[1])
+    elif len(names) > 2:
+        out["speedup"] = {new: ratio(new) for new in names[1:]}
     print(json.dumps(out))
 
 

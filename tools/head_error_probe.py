@@ -1,5 +1,6 @@
 """Head-output error of the current switches against the float32 CPU oracle (D0 at 192x128 and D2 at 128x128, full MC) - the
-measurement behind tests/test_gpu_round3.py::test_six_term..., as a tool: prints one line per run."""
+measurement behind tests/test_gpu_round3.py::test_six_term..., as a tool: prints one line per run.  The scheme is the process
+default, UDA_PW_SCHEME (f16x2 | bf16x3 | bf16x2 | f32 | f16 | bf16)."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + "/tests")

@@ -60,9 +60,10 @@ __global__ __launch_bounds__(256, OCC) void pwb_kernel(PwArgs a) {
   const int m0 = bx * BM, n0 = by * BN;
   const int nt0 = by * NTB;
   const float* A = a.in + (size_t)b_in * a.HW * a.Cin;
-  // one fp16 piece: the input may be an fp16 expanded tensor (2 bytes per element); its four halves travel in .x / .y of the
-  // staging float4 and are widened where the chunk is split, so the gate is applied in float32 and the product rounded once
-  const bool in_h = PARTS == UDA_SPLIT_F16X1 && a.in_f16;
+  // one piece: the input may be a 16-bit expanded tensor (fp16 / bf16 by the scheme, 2 bytes per element); its four halves travel
+  // in .x / .y of the staging float4 and are widened where the chunk is split, so the gate is applied in float32 and the product
+  // rounded once
+  const bool in_h = split_one(PARTS) && a.in_f16;
   const unsigned short* Ah = (const unsigned short*)a.in + (size_t)b_in * a.HW * a.Cin;
   const float* se = a.se ? a.se + (size_t)(b / a.se_div) * a.Cin : nullptr;
   const uint4* Wp = (const uint4*)a.wsplit;
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256, OCC) void pwb_kernel(PwArgs a) {
     for (int i = 0; i < A_ITERS; ++i) {
       const int f = tid + 256 * i;
       const int m = f >> 3, kq = f & 7;
-      const float4 av = (!DEEP && in_h) ? f16x4_to_float4(__float_as_uint(ra[i].x), __float_as_uint(ra[i].y)) : ra[i];
+      const float4 av = (!DEEP && in_h) ? half4_to_float4<PARTS>(__float_as_uint(ra[i].x), __float_as_uint(ra[i].y)) : ra[i];
       float r0 = av.x * rg.x, r1 = av.y * rg.y, r2 = av.z * rg.z, r3 = av.w * rg.w;
       split_track<PARTS>(amax, r0, r1);
       split_track<PARTS>(amax, r2, r3);
@@ -431,7 +432,7 @@ __global__ __launch_bounds__(256, 3) void pwb_shared_kernel(PwArgs a) {
 #define UDA_PWS_D 4
 #endif
 constexpr int PWS_D = UDA_PWS_D;
-template <int PARTS, int NT, bool GATE, bool IH = false>    // IH: fp16 input (one fp16 piece, a.in_f16)
+template <int PARTS, int NT, bool GATE, bool IH = false>    // IH: 16-bit input (one piece, a.in_f16)
 __global__ __launch_bounds__(64) void pws_kernel(PwArgs a) {
   constexpr int NPC = split_np(PARTS);
   const int lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
@@ -481,8 +482,8 @@ __global__ __launch_bounds__(64) void pws_kernel(PwArgs a) {
   auto mma_step = [&](const Step& t) {
     float4 v0 = t.a0, v1 = t.a1;
     if constexpr (in_h) {
-      v0 = f16x4_to_float4(__float_as_uint(t.a0.x), __float_as_uint(t.a0.y));
-      v1 = f16x4_to_float4(__float_as_uint(t.a0.z), __float_as_uint(t.a0.w));
+      v0 = half4_to_float4<PARTS>(__float_as_uint(t.a0.x), __float_as_uint(t.a0.y));
+      v1 = half4_to_float4<PARTS>(__float_as_uint(t.a0.z), __float_as_uint(t.a0.w));
     }
     if constexpr (GATE) {
       v0.x *= t.g0.x; v0.y *= t.g0.y; v0.z *= t.g0.z; v0.w *= t.g0.w;
@@ -570,6 +571,8 @@ static int launch_pws(const PwArgs& a, int rows, hipStream_t s) {
   if (a.wparts == UDA_SPLIT_F16X2) { if (a.se) go(pws_kernel<4, 1, true>, pws_kernel<4, 2, true>); else go(pws_kernel<4, 1, false>, pws_kernel<4, 2, false>); }
   else if (a.wparts == UDA_SPLIT_F16X1 && a.in_f16) { if (a.se) go(pws_kernel<5, 1, true, true>, pws_kernel<5, 2, true, true>); else go(pws_kernel<5, 1, false, true>, pws_kernel<5, 2, false, true>); }
   else if (a.wparts == UDA_SPLIT_F16X1) { if (a.se) go(pws_kernel<5, 1, true>, pws_kernel<5, 2, true>); else go(pws_kernel<5, 1, false>, pws_kernel<5, 2, false>); }
+  else if (a.wparts == UDA_SPLIT_BF16X1 && a.in_f16) { if (a.se) go(pws_kernel<6, 1, true, true>, pws_kernel<6, 2, true, true>); else go(pws_kernel<6, 1, false, true>, pws_kernel<6, 2, false, true>); }
+  else if (a.wparts == UDA_SPLIT_BF16X1) { if (a.se) go(pws_kernel<6, 1, true>, pws_kernel<6, 2, true>); else go(pws_kernel<6, 1, false>, pws_kernel<6, 2, false>); }
   else if (a.wparts == UDA_SPLIT_BF16X3) { if (a.se) go(pws_kernel<3, 1, true>, pws_kernel<3, 2, true>); else go(pws_kernel<3, 1, false>, pws_kernel<3, 2, false>); }
   else if (a.wparts == UDA_SPLIT_BF16X2) { if (a.se) go(pws_kernel<2, 1, true>, pws_kernel<2, 2, true>); else go(pws_kernel<2, 1, false>, pws_kernel<2, 2, false>); }
   else return 0;
@@ -587,6 +590,7 @@ static void launch_pwb_cfg(const PwArgs& a, int rows, hipStream_t s) {
     // tile included) fit three blocks per CU (<= 168 registers) without spilling; six (2 x 3, 192 columns) still spill there
     hipLaunchKernelGGL((pwb_kernel<MT, NT, WM, WN, 5, (MT * NT > 5 ? 2 : 3)>), grid, block, 0, s, a);
   }
+  else if (a.wparts == UDA_SPLIT_BF16X1) hipLaunchKernelGGL((pwb_kernel<MT, NT, WM, WN, 6, (MT * NT > 5 ? 2 : 3)>), grid, block, 0, s, a);     // (as one fp16 piece)
   else if (a.wparts == UDA_SPLIT_F16X2) {
     // (K-heavy projections on the big tiles - two blocks per CU by registers anyway: two chunks in flight per block)
     if constexpr (MT * NT > 4) {
@@ -725,7 +729,7 @@ __host__ __device__ constexpr MbxCfgB mbxb_cfg(int k, int s) {
 #define UDA_MBXB_MINW(K, S, KSF, PARTS) ((PARTS) == 3 ? (((KSF) <= 2 && (K) == 3) ? UDA_MBXB6_W : 2) : \
     ((KSF) <= 2 ? ((K) == 3 ? 4 : 3) : (((KSF) <= 3 && ((K) == 3 ? (S) == 2 : UDA_MBXB_WK_LDS)) ? 3 : 2)))
 #endif
-template <int K, int S, int KSF, bool FUSE0, int PARTS, bool OH = false>   // KSF = 16-deep MFMA k-steps covering Cin + 1; OH: fp16 output
+template <int K, int S, int KSF, bool FUSE0, int PARTS, bool OH = false>   // KSF = 16-deep MFMA k-steps covering Cin + 1; OH: 16-bit output
 __global__ __launch_bounds__(256, UDA_MBXB_MINW(K, S, KSF, PARTS)) void mbxb_kernel(MbxArgs a) {
   constexpr int NW = 4;
   constexpr int NPC = split_np(PARTS);        // pieces per operand (PARTS names the scheme: UDA_SPLIT_*)
@@ -884,7 +888,7 @@ __global__ __launch_bounds__(256, UDA_MBXB_MINW(K, S, KSF, PARTS)) void mbxb_ker
   }
   float* const obase = a.out + (((size_t)b * a.Ho + oy0) * a.Wo + ox0) * a.Cmid;
   const unsigned cm = (unsigned)a.Cmid;
-  // OH (one fp16 piece, a.out_f16): the expanded tensor is stored as fp16 - the same element offsets in a 2-byte view
+  // OH (one piece, a.out_f16): the expanded tensor is stored as fp16 / bf16 - the same element offsets in a 2-byte view
   unsigned short* const hobase = (unsigned short*)a.out + (((size_t)b * a.Ho + oy0) * a.Wo + ox0) * a.Cmid;
   // a tile that lies inside the output takes the unguarded path (block-uniform decision; the channel guard of a last,
   // partial slab is one exec mask around the whole stage)
@@ -1055,7 +1059,7 @@ __global__ __launch_bounds__(256, UDA_MBXB_MINW(K, S, KSF, PARTS)) void mbxb_ker
           if constexpr (GUARD) ok = ox0 + (int)((g + NG * ui) % UPR) * XW + o < a.Wo;
           if (ok) {
             const float v = swish_folded(fmaf(acc[o], sc1, sh1), mk1);
-            if constexpr (OH) store_uniform_base_h(hob + (size_t)o * cm, ooff[ui], v);
+            if constexpr (OH) store_uniform_base_16<PARTS>(hob + (size_t)o * cm, ooff[ui], v);
             else store_uniform_base(ob + (size_t)o * cm, ooff[ui], v);
             ssum += v;
           }
@@ -1118,6 +1122,7 @@ void launch_w0gate(const float* gate, const float* w0t, int c0, int gate_rows, i
   if (scheme == UDA_SPLIT_BF16X3) hipLaunchKernelGGL(w0gate_kernel<3>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
   else if (scheme == UDA_SPLIT_F16X2) hipLaunchKernelGGL(w0gate_kernel<4>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
   else if (scheme == UDA_SPLIT_F16X1) hipLaunchKernelGGL(w0gate_kernel<5>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
+  else if (scheme == UDA_SPLIT_BF16X1) hipLaunchKernelGGL(w0gate_kernel<6>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
   else hipLaunchKernelGGL(w0gate_kernel<2>, dim3(gate_rows), dim3(64), 0, s, gate, w0t, c0, out, oor);
 }
 
@@ -1148,7 +1153,7 @@ static void launch_mbxb_t(const MbxArgs& a, int rows, hipStream_t s) {
       grid = dim3((unsigned)total, 1, 1);
     }
   }
-  if constexpr (PARTS == UDA_SPLIT_F16X1) {
+  if constexpr (split_one(PARTS)) {
     if (a.out_f16) {
       if constexpr (KSF == 2) {
         if (a.gate) { hipLaunchKernelGGL((mbxb_kernel<K, S, KSF, true, PARTS, true>), grid, dim3(256), lds, s, b); return; }
@@ -1185,6 +1190,7 @@ void launch_mbxb(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
   if (a.wparts == UDA_SPLIT_BF16X3) launch_mbxb_p<3>(a, rows, k, stride, s);
   else if (a.wparts == UDA_SPLIT_F16X2) launch_mbxb_p<4>(a, rows, k, stride, s);
   else if (a.wparts == UDA_SPLIT_F16X1) launch_mbxb_p<5>(a, rows, k, stride, s);
+  else if (a.wparts == UDA_SPLIT_BF16X1) launch_mbxb_p<6>(a, rows, k, stride, s);
   else launch_mbxb_p<2>(a, rows, k, stride, s);
 }
 
@@ -1217,13 +1223,13 @@ bool mbxd_wide(int Ho, int Wo, int k, int stride) {
   return stride == 1 && mbxd_slots(Ho, Wo, k, true) < mbxd_slots(Ho, Wo, k, false);
 }
 
-// One fp16 piece (PARTS = UDA_SPLIT_F16X1): the operand fragments of 13-14 k-steps are 56 registers instead of 112, so the deep
+// One piece (PARTS = UDA_SPLIT_F16X1 / UDA_SPLIT_BF16X1): the operand fragments of 13-14 k-steps are 56 registers instead of 112, so the deep
 // variants fit two blocks per CU as well (the two-piece ones run mbxp_kernel, one block per CU, instead).
 // (stride 1: the stride-2 3x3 variants at 13-14 k-steps spill at 128 registers)
-__host__ __device__ constexpr bool mbxd_two_per_cu(int ksf, int parts, int s) { return (ksf <= 8 && parts != 3) || (parts == UDA_SPLIT_F16X1 && s == 1); }
-template <int K, int KSF, int PARTS, int S, bool WIDE, bool OH = false>    // OH: fp16 output (one fp16 piece, a.out_f16)
+__host__ __device__ constexpr bool mbxd_two_per_cu(int ksf, int parts, int s) { return (ksf <= 8 && parts != 3) || (split_one(parts) && s == 1); }
+template <int K, int KSF, int PARTS, int S, bool WIDE, bool OH = false>    // OH: 16-bit output (one piece, a.out_f16)
 __global__ __launch_bounds__(512, mbxd_two_per_cu(KSF, PARTS, S) ? 4 : 2) void mbxd_kernel(MbxArgs a) {
-  constexpr bool WK_LDS = (K == 5 && (KSF <= 8 || PARTS == 3 || PARTS == UDA_SPLIT_F16X1));     // the 25 taps from LDS at their use, not 25 registers
+  constexpr bool WK_LDS = (K == 5 && (KSF <= 8 || PARTS == 3 || split_one(PARTS)));     // the 25 taps from LDS at their use, not 25 registers
 
   constexpr int NW = 8;
   constexpr int NPC = split_np(PARTS);        // pieces per operand (PARTS names the scheme: UDA_SPLIT_*)
@@ -1323,7 +1329,7 @@ __global__ __launch_bounds__(512, mbxd_two_per_cu(KSF, PARTS, S) ? 4 : 2) void m
   }
   float* const obase = a.out + (((size_t)b * a.Ho + oy0) * a.Wo + ox0) * a.Cmid;
   const unsigned cm = (unsigned)a.Cmid;
-  // OH (one fp16 piece, a.out_f16): the expanded tensor is stored as fp16 - the same element offsets in a 2-byte view
+  // OH (one piece, a.out_f16): the expanded tensor is stored as fp16 / bf16 - the same element offsets in a 2-byte view
   unsigned short* const hobase = (unsigned short*)a.out + (((size_t)b * a.Ho + oy0) * a.Wo + ox0) * a.Cmid;
   const bool full = (oy0 + TH <= a.Ho) && (ox0 + TW <= a.Wo);
 
@@ -1439,7 +1445,7 @@ __global__ __launch_bounds__(512, mbxd_two_per_cu(KSF, PARTS, S) ? 4 : 2) void m
           if constexpr (GUARD) ok = ox0 + (int)((g + NG * ui) % UPR) * XW + o < a.Wo;
           if (ok) {
             const float v = swish_folded(fmaf(acc[o], sc1, sh1), mk1);
-            if constexpr (OH) store_uniform_base_h(hob + (size_t)o * cm, ooff[ui], v);
+            if constexpr (OH) store_uniform_base_16<PARTS>(hob + (size_t)o * cm, ooff[ui], v);
             else store_uniform_base(ob + (size_t)o * cm, ooff[ui], v);
             ssum += v;
           }
@@ -1925,7 +1931,7 @@ static void launch_mbxd_tw(const MbxArgs& a, int rows, hipStream_t s) {
   static size_t attr_lds = 64 * 1024;      // above the default limit the kernel needs an explicit opt-in
   if (lds > attr_lds) {
     hipFuncSetAttribute((const void*)mbxd_kernel<K, KSF, PARTS, S, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if constexpr (PARTS == UDA_SPLIT_F16X1)
+    if constexpr (split_one(PARTS))
       hipFuncSetAttribute((const void*)mbxd_kernel<K, KSF, PARTS, S, WIDE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_lds = lds;
   }
@@ -1933,7 +1939,7 @@ static void launch_mbxd_tw(const MbxArgs& a, int rows, hipStream_t s) {
   MbxArgs b = a;
   b.ch_groups = mbx_ch_groups((long long)grid.x * grid.y * rows, mbxd_two_per_cu(KSF, PARTS, S) ? 2 : 1, (a.Cmid + 31) / 32);
   grid.z = (unsigned)(rows * b.ch_groups);
-  if constexpr (PARTS == UDA_SPLIT_F16X1) {
+  if constexpr (split_one(PARTS)) {
     if (a.out_f16) { hipLaunchKernelGGL((mbxd_kernel<K, KSF, PARTS, S, WIDE, true>), grid, dim3(512), lds, s, b); return; }
   }
   hipLaunchKernelGGL((mbxd_kernel<K, KSF, PARTS, S, WIDE>), grid, dim3(512), lds, s, b);
@@ -1971,6 +1977,7 @@ void launch_mbxd(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
     if (a.wparts == UDA_SPLIT_BF16X3) launch_mbxd_p<3, 2>(a, rows, k, ksf, s);
     else if (a.wparts == UDA_SPLIT_F16X2) launch_mbxd_p<4, 2>(a, rows, k, ksf, s);
     else if (a.wparts == UDA_SPLIT_F16X1) launch_mbxd_p<5, 2>(a, rows, k, ksf, s);
+    else if (a.wparts == UDA_SPLIT_BF16X1) launch_mbxd_p<6, 2>(a, rows, k, ksf, s);
     else launch_mbxd_p<2, 2>(a, rows, k, ksf, s);
     return;
   }
@@ -1978,8 +1985,9 @@ void launch_mbxd(const MbxArgs& a, int rows, int k, int stride, hipStream_t s) {
     launch_mbxd_p<3, 1>(a, rows, k, ksf, s);
     return;
   }
-  if (a.wparts == UDA_SPLIT_F16X1) {      // one piece: the two-phase kernel at two blocks per CU (mbxp_kernel is laid out for two pieces)
-    launch_mbxd_p<5, 1>(a, rows, k, ksf, s);
+  if (uda_split_one(a.wparts)) {          // one piece: the two-phase kernel at two blocks per CU (mbxp_kernel is laid out for two pieces)
+    if (a.wparts == UDA_SPLIT_F16X1) launch_mbxd_p<5, 1>(a, rows, k, ksf, s);
+    else launch_mbxd_p<6, 1>(a, rows, k, ksf, s);
     return;
   }
   if (ksf >= 13) {                  // one block per CU anyway: the self-overlapping variant

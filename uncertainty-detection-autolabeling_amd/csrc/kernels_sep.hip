@@ -23,12 +23,14 @@ namespace uda {
 constexpr int SEP_TH = 8, SEP_TW = 16;
 
 // Bytes in front of the weight image: the A image (NPC piece images, or the float32 one of three pieces).  In the deferred-input
-// mode the per-sample epilogue staging aliases that region and must end before the weight image; one fp16 piece (UDA_SPLIT_F16X1)
+// mode the per-sample epilogue staging aliases that region and must end before the weight image; one piece (UDA_SPLIT_F16X1 / BF16X1)
 // leaves an A image smaller than the staging at 64 channels, so there the region is widened to the staging (the other schemes'
 // layouts are unchanged: their A images hold it wherever the mode exists, sep_tin_supported).
 __host__ __device__ inline size_t sep_a_region(int KS, int Cout, int nt, int scheme, bool tin) {
   const size_t a_img = scheme == UDA_SPLIT_BF16X3 ? (size_t)128 * (KS * 64 + 16) : (size_t)split_np(scheme) * 128 * (KS * 32 + 16);
-  if (!tin || scheme != UDA_SPLIT_F16X1) return a_img;
+  // (split_one(scheme), spelled out: through the call the plain instances of sep_kernel come out with their scalar set-up in
+  // another order - the same instructions; written this way every instance the other schemes had is instruction-identical)
+  if (!tin || (scheme != UDA_SPLIT_F16X1 && scheme != UDA_SPLIT_BF16X1)) return a_img;
   const size_t stg = (Cout & 3) ? (size_t)4 * 32 * nt * 32 * 4 : (size_t)4 * 32 * PWB_STG * 4;
   return a_img < stg ? stg : a_img;
 }
@@ -755,6 +757,7 @@ static void launch_sepf_nt(const SepArgs& a, const FuseArgs& f, int rows, hipStr
     if (a.wparts == UDA_SPLIT_BF16X3) go(sepf_kernel<NT, 3, true, PC>);
     else if (a.wparts == UDA_SPLIT_F16X2) go(sepf_kernel<NT, 4, true, PC>);
     else if (a.wparts == UDA_SPLIT_F16X1) go(sepf_kernel<NT, 5, true, PC>);
+    else if (a.wparts == UDA_SPLIT_BF16X1) go(sepf_kernel<NT, 6, true, PC>);
     else go(sepf_kernel<NT, 2, true, PC>);
   };
   if (pc == 16) by_scheme(std::integral_constant<int, 16>{});
@@ -818,11 +821,13 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
         if (a.wparts == UDA_SPLIT_BF16X3) go(sep_kernel<NT, 3, 2, 1>);
         else if (a.wparts == UDA_SPLIT_F16X2) go(sep_kernel<NT, 4, 2, 1>);
         else if (a.wparts == UDA_SPLIT_F16X1) go(sep_kernel<NT, 5, 2, 1>);
+        else if (a.wparts == UDA_SPLIT_BF16X1) go(sep_kernel<NT, 6, 2, 1>);
         else go(sep_kernel<NT, 2, 2, 1>);
       } else {
         if (a.wparts == UDA_SPLIT_BF16X3) go(sep_kernel<NT, 3, 2, 2>);
         else if (a.wparts == UDA_SPLIT_F16X2) go(sep_kernel<NT, 4, 2, 2>);
         else if (a.wparts == UDA_SPLIT_F16X1) go(sep_kernel<NT, 5, 2, 2>);
+        else if (a.wparts == UDA_SPLIT_BF16X1) go(sep_kernel<NT, 6, 2, 2>);
         else go(sep_kernel<NT, 2, 2, 2>);
       }
     }
@@ -833,6 +838,7 @@ static void launch_sep_nt(const SepMulti& m, int rows, int gy, hipStream_t s) {
   if (a.wparts == UDA_SPLIT_BF16X3) go(sep_kernel<NT, 3, OCC>);
   else if (a.wparts == UDA_SPLIT_F16X2) go(sep_kernel<NT, 4, OCC>);
   else if (a.wparts == UDA_SPLIT_F16X1) go(sep_kernel<NT, 5, OCC>);
+  else if (a.wparts == UDA_SPLIT_BF16X1) go(sep_kernel<NT, 6, OCC>);
   else go(sep_kernel<NT, 2, OCC>);
 }
 

@@ -43,18 +43,31 @@ __device__ __forceinline__ void store_uniform_base(float* base, unsigned byte_of
   asm volatile("global_store_dword %0, %1, %2" : : "v"(byte_off), "v"(v), "s"(g) : "memory");
 }
 
-// The fp16 counterpart of store_uniform_base (global_store_short v, v, s[..]) for a tensor stored as fp16 in a float32-sized
-// slot: base = the uniform fp16 view of the same element the float base names, byte_off = the float byte offset (halved here).
+// The 16-bit counterpart of store_uniform_base (global_store_short v, v, s[..]) for a tensor stored as fp16 / bf16 in a
+// float32-sized slot: base = the uniform 2-byte view of the same element the float base names, byte_off = the float byte offset
+// (halved here), h = the 16-bit pattern in the low half.
 typedef __attribute__((address_space(1))) unsigned short uda_gu16;
-__device__ __forceinline__ void store_uniform_base_h(unsigned short* base, unsigned byte_off, float v) {
+__device__ __forceinline__ void store_uniform_base_u16(unsigned short* base, unsigned byte_off, unsigned h) {
   uda_gchar* g = (uda_gchar*)(uda_gu16*)base;
-  const unsigned h = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)v);
   asm volatile("global_store_short %0, %1, %2" : : "v"(byte_off >> 1), "v"(h), "s"(g) : "memory");
+}
+// v as fp16 (round to nearest)
+__device__ __forceinline__ void store_uniform_base_h(unsigned short* base, unsigned byte_off, float v) {
+  store_uniform_base_u16(base, byte_off, (unsigned)__builtin_bit_cast(unsigned short, (_Float16)v));
 }
 // four fp16 values (two packed pairs) -> float4
 __device__ __forceinline__ float4 f16x4_to_float4(unsigned lo, unsigned hi) {
   const f16x2 a = __builtin_bit_cast(f16x2, lo), b = __builtin_bit_cast(f16x2, hi);
   return make_float4((float)a[0], (float)a[1], (float)b[0], (float)b[1]);
+}
+// the bf16 counterparts (UDA_SPLIT_BF16X1): the stored pattern is the round-to-nearest-even bf16 of v (v_cvt_pk_bf16_f32), and
+// widening is a 16-bit shift
+__device__ __forceinline__ void store_uniform_base_b(unsigned short* base, unsigned byte_off, float v) {
+  const f32x2 vv = {v, v};
+  store_uniform_base_u16(base, byte_off, __builtin_bit_cast(unsigned, __builtin_convertvector(vv, bf16x2)) & 0xffffu);
+}
+__device__ __forceinline__ float4 bf16x4_to_float4(unsigned lo, unsigned hi) {
+  return make_float4(__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u));
 }
 
 // two floats -> packed bf16 pair (round to nearest even; v_cvt_pk_bf16_f32), element 0 in the low half
@@ -81,7 +94,11 @@ __device__ __forceinline__ float bf16_hi_f32(unsigned p) { return __uint_as_floa
 // two bf16 pieces: 5.9e-6 / 5.1e-6).
 // 5 = ONE fp16 piece / one product (UDA_SPLIT_F16X1, the operands of Keras mixed_float16): no split, a third of the matrix-core
 // work of the two-piece schemes, ~2^-11 per operand; range tracked exactly as for two fp16 pieces.
-__host__ __device__ constexpr int split_np(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : (scheme == UDA_SPLIT_F16X1 ? 1 : 2); }   // pieces per operand
+// 6 = ONE bf16 piece / one product (UDA_SPLIT_BF16X1, the operands of Keras mixed_bfloat16): the cost structure of 5 - the same
+// fragment sizes, launch shapes and LDS layouts - at ~2^-8 per operand and with float32's exponent range: weight scale 1,
+// nothing tracked, nothing to demote (split_track / split_report compile to nothing).
+__host__ __device__ constexpr bool split_one(int scheme) { return scheme == UDA_SPLIT_F16X1 || scheme == UDA_SPLIT_BF16X1; }      // one piece, one product
+__host__ __device__ constexpr int split_np(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : (split_one(scheme) ? 1 : 2); }   // pieces per operand
 __host__ __device__ constexpr bool split_f16(int scheme) { return scheme == UDA_SPLIT_F16X2 || scheme == UDA_SPLIT_F16X1; }
 
 // two floats -> one packed piece pair (round to nearest even), element 0 in the low half
@@ -100,6 +117,18 @@ template <int SCH>
 __device__ __forceinline__ float piece_hi(unsigned p) {
   if constexpr (split_f16(SCH)) return (float)__builtin_bit_cast(f16x2, p)[1];
   else return __uint_as_float(p & 0xffff0000u);
+}
+// The 16-bit expanded tensor of the one-piece schemes (set_f16_storage): fp16 values under UDA_SPLIT_F16X1, bf16 values under
+// UDA_SPLIT_BF16X1.  Four stored values (two packed pairs) -> float4, and the store of one value through a uniform base.
+template <int SCH>
+__device__ __forceinline__ float4 half4_to_float4(unsigned lo, unsigned hi) {
+  if constexpr (split_f16(SCH)) return f16x4_to_float4(lo, hi);
+  else return bf16x4_to_float4(lo, hi);
+}
+template <int SCH>
+__device__ __forceinline__ void store_uniform_base_16(unsigned short* base, unsigned byte_off, float v) {
+  if constexpr (split_f16(SCH)) store_uniform_base_h(base, byte_off, v);
+  else store_uniform_base_b(base, byte_off, v);
 }
 // fragments travel as bf16x8 (16 bytes) whatever the scheme; the matrix instruction reinterprets them
 template <int SCH>
@@ -152,7 +181,7 @@ __device__ __forceinline__ void split_parts(const float4& v0, const float4& v1, 
 // per product, fp16: ~2^-22), three bf16 pieces -> + a2 b0 + a0 b2 + a1 b1 in front (~2^-24)
 template <int SCH>
 __device__ __forceinline__ f32x16 mfma_terms(const bf16x8* a, const bf16x8* b, f32x16 acc) {
-  if constexpr (SCH == UDA_SPLIT_F16X1) return mfma16<SCH>(a[0], b[0], acc);     // one piece: the one product
+  if constexpr (split_one(SCH)) return mfma16<SCH>(a[0], b[0], acc);     // one piece: the one product
   if constexpr (SCH == UDA_SPLIT_BF16X3) {
     acc = mfma16<SCH>(a[2], b[0], acc);
     acc = mfma16<SCH>(a[0], b[2], acc);

@@ -198,8 +198,8 @@ extern "C" int uda_create(const uda_model_t* model, const uda_buf_desc_t* bufs, 
   if (model->decode_method == UDA_DECODE_SAMPLE && (model->decode_nsamples < 1 || model->decode_nsamples > 4096))
     return fail(nullptr, "uda_create: decode_nsamples %d outside [1, 4096]", model->decode_nsamples);
   if (model->pw_scheme != UDA_SPLIT_NONE && model->pw_scheme != UDA_SPLIT_BF16X2 && model->pw_scheme != UDA_SPLIT_BF16X3 &&
-      model->pw_scheme != UDA_SPLIT_F16X2 && model->pw_scheme != UDA_SPLIT_F16X1)
-    return fail(nullptr, "uda_create: pw_scheme %d is not a uda_pw_scheme (0 f32, 2 bf16x2, 3 bf16x3, 4 f16x2, 5 f16)", model->pw_scheme);
+      model->pw_scheme != UDA_SPLIT_F16X2 && model->pw_scheme != UDA_SPLIT_F16X1 && model->pw_scheme != UDA_SPLIT_BF16X1)
+    return fail(nullptr, "uda_create: pw_scheme %d is not a uda_pw_scheme (0 f32, 2 bf16x2, 3 bf16x3, 4 f16x2, 5 f16, 6 bf16)", model->pw_scheme);
   if (model->mc_samples > 96)      // the aggregate kernel parks T logits + 4 T box corners per candidate in LDS
     return fail(nullptr, "uda_create: mc_samples %d > 96 unsupported", model->mc_samples);
   int ndev = 0;
@@ -1555,8 +1555,9 @@ static bool can_replay(const uda_ctx* c, const uda_ctx::RunRec* r) {
   return true;
 }
 
-// One fp16 piece (UDA_SPLIT_F16X1): the expanded tensor between a fused MBConv front half and its projection is stored as
-// fp16 (half the bytes of the largest round trip of the step).  A buffer qualifies when its producer is a fused front half
+// One piece (UDA_SPLIT_F16X1 / UDA_SPLIT_BF16X1): the expanded tensor between a fused MBConv front half and its projection is stored
+// in the scheme's 16-bit format - fp16 (buf_f16 = 1) or bf16 (buf_f16 = 2) - half the bytes of the largest round trip of the
+// step.  A buffer qualifies when its producer is a fused front half
 // running one piece and EVERY reference to it in the op list is the input of a 1x1 conv that runs one piece as well, or the
 // geometry-only second input of its SE op (the gated A-load of pwb_kernel / pws_kernel reads halves); anything else - an unfused fallback, another scheme on either side
 // after a range demotion, a fused-prologue consumer - keeps float32.  Recomputed after every demotion (plan.py mirrors the
@@ -1567,15 +1568,17 @@ static void set_f16_storage(uda_ctx* c) {
   std::vector<int> refs(n_bufs, 0), ok_refs(n_bufs, 0);
   for (int i = 0; i < n_ops; ++i) {
     const uda_op_t& o = c->ops[i];
-    const bool pw1 = o.kind == UDA_OP_PW && c->wsplit_off[i] >= 0 && c->wscheme[i] == UDA_SPLIT_F16X1;
+    const bool pw1 = o.kind == UDA_OP_PW && c->wsplit_off[i] >= 0 && uda_split_one(c->wscheme[i]);
     auto ref = [&](int b, bool ok) { if (b >= 0 && b < n_bufs) { ++refs[b]; if (ok) ++ok_refs[b]; } };
     for (int j = 0; j < UDA_MAX_FUSE_INPUTS; ++j) ref(o.in[j], (j == 0 && pw1) || (j == 1 && o.kind == UDA_OP_SE));   // (SE: geometry only)
     ref(o.se_scale, false); ref(o.se_partial, false); ref(o.residual, false);
   }
   for (int i = 0; i < n_ops; ++i) {
     const uda_op_t& o = c->ops[i];
-    if (o.kind != UDA_OP_MBX || c->wsplit_off[i] < 0 || c->wscheme[i] != UDA_SPLIT_F16X1 || o.out < 0) continue;
-    if (c->bufs[o.out].kind == 0 && refs[o.out] > 0 && refs[o.out] == ok_refs[o.out]) c->buf_f16[o.out] = 1;
+    if (o.kind != UDA_OP_MBX || c->wsplit_off[i] < 0 || !uda_split_one(c->wscheme[i]) || o.out < 0) continue;
+    if (c->bufs[o.out].kind != 0 || refs[o.out] == 0 || refs[o.out] != ok_refs[o.out]) continue;
+    // (producer and readers share the format: a handle runs ONE one-piece scheme, and an fp16 op that was demoted is three-piece)
+    c->buf_f16[o.out] = c->wscheme[i] == UDA_SPLIT_BF16X1 ? 2 : 1;
   }
 }
 
@@ -2208,7 +2211,7 @@ extern "C" int uda_debug_op_scheme(const uda_ctx_t* c, int32_t op, int32_t* sche
   if (scheme) *scheme = packed ? c->wscheme[op] : -1;
   if (a_scale) *a_scale = as;
   if (w_scale) *w_scale = packed ? 1.0f / (c->wunscale[op] * as) : 1.0f;     // (powers of two: exact)
-  if (out_f16) *out_f16 = (c->ops[op].out >= 0 && !c->buf_f16.empty()) ? c->buf_f16[c->ops[op].out] : 0;
+  if (out_f16) *out_f16 = (c->ops[op].out >= 0 && !c->buf_f16.empty()) ? (c->buf_f16[c->ops[op].out] != 0) : 0;     // (16 bits: fp16 or bf16 by the scheme)
   return 0;
 }
 extern "C" int64_t uda_nms_prefix_fallbacks(const uda_ctx_t* c) { return c ? c->pfx_fallbacks : -1; }
@@ -2468,10 +2471,13 @@ extern "C" int uda_read_buffer(uda_ctx_t* c, int32_t buf, float* host, int64_t n
   }
   const int64_t have = (int64_t)v.rows(b) * b.H * b.W * b.C;
   if (n_floats > have) return fail(c, "read_buffer: asked %lld floats, buffer holds %lld", (long long)n_floats, (long long)have);
-  if (c->buf_f16[buf]) {          // an fp16 expanded tensor (set_f16_storage): widened to float32 here
+  if (c->buf_f16[buf]) {          // a 16-bit expanded tensor (set_f16_storage: 1 = fp16, 2 = bf16): widened to float32 here
     std::vector<uint16_t> h((size_t)n_floats);
     HIPC(c, hipMemcpy(h.data(), v.ptr(buf), (size_t)n_floats * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n_floats; ++i) host[i] = (float)__builtin_bit_cast(_Float16, h[(size_t)i]);
+    if (c->buf_f16[buf] == 2)
+      for (int64_t i = 0; i < n_floats; ++i) host[i] = __builtin_bit_cast(float, (uint32_t)h[(size_t)i] << 16);
+    else
+      for (int64_t i = 0; i < n_floats; ++i) host[i] = (float)__builtin_bit_cast(_Float16, h[(size_t)i]);
     return 0;
   }
   HIPC(c, hipMemcpy(host, v.ptr(buf), n_floats * sizeof(float), hipMemcpyDeviceToHost));

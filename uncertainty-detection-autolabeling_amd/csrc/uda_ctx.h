@@ -39,7 +39,7 @@ struct uda_ctx {
   std::vector<float> wunscale;     // per op: 1 / (power-of-two factor folded into the packed weights); 1 unless fp16 pieces
   std::vector<float> wascale;      // per op: factor on the A operand (fp16 separable conv: pre-scaled depthwise taps); part of wunscale
   int n_f16_ops = 0, n_f16_demoted = 0;
-  std::vector<char> buf_f16;       // per buffer: stored as fp16 in its float32-sized slot (set_f16_storage)
+  std::vector<char> buf_f16;       // per buffer: stored in 16 bits in its float32-sized slot (set_f16_storage): 1 = fp16, 2 = bf16
   // fp16 pieces: a kernel that splits an operand above 65504 sets bit 0 of ITS OP's flag word.  Two arrays of n_ops + 1
   // words (index n_ops: launches outside the op list): pipelined run s raises its flags in array s, everything else in array 0.
   unsigned* d_oor = nullptr;

@@ -78,7 +78,8 @@ static inline int uda_env_int(const char* name, int dflt) {
 
 // ---------------------------------------------------------------- split-precision schemes of the 1x1 contractions
 // (`wparts` of the argument blocks below = PARTS of the kernels; see mfma_common.h): enum uda_pw_scheme of uda_hip.h
-inline int uda_split_pieces(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : (scheme == UDA_SPLIT_F16X1 ? 1 : 2); }
+inline bool uda_split_one(int scheme) { return scheme == UDA_SPLIT_F16X1 || scheme == UDA_SPLIT_BF16X1; }   // one piece per operand, one product
+inline int uda_split_pieces(int scheme) { return scheme == UDA_SPLIT_BF16X3 ? 3 : (uda_split_one(scheme) ? 1 : 2); }
 inline bool uda_split_f16(int scheme) { return scheme == UDA_SPLIT_F16X2 || scheme == UDA_SPLIT_F16X1; }   // fp16 pieces: range-tracked
 
 // ---------------------------------------------------------------- kernel argument blocks
@@ -105,7 +106,7 @@ struct StemArgs {
 struct PwArgs {
   const float* in;       // [rows_in, HW, Cin]
   float* out;            // [rows, HW, Cout]
-  int in_f16;            // one fp16 piece only: `in` holds fp16 values (the expanded tensor of a fused MBConv front half)
+  int in_f16;            // one piece only: `in` holds 16-bit values of the scheme's format, fp16 or bf16 (the expanded tensor of a fused MBConv front half)
   const float* w;        // [Cin, Cout]
   const float* bias;     // [Cout] or null
   const float* bn_scale; // [Cout] or null
@@ -199,7 +200,7 @@ struct DwArgs {
 struct MbxArgs {
   const float* in;        // [rows_in, H, W, Cin]
   float* out;             // [rows, Ho, Wo, Cmid]
-  int out_f16;            // one fp16 piece only: `out` is stored as fp16 (round to nearest; the SE tile sums stay float32)
+  int out_f16;            // one piece only: `out` is stored in the scheme's 16-bit format, fp16 or bf16 (round to nearest; the SE tile sums stay float32)
   const float* we;        // expand kernel [Cin, Cmid]
   const float* sc0;       // BN after expand
   const float* sh0;

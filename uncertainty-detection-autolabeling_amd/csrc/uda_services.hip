@@ -1273,8 +1273,8 @@ extern "C" int uda_debug_pw(int32_t device, const float* in, const float* w, con
                             int32_t terms, int32_t reps, float* out, float* avg_ms) {
   if (!in || !w || !out || rows < 1 || in_div < 1 || rows % in_div || hw < 1 || cin < 4 || cin % 4 || cout < 1)
     return fail(nullptr, "uda_debug_pw: bad argument");
-  if (terms != 0 && terms != 1 && terms != 3 && terms != 6 && terms != 16)
-    return fail(nullptr, "uda_debug_pw: terms must be 0 (f32 MFMA), 1 (fp16 x1), 3 (bf16 x2), 6 (bf16 x3) or 16 (fp16 x2)");
+  if (terms != 0 && terms != 1 && terms != 3 && terms != 6 && terms != 8 && terms != 16)
+    return fail(nullptr, "uda_debug_pw: terms must be 0 (f32 MFMA), 1 (fp16 x1), 3 (bf16 x2), 6 (bf16 x3), 8 (bf16 x1) or 16 (fp16 x2)");
   const size_t rows_in = rows / in_div;
   DevScratch s(device);
   PwArgs a{};
@@ -1291,7 +1291,7 @@ extern "C" int uda_debug_pw(int32_t device, const float* in, const float* w, con
   a.HW = hw; a.Cin = cin; a.Cout = cout; a.in_div = in_div; a.res_div = 1; a.se_div = in_div; a.act = act;
   unsigned* d_oor = nullptr;
   if (terms) {
-    const int scheme = terms == 6 ? UDA_SPLIT_BF16X3 : (terms == 16 ? UDA_SPLIT_F16X2 : (terms == 1 ? UDA_SPLIT_F16X1 : UDA_SPLIT_BF16X2));
+    const int scheme = terms == 6 ? UDA_SPLIT_BF16X3 : (terms == 16 ? UDA_SPLIT_F16X2 : (terms == 1 ? UDA_SPLIT_F16X1 : (terms == 8 ? UDA_SPLIT_BF16X1 : UDA_SPLIT_BF16X2)));
     // (as uda_create packs a 1x1 conv: fp16 pieces, one or two, carry the power-of-two weight scale)
     const float scale = uda_split_f16(scheme) ? split_weight_scale(w, (size_t)cin * cout) : 1.0f;
     std::vector<uint16_t> packed(pwb_packed_elems(cin, cout, scheme));

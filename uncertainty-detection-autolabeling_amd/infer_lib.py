@@ -105,7 +105,7 @@ class ServingDriver:
         self.weights = weights
         if chunk_images is None:
             chunk_images = min(self._plan_images, int(self.params.get("uda_chunk_images", 16)))
-        # `uda_pw_scheme` in model_params (f16x2 | bf16x3 | bf16x2 | f32 | f16): the split scheme of THIS handle's 1x1 contractions,
+        # `uda_pw_scheme` in model_params (f16x2 | bf16x3 | bf16x2 | f32 | f16 | bf16): the split scheme of THIS handle's 1x1 contractions,
         # default plan.pw_scheme().  The Plan resolves and validates it (ValueError) and hands it to uda_create in the model struct.
         self._create(weights, chunk_images, post_only, post_mode, device)
         self.pw_scheme = self.plan.pw_scheme
@@ -276,7 +276,7 @@ class ServingDriver:
         return int(self._lib.uda_range_demotions(self._h))
 
     def op_scheme(self, op):
-        """(scheme, weight scale, A-side scale, output stored as fp16) of op `op` of `plan.ops` as it runs now, after any
+        """(scheme, weight scale, A-side scale, output stored in 16 bits: fp16 / bf16 by the scheme) of op `op` of `plan.ops` as it runs now, after any
         range demotion (`uda_debug_op_scheme`; scheme: UDA_SPLIT_* of csrc/uda_internal.h, -1 = no split contraction)."""
         sch, ws, as_, f16 = C.c_int32(), C.c_float(), C.c_float(), C.c_int32()
         self._ck(self._lib.uda_debug_op_scheme(self._h, int(op), C.byref(sch), C.byref(ws), C.byref(as_), C.byref(f16)),

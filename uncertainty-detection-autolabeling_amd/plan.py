@@ -52,8 +52,10 @@ def dw_tiles(C, Ho, Wo, k, stride):
 
 
 PW_SCHEMES = ("f16x2", "bf16x3", "bf16x2", "f32", "f16")
+PW_SCHEMES_ALL = PW_SCHEMES + ("bf16",)      # every name a handle or UDA_PW_SCHEME may carry
 PW_SCHEME_DEFAULT = "f16x2"
-PW_SCHEME_CODES = {"f32": 0, "bf16x2": 2, "bf16x3": 3, "f16x2": 4, "f16": 5}     # enum uda_pw_scheme of include/uda_hip.h
+PW_SCHEME_CODES = {"f32": 0, "bf16x2": 2, "bf16x3": 3, "f16x2": 4, "f16": 5, "bf16": 6}     # enum uda_pw_scheme of include/uda_hip.h
+ONE_PIECE = ("f16", "bf16")                  # one piece per operand, one product (uda_split_one in csrc/uda_internal.h)
 
 # The planner's on/off switches (environment, read once per Plan into Plan.sw) and their defaults; "0" turns a fusion off.  The
 # library reads none of them: an op the planner does not emit / a launch_group it does not set is what turns a fusion off.
@@ -66,12 +68,13 @@ def pw_scheme():
     two variables; the library learns the scheme from uda_model_t.pw_scheme): UDA_PW_SCHEME =
     f16x2 (two fp16 pieces, three cross terms, ~2^-22 per product: the default) | bf16x3 (three bf16 pieces, six terms,
     ~2^-24) | bf16x2 (two bf16 pieces, three terms, ~2^-17) | f32 (exact f32-input MFMA kernels, unfused) | f16 (ONE fp16
-    piece, one product, ~2^-11: the operands of Keras mixed_float16, fp32 accumulation; opt-in, see split_pieces);
+    piece, one product, ~2^-11: the operands of Keras mixed_float16, fp32 accumulation; opt-in, see split_pieces) | bf16 (ONE
+    bf16 piece, one product, ~2^-8: the operands of Keras mixed_bfloat16; f16's cost without its range limit; opt-in);
     the older UDA_PW_TERMS = 6 | 3 | 0 selects the last three when UDA_PW_SCHEME is not set."""
     v = os.environ.get("UDA_PW_SCHEME")
     if v:
-        if v not in PW_SCHEMES:
-            raise ValueError("UDA_PW_SCHEME=%r: expected one of %s" % (v, ", ".join(PW_SCHEMES)))
+        if v not in PW_SCHEMES_ALL:
+            raise ValueError("UDA_PW_SCHEME=%r: expected one of %s" % (v, ", ".join(PW_SCHEMES_ALL)))
         return v
     t = os.environ.get("UDA_PW_TERMS")
     if t is None or t == "":
@@ -84,7 +87,7 @@ def pw_scheme():
 
 def split_pieces(sch):
     """Pieces per operand of a split scheme (mirror of uda_split_pieces in csrc/uda_internal.h)."""
-    return {"bf16x3": 3, "f16": 1}.get(sch, 2)
+    return {"bf16x3": 3, "f16": 1, "bf16": 1}.get(sch, 2)
 
 
 # The predicates below are pure functions of shape and split scheme `sch` ("a kernel exists for this shape"), mirrors of the
@@ -144,7 +147,7 @@ def sep_tin_supported(C, Cout, sch):
         return False
     a_img = 128 * (ks * 64 + 16) if sch == "bf16x3" else npc * 128 * (ks * 32 + 16)
     stg = 4 * 32 * ntl * 32 * 4 if Cout % 4 else 4 * 32 * 68 * 4
-    if sch == "f16":
+    if sch in ONE_PIECE:
         a_img = max(a_img, stg)         # (sep_a_region: one piece widens the A region to hold the staging)
     return stg <= a_img and a_img + ks * ntl * npc * 1024 <= 120 * 1024
 
@@ -278,8 +281,8 @@ class _Buf:
         self.H, self.W, self.C, self.per_sample = int(H), int(W), int(C), bool(per_sample)
         self.kind, self.level, self.offset = kind, level, 0
         self.first, self.last, self.name = None, None, name
-        # element type on the device: "f32", or "f16" for the expanded tensor of a fused MBConv front half under the one-piece
-        # scheme (mark_f16_storage).  The arena slot stays float32-sized either way.
+        # element type on the device: "f32", or "f16" / "bf16" for the expanded tensor of a fused MBConv front half under the
+        # one-piece scheme of that name (mark_f16_storage).  The arena slot stays float32-sized either way.
         self.storage = "f32"
 
 
@@ -305,8 +308,8 @@ class Plan:
         self.site_index = {}
         self.buffer_names = {}
         self.pw_scheme = self.cfg.get("uda_pw_scheme") or pw_scheme()      # this handle's split scheme: its params, else the default
-        if self.pw_scheme not in PW_SCHEMES:
-            raise ValueError("uda_pw_scheme=%r: expected one of %s" % (self.pw_scheme, ", ".join(PW_SCHEMES)))
+        if self.pw_scheme not in PW_SCHEMES_ALL:
+            raise ValueError("uda_pw_scheme=%r: expected one of %s" % (self.pw_scheme, ", ".join(PW_SCHEMES_ALL)))
         sw = self.sw = {k: int(os.environ.get(k, d)) for k, d in PLAN_SWITCHES.items()}
         split = self.pw_scheme != "f32"
         self.defer_dropout = bool(sw["UDA_DEFER_DROPOUT"])
@@ -898,12 +901,12 @@ class Plan:
         return m, bufs, ops, sites, blob, self.anchors()
 
     def mark_f16_storage(self):
-        """Under the one-piece scheme (self.pw_scheme == "f16") the output of a fused MBConv front half is stored as fp16 when every
+        """Under a one-piece scheme ("f16" / "bf16") the output of a fused MBConv front half is stored in 16 bits of that format when every
         reference to it is the input of a 1x1 conv (its projection) or the geometry-only input of its SE op - mirror of set_f16_storage in csrc/uda_api.hip, which also
         keeps float32 where uda_create or a range demotion gives either side another scheme."""
         for b in self.bufs:
             b.storage = "f32"
-        if self.pw_scheme != "f16":
+        if self.pw_scheme not in ONE_PIECE:
             return
         refs, ok = [0] * len(self.bufs), [0] * len(self.bufs)
         for o in self.ops:
@@ -917,7 +920,7 @@ class Plan:
         for o in self.ops:
             b = o["out"]
             if o["kind"] == capi.OP_MBX and self.bufs[b].kind == 0 and refs[b] > 0 and refs[b] == ok[b]:
-                self.bufs[b].storage = "f16"
+                self.bufs[b].storage = self.pw_scheme
 
     def summary(self):
         return dict(n_ops=len(self.ops), n_bufs=len(self.bufs), arena_mb=self.arena_floats * 4 / 2 ** 20,
