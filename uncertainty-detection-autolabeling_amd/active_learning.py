@@ -311,27 +311,18 @@ def _column(a, shape, what, dtype, finite=True):
     return a
 
 
-def score_detections(columns, strategy, min_score, params=None, opt_params=None, num_classes=None, device=0, as_float32=False):
-    """`score_image`'s per-image part on host arrays, through the same kernel in float64 (uda_score_images_np): for the
-    calibrated strategies - the columns `BoxCalibrator` / `ClassCalibrator` return already are on the host - and for callers
-    that hold detections of their own (a gathered multi-GPU batch).
-
-    columns: dict with boxes [n, M, 4], scores [n, M], classes [n, M] and the uncertainty columns the strategy names
-    (`Strategy.columns`: "entropy" [n, M], "albox" / "mcbox" [n, M, 4], "mcclass" [n, M, C'] - the keys of
-    `ServingDriver.serve_unpacked` - or "iso_percls_entropy", "iso_perclscoo_albox", ... under a `calib` strategy).
-    strategy: a string (resolved against params, or against the columns present when params is None) or a `Strategy`.
-    Values must be finite (ValueError).  as_float32=True runs the float32 instantiation the handle runs
-    (uda_score_images_np_f32) on the columns cast to float32: the raw device columns, whose albox / mcbox / mcclass may then
-    hold NaN / inf - the kernel applies np.nan_to_num to them, as the reference's caller does (infer_model.py:607-631).
-    Returns (components [n, n_comp] float64, count [n], class_counts [n, num_classes])."""
+def detection_columns(columns, strategy, resolver, params, opt_params, num_classes, as_float32):
+    """What `score_detections` and `pseudo_labels.select_detections` do before they call the library: the strategy resolved by
+    `resolver` (a string: against params, or against the columns present when params is None), every column it reads checked
+    and cast.  -> (strategy, the seven arrays boxes, scores, classes, entropy, albox, mcbox, mcclass - None where the strategy
+    reads none -, n, M, mcclass columns, num_classes)."""
     dt = np.float32 if as_float32 else np.float64
     cols = {k: v for k, v in columns.items() if v is not None}
     if not isinstance(strategy, Strategy):
         if params is None:
             present = {src for src in ("entropy", "albox", "mcbox", "mcclass") if any(k == src or k.endswith("_" + src) for k in cols)}
-            strategy = resolve_strategy(strategy, dict.fromkeys(present), opt_params)
-        else:
-            strategy = resolve_strategy(strategy, params, opt_params)
+            params = dict.fromkeys(present)
+        strategy = resolver(strategy, params, opt_params)
     scores = np.asarray(cols["scores"])
     if scores.ndim != 2:
         raise ValueError("scores must be [n, M], got %s" % (scores.shape,))
@@ -358,16 +349,38 @@ def score_detections(columns, strategy, min_score, params=None, opt_params=None,
             arrays[src] = _column(a, (n, M, mcw), key, dt, finite)
         else:
             arrays[src] = _column(a, (n, M) if src == "entropy" else (n, M, 4), key, dt, finite)
+    return strategy, [boxes, scores, classes] + list(arrays.values()), n, M, int(mcw), int(num_classes)
+
+
+def raise_from_rc(rc, lib, what):
+    """A handle-free entry point returned rc: a class id the caller's num_classes does not cover is a ValueError."""
+    if rc != 0:
+        msg = lib.uda_last_error(None).decode()
+        raise (ValueError if "class id outside" in msg else capi.UdaError)("%s failed: %s" % (what, msg))
+
+
+def score_detections(columns, strategy, min_score, params=None, opt_params=None, num_classes=None, device=0, as_float32=False):
+    """`score_image`'s per-image part on host arrays, through the same kernel in float64 (uda_score_images_np): for the
+    calibrated strategies - the columns `BoxCalibrator` / `ClassCalibrator` return already are on the host - and for callers
+    that hold detections of their own (a gathered multi-GPU batch).
+
+    columns: dict with boxes [n, M, 4], scores [n, M], classes [n, M] and the uncertainty columns the strategy names
+    (`Strategy.columns`: "entropy" [n, M], "albox" / "mcbox" [n, M, 4], "mcclass" [n, M, C'] - the keys of
+    `ServingDriver.serve_unpacked` - or "iso_percls_entropy", "iso_perclscoo_albox", ... under a `calib` strategy).
+    strategy: a string (resolved against params, or against the columns present when params is None) or a `Strategy`.
+    Values must be finite (ValueError).  as_float32=True runs the float32 instantiation the handle runs
+    (uda_score_images_np_f32) on the columns cast to float32: the raw device columns, whose albox / mcbox / mcclass may then
+    hold NaN / inf - the kernel applies np.nan_to_num to them, as the reference's caller does (infer_model.py:607-631).
+    Returns (components [n, n_comp] float64, count [n], class_counts [n, num_classes])."""
+    strategy, arrays, n, M, mcw, num_classes = detection_columns(columns, strategy, resolve_strategy, params, opt_params, num_classes,
+                                                                 as_float32)
     comp = np.zeros((n, strategy.n_comp), np.float64)
     count = np.zeros((n,), np.int32)
-    cls = np.zeros((n, int(num_classes)), np.int32)
+    cls = np.zeros((n, num_classes), np.int32)
     lib = capi.load()
     p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
     desc = strategy.desc()
     fn, what = (lib.uda_score_images_np_f32, "uda_score_images_np_f32") if as_float32 else (lib.uda_score_images_np, "uda_score_images_np")
-    rc = fn(int(device), C.byref(desc), float(min_score), p(boxes), p(scores), p(classes), p(arrays["entropy"]), p(arrays["albox"]),
-            p(arrays["mcbox"]), p(arrays["mcclass"]), n, M, int(num_classes), int(mcw), p(comp), p(count), p(cls))
-    if rc != 0:
-        msg = lib.uda_last_error(None).decode()
-        raise (ValueError if "class id outside" in msg else capi.UdaError)("%s failed: %s" % (what, msg))
+    raise_from_rc(fn(int(device), C.byref(desc), float(min_score), *[p(a) for a in arrays], n, M, num_classes, mcw, p(comp), p(count),
+                     p(cls)), lib, what)
     return comp, count, cls

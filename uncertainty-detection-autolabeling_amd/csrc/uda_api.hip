@@ -84,12 +84,7 @@ extern "C" void uda_destroy(uda_ctx_t* c) {
                   c->d_site_off, c->d_site_ch, c->d_site_rate, c->d_cboxes, c->d_cscores, c->d_clogits,
                   c->d_cclasses, c->d_ucls, c->d_ual, c->d_uep, c->d_clsmean, c->d_cand_flat, c->d_merge_keys,
                   c->d_oboxes, c->d_oscores, c->d_oclasses, c->d_ologits, c->d_ovalid, c->d_oprobs, c->d_oentropy,
-                  c->d_opacked, c->d_cons_iou, c->d_cons_agree, c->d_gt_boxes, c->d_gt_classes, c->d_asg_pack,
-                  c->d_asg_rows, c->d_score_pack, c->d_egt, c->d_eval_pack, c->d_pseudo_pack, c->d_pseudo_slots, c->d_lc_pack};
-  if (c->h_gt) hipHostFree(c->h_gt);
-  if (c->gt_ev) hipEventDestroy(c->gt_ev);
-  if (c->h_egt) hipHostFree(c->h_egt);
-  if (c->egt_ev) hipEventDestroy(c->egt_ev);
+                  c->d_opacked, c->d_cons_iou, c->d_cons_agree};      // (the services' slots and stagings free themselves)
   for (void* p : ptrs)
     if (p) hipFree(p);
   free_prefix_ws(c->pfx);

@@ -1,6 +1,7 @@
 // Host-only: the handle behind the C ABI (include/uda_hip.h) and what uda_api.hip (create / destroy, inputs, the executor, the
 // post-process, pipelined runs, readers of detections) shares with uda_services.hip (the services that read the resident detections
-// and the entry points that work on host arrays).  No kernels.
+// and the entry points that work on host arrays): the handle itself, the two owners of what a service keeps in it (ResultSlot,
+// GtStaging), the error and profiling helpers.  No kernels.
 #pragma once
 #include <stdint.h>
 
@@ -17,6 +18,50 @@ struct ProfSlot {
   int64_t launches = 0;       // in units of PLANNED ops: a launch that covers a group of n ops counts n (plan.op_costs counts per op)
   struct Pending { hipEvent_t first, second; int weight; };
   std::vector<Pending> pending;
+};
+
+// What a service leaves on the device until somebody reads it: ONE buffer, packed so that one copy brings the result to the host,
+// and the host copy the first reader makes (fetch_result, uda_services.hip).  Owns its device memory.
+struct ResultSlot {
+  char* d = nullptr;           // the pack
+  void* aux = nullptr;         // a second device buffer that is sized, grown and freed with the pack
+  int cap = 0;                 // rows per image the pack holds, where it grows with the ground truth
+  std::vector<char> h;         // host copy of what the readers need of the pack
+  bool fetched = false;        // `h` holds the result of the last queued run
+  ResultSlot() = default;
+  ResultSlot(const ResultSlot&) = delete;
+  ResultSlot& operator=(const ResultSlot&) = delete;
+  ~ResultSlot() { release(); }
+  void release() {
+    if (d) hipFree(d);
+    if (aux) hipFree(aux);
+    d = nullptr; aux = nullptr; cap = 0; fetched = false;
+  }
+};
+
+// Per-image ground-truth rows on their way to the device: up to two device arrays of width[k] floats per row and ONE pinned staging
+// buffer the rows are copied through, so that the upload is asynchronous.  Owns its memory and its event.
+struct GtStaging {
+  const int width[2];
+  float* d[2] = {nullptr, nullptr};  // [max_images, cap, width[k]]
+  float* h = nullptr;                // pinned, the arrays back to back
+  hipEvent_t ev = nullptr;           // the upload out of `h` has been consumed
+  int cap = 0, n = 0, G = 0;         // rows per image the buffers hold; images / rows per image of what is set (n 0: nothing)
+  GtStaging(int w0, int w1) : width{w0, w1} {}
+  GtStaging(const GtStaging&) = delete;
+  GtStaging& operator=(const GtStaging&) = delete;
+  ~GtStaging() {
+    release();
+    if (ev) hipEventDestroy(ev);
+  }
+  void release() {
+    for (float*& p : d) {
+      if (p) hipFree(p);
+      p = nullptr;
+    }
+    if (h) hipHostFree(h);
+    h = nullptr; cap = 0; n = 0;
+  }
 };
 
 struct uda_ctx {
@@ -180,48 +225,24 @@ struct uda_ctx {
   float *d_oprobs = nullptr, *d_oentropy = nullptr;   // stable softmax / entropy of the selected rows (lazy)
   float* d_opacked = nullptr;                        // packed detection records for the multi-GPU gather (lazy, uda_detections_device)
   int32_t* d_ovalid = nullptr;
-  // ground-truth assignment (uda_set_ground_truth / uda_assign_ground_truth): buffers for max_images x gt_cap GT rows, grown when a
-  // call brings more rows per image; nothing is allocated per call in the steady state
-  float *d_gt_boxes = nullptr, *d_gt_classes = nullptr, *h_gt = nullptr;   // h_gt: pinned staging [max_images, gt_cap, 5]
-  hipEvent_t gt_ev = nullptr;        // the upload out of h_gt has been consumed
-  // results of an assignment of n images x G rows, packed so that ONE copy brings them to the host:
-  // iou [n G] float64 | det_index [n G] int32 | count [n] int32 | error flag int32 (AssignPack, uda_services.hip)
-  char* d_asg_pack = nullptr;
-  std::vector<char> h_asg;           // host copy of the pack (filled by the first reader of an assignment)
-  float* d_asg_rows = nullptr;       // [max_images * gt_cap, assigned_row_cols]
-  int gt_cap = 0, gt_n = 0, gt_G = 0; // rows per image the buffers hold; images / rows per image of the GT that is set (0: none)
+  // per-image ground truth, set before the service that reads it (stage_ground_truth, uda_services.hip): the buffers hold
+  // max_images x cap rows and grow when a call brings more rows per image; nothing is allocated per call in the steady state
+  GtStaging gt{4, 1};                // uda_set_ground_truth: boxes [n, G, 4] | classes [n, G] (assignment, label check)
+  GtStaging egt{7, 0};               // uda_set_eval_ground_truth: rows [n, G, 7] (COCO matching)
+  // the services' results (the *Pack structs of uda_services.hip name the layouts).  asg holds max_images x gt.cap rows and grows
+  // with `gt`, lc max_images x lc.cap rows and grows when a check brings more; the others are sized once for max_images
+  ResultSlot asg;                    // uda_assign_ground_truth (AssignPack); aux: the matched rows [max_images * cap, assigned_row_cols]
   int asg_n = 0, asg_G = 0;          // images / rows per image of the last assignment (0: none)
-  int64_t asg_rows = -1;             // sum(count) of the last assignment once the host has seen it
-  // active-learning image scores (uda_score_images), packed for max_images so that ONE copy brings them to the host:
-  // components [n, n_comp] float64 | count [n] int32 | class_counts [n, num_classes] int32 | error flag int32 (ScorePack)
-  char* d_score_pack = nullptr;
-  std::vector<char> h_score;         // host copy of the pack (filled by the first reader of a scoring)
+  int64_t asg_rows = 0;              // sum(count) of the last assignment, as its first reader found it
+  ResultSlot score;                  // uda_score_images (ScorePack)
   int score_n = 0, score_nc = 0;     // images / components of the last scoring (0: none)
-  bool score_fetched = false;
-  // pseudo-labelling rows (uda_pseudo_rows), sized for max_images x max_output_size records: a head of minmax [n, 2] float64 |
-  // kept [n] | cand [n] | error flag, then records [n, cap] x 40 bytes of which the first sum(cand) are used (PseudoPack); the
-  // host copies the head, then the used records
-  char* d_pseudo_pack = nullptr;
-  char* d_pseudo_slots = nullptr;    // [max_images, max_output_size] records: per-image staging of the packing kernel
-  std::vector<char> h_pseudo;        // host copy of the pack's head (filled by the first reader of a run)
+  ResultSlot pseudo;                 // uda_pseudo_rows (PseudoPack; the host copies the head, then the used records); aux: the
+                                     // packing kernel's staging, [max_images, max_output_size] records
   int pseudo_n = 0, pseudo_cap = 0;  // images / record slots per image of the last uda_pseudo_rows (0: none)
-  bool pseudo_fetched = false;
-  // label correction (uda_label_check): the verdicts for n images x G rows and M detections, packed so that ONE copy brings them
-  // to the host (LabelPack, uda_services.hip); the buffer holds max_images x lc_cap rows and grows when a check brings more
-  char* d_lc_pack = nullptr;
-  std::vector<char> h_lc;            // host copy of the pack (filled by the first reader of a check)
-  int lc_cap = 0, lc_n = 0, lc_G = 0; // rows per image the buffer holds; images / rows per image of the last check (0: none)
-  bool lc_fetched = false;
-  // COCO matching (uda_set_eval_ground_truth / uda_eval_match): ground truth [max_images, egt_cap, 7], grown when a call brings
-  // more rows per image; results packed for max_images so that ONE copy brings them to the host:
-  // records [n, M] x 44 bytes | npig [n, num_classes, 4] int32 | used [n] int32 (EvalPack)
-  float *d_egt = nullptr, *h_egt = nullptr;   // h_egt: pinned staging
-  hipEvent_t egt_ev = nullptr;       // the upload out of h_egt has been consumed
-  char* d_eval_pack = nullptr;
-  std::vector<char> h_eval;          // host copy of the pack (filled by the first reader of a match)
-  int egt_cap = 0, egt_n = 0, egt_G = 0;   // rows per image the buffer holds; images / rows per image of the GT that is set (0: none)
+  ResultSlot lc;                     // uda_label_check (LabelPack)
+  int lc_n = 0, lc_G = 0;            // images / rows per image of the last check (0: none)
+  ResultSlot eval;                   // uda_eval_match (EvalPack)
   int eval_n = 0;                    // images of the last match (0: none)
-  bool eval_fetched = false;
   int last_post_mode = 0;
   int last_n = 0;
   int last_chunk_i0 = 0, last_chunk_n = 0;

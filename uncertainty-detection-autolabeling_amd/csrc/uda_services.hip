@@ -3,6 +3,11 @@
 // on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, the pseudo-label audit, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
+//
+// What the services share is stated once, ahead of them: the checks of the resident run (resident_ready, gt_covers_run), the
+// pinned staging of per-image ground truth (stage_ground_truth), the result packs with their first-reader fetch (fetch_result
+// over a ResultSlot of uda_ctx.h), the sources of a score descriptor (score_sources_missing, resident_score_sources,
+// upload_score_sources) and the tail of the entry points that own a DevScratch (scratch_done, fetch_pack).
 #include <stdio.h>
 #include <string.h>
 
@@ -29,6 +34,66 @@ static int settle_detections(uda_ctx* c) {
   HIPC(c, hipSetDevice(c->device));
   return finish_post(c);
 }
+// after a consistency run the handle holds 4n images, the n originals first
+static bool holds_consistency_run(const uda_ctx* c) { return c->noise_from >= 0 && c->cons_n > 0 && c->last_n == 4 * c->cons_n; }
+// The ground truth that is set covers the images the service reads: with `originals` those of a consistency run, to which the
+// ground truth belongs, else every image of the last run.
+static int gt_covers_run(uda_ctx* c, const char* who, int gt_n, bool originals) {
+  const int held = originals && holds_consistency_run(c) ? c->cons_n : c->last_n;
+  if (gt_n != held) return fail(c, "%s: ground truth of %d images, the last post-process holds %d", who, gt_n, held);
+  return 0;
+}
+
+// Ground truth of n images x G rows into `st`: through its pinned buffer, so that the upload is queued on the handle's stream
+// (a service queued behind a run finds it there) and the caller's arrays are free at once.  src[k]: [n, G, st.width[k]].
+// Allocates only when G exceeds what the buffers hold, after a stream sync; *grew tells a caller whose buffers follow st.cap.
+static int stage_ground_truth(uda_ctx* c, GtStaging& st, const float* const* src, int n, int G, bool* grew = nullptr) {
+  HIPC(c, hipSetDevice(c->device));
+  if (!st.ev) HIPC(c, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+  else HIPC(c, hipEventSynchronize(st.ev));              // the previous upload has left the staging buffer
+  const bool grow = G > st.cap || !st.d[0];
+  if (grew) *grew = grow;
+  if (grow) {
+    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffers)
+    st.release();
+    const size_t rows = (size_t)c->model.max_images * std::max(G, 1);
+    for (int k = 0; k < 2; ++k)
+      if (st.width[k]) HIPC(c, dalloc(&st.d[k], rows * st.width[k]));
+    HIPC(c, hipHostMalloc((void**)&st.h, rows * (st.width[0] + st.width[1]) * sizeof(float)));
+    st.cap = std::max(G, 1);
+  }
+  float* h = st.h;
+  for (int k = 0; k < 2; ++k)
+    if (const size_t floats = (size_t)n * G * st.width[k]) {
+      memcpy(h, src[k], floats * sizeof(float));
+      HIPC(c, hipMemcpyAsync(st.d[k], h, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      h += floats;
+    }
+  HIPC(c, hipEventRecord(st.ev, c->stream));
+  st.n = n; st.G = G;
+  return 0;
+}
+
+// The first reader of a result waits for it and brings `bytes` of the pack to the host in one copy; later readers find s.h.
+static int fetch_result(uda_ctx* c, ResultSlot& s, size_t bytes) {
+  if (s.fetched) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  s.h.resize(bytes);
+  HIPC(c, hipMemcpy(s.h.data(), s.d, bytes, hipMemcpyDeviceToHost));
+  s.fetched = true;
+  return 0;
+}
+
+// ---- the tail of an entry point that owns a DevScratch
+static int scratch_done(uda_ctx* c, const char* who, const DevScratch& s) { return s.ok() ? 0 : hip_failed(c, who, s.err); }
+// the handle-free twins: the launches' error, the end of the work, then `bytes` of the device pack as the host copy `h`
+static int fetch_pack(const char* who, DevScratch& s, const void* d_pack, size_t bytes, std::vector<char>& h) {
+  s.sync();
+  h.resize(bytes);
+  s.download(h.data(), d_pack, bytes);
+  return scratch_done(nullptr, who, s);
+}
 
 // ---- result packs: one device buffer per service, so that ONE copy brings a result to the host.  Built over the device buffer
 // where the kernel arguments are filled and over the host copy where the results are handed out.
@@ -41,6 +106,10 @@ struct AssignPack {      // iou [n G] float64 | det_index [n G] int32 | count [n
   int32_t* det_index() const { return (int32_t*)(base + n * G * sizeof(double)); }
   int32_t* count() const { return det_index() + n * G; }
   int32_t* err() const { return count() + n; }
+  void fill(AssignArgs& a, int M, int method, int keep) const {       // where the kernel writes, and the problem's scalars
+    a.det_index = det_index(); a.iou = iou(); a.count = count(); a.err = err();
+    a.n = (int)n; a.M = M; a.G = (int)G; a.method = method; a.keep = keep;
+  }
   int copy_out(uda_ctx* c, const char* who, int M, int32_t* det_index_out, double* iou_out, int32_t* count_out) const {
     if (*err())
       return fail(c, M > 0 ? "%s: the rank method met a kept ground-truth row beyond the %d detections"
@@ -126,10 +195,14 @@ struct LabelPack {       // iou [n G] float64 | det_max_iou [n M] float64 | det_
   size_t copy_bytes() const { return (size_t)(det_flags() + n * M - (uint8_t*)base); }
   int32_t* first_row() const { return (int32_t*)(base + ((copy_bytes() + 3) & ~(size_t)3)); }
   size_t bytes() const { return ((copy_bytes() + 3) & ~(size_t)3) + n * M * sizeof(int32_t); }
-  template <typename T>
-  void fill(LabelCheckArgs<T>& a) const {
+  template <typename T>      // where the kernel writes, and the problem's scalars
+  void fill(LabelCheckArgs<T>& a, int methods, int md_rule, T min_score, T correct_score, double iou_consist, double md_max_inter,
+            double correct_max_inter) const {
     a.iou = iou(); a.det_max_iou = det_max(); a.det_rank = det_rank(); a.counts = counts(); a.gt_boxes_out = gt_boxes();
     a.gt_flags = gt_flags(); a.det_flags = det_flags(); a.first_row = first_row();
+    a.n = (int)n; a.M = (int)M; a.G = (int)G; a.methods = methods; a.md_rule = md_rule;
+    a.min_score = min_score; a.correct_score = correct_score;
+    a.iou_consist = iou_consist; a.md_max_inter = md_max_inter; a.correct_max_inter = correct_max_inter;
   }
   void copy_out(int32_t* det_rank_out, double* iou_out, uint8_t* gt_flags_out, float* gt_boxes_out, uint8_t* det_flags_out,
                 double* det_max_out, int32_t* counts_out) const {
@@ -140,6 +213,24 @@ struct LabelPack {       // iou [n G] float64 | det_max_iou [n M] float64 | det_
     if (det_flags_out && n * M) memcpy(det_flags_out, det_flags(), n * M);
     if (det_max_out && n * M) memcpy(det_max_out, det_max(), n * M * sizeof(double));
     if (counts_out) memcpy(counts_out, counts(), n * 5 * sizeof(int32_t));
+  }
+};
+
+struct AuditPack {       // float64 gt_max_iou [NG] | det_max_iou [ND] | det_alloc_miou [ND] | det_alloc_pair_iou [ND]; int32 gt_best_det
+  char* base;            // [NG] | gt_alloc_det [NG] | det_best_gt [ND] | det_alloc_gt [ND] | n_matches [B]; uint8 gt_flags [NG] |
+  size_t NG, ND, B;      // det_flags [ND].  Read where it lies: every array the caller asked for is copied straight out of it
+  AuditPack(void* b, size_t NG_, size_t ND_, size_t B_) : base((char*)b), NG(NG_), ND(ND_), B(B_) {}
+  size_t n64() const { return NG + 3 * ND; }
+  size_t n32() const { return 2 * NG + 2 * ND + B; }
+  size_t bytes() const { return n64() * sizeof(double) + n32() * sizeof(int32_t) + NG + ND; }
+  void fill(AuditArgs& a) const {
+    double* f = (double*)base;
+    int32_t* i = (int32_t*)(f + n64());
+    uint8_t* u = (uint8_t*)(i + n32());
+    a.gt_max_iou = f; a.det_max_iou = f + NG; a.det_alloc_miou = f + NG + ND; a.det_alloc_pair_iou = f + NG + 2 * ND;
+    a.gt_best_det = i; a.gt_alloc_det = i + NG; a.det_best_gt = i + 2 * NG; a.det_alloc_gt = i + 2 * NG + ND;
+    a.n_matches = i + 2 * NG + 2 * ND;
+    a.gt_flags = u; a.det_flags = u + NG;
   }
 };
 
@@ -163,34 +254,22 @@ extern "C" int uda_set_ground_truth(uda_ctx_t* c, const float* boxes, const floa
   const uda_model_t& m = c->model;
   if (n < 1 || n > m.max_images) return fail(c, "set_ground_truth: %d images, the handle holds 1..%d", n, m.max_images);
   if (G < 0 || G > kAssignMaxG) return fail(c, "set_ground_truth: %d ground-truth rows per image, at most %d", G, kAssignMaxG);
-  HIPC(c, hipSetDevice(c->device));
-  if (!c->gt_ev) HIPC(c, hipEventCreateWithFlags(&c->gt_ev, hipEventDisableTiming));
-  else HIPC(c, hipEventSynchronize(c->gt_ev));          // the previous upload has left the staging buffer
-  if (G > c->gt_cap || !c->d_gt_boxes) {
-    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffers)
-    void* old[] = {c->d_gt_boxes, c->d_gt_classes, c->d_asg_pack, c->d_asg_rows};
-    for (void* p : old)
-      if (p) hipFree(p);
-    if (c->h_gt) hipHostFree(c->h_gt);
-    c->d_gt_boxes = c->d_gt_classes = c->d_asg_rows = c->h_gt = nullptr; c->d_asg_pack = nullptr;
-    c->gt_cap = 0; c->asg_n = 0; c->asg_rows = -1;
-    const size_t cap = (size_t)std::max(G, 1), rows = (size_t)m.max_images * cap;
-    HIPC(c, dalloc(&c->d_gt_boxes, rows * 4));
-    HIPC(c, dalloc(&c->d_gt_classes, rows));
-    HIPC(c, dalloc(&c->d_asg_pack, AssignPack(nullptr, (size_t)m.max_images, cap).bytes()));
-    HIPC(c, dalloc(&c->d_asg_rows, rows * (size_t)assigned_row_cols_of(m)));
-    HIPC(c, hipHostMalloc((void**)&c->h_gt, rows * 5 * sizeof(float)));
-    c->gt_cap = (int)cap;
+  const float* src[] = {boxes, classes};
+  bool grew = false;
+  if (int rc = stage_ground_truth(c, c->gt, src, n, G, &grew)) return rc;
+  if (grew) {              // the assignment's pack and row table hold gt.cap rows per image as well: the last assignment is gone
+    c->asg.release();
+    c->asg_n = 0;
+    const size_t cap = (size_t)c->gt.cap;
+    float* rows = nullptr;
+    hipError_t e = dalloc(&c->asg.d, AssignPack(nullptr, (size_t)m.max_images, cap).bytes());
+    if (e == hipSuccess) e = dalloc(&rows, (size_t)m.max_images * cap * (size_t)assigned_row_cols_of(m));
+    c->asg.aux = rows;
+    if (e != hipSuccess) {
+      c->gt.n = 0;         // (nothing may be assigned into a pack that is not there)
+      return hip_failed(c, "set_ground_truth", e);
+    }
   }
-  const size_t rows = (size_t)n * G;
-  if (rows) {
-    memcpy(c->h_gt, boxes, rows * 4 * sizeof(float));
-    memcpy(c->h_gt + rows * 4, classes, rows * sizeof(float));
-    HIPC(c, hipMemcpyAsync(c->d_gt_boxes, c->h_gt, rows * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(c->d_gt_classes, c->h_gt + rows * 4, rows * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPC(c, hipEventRecord(c->gt_ev, c->stream));
-  c->gt_n = n; c->gt_G = G;
   return 0;
 }
 
@@ -199,46 +278,38 @@ extern "C" int uda_assign_ground_truth(uda_ctx_t* c, int32_t method, int32_t kee
   const uda_model_t& m = c->model;
   if (method < ASSIGN_IOU || method > ASSIGN_RANK) return fail(c, "assign_ground_truth: unknown method %d", method);
   if (keep != ASSIGN_KEEP_VALIDATE && keep != ASSIGN_KEEP_CALIBRATE) return fail(c, "assign_ground_truth: unknown keep rule %d", keep);
-  if (c->gt_n < 1) return fail(c, "assign_ground_truth: no ground truth is set (uda_set_ground_truth)");
+  if (c->gt.n < 1) return fail(c, "assign_ground_truth: no ground truth is set (uda_set_ground_truth)");
   if (int rc = resident_ready(c, "assign_ground_truth", "the assignment reads")) return rc;
-  // after a consistency run the handle holds 4n images, the n originals first: the ground truth belongs to those
-  const bool cons = c->noise_from >= 0 && c->cons_n > 0 && c->last_n == 4 * c->cons_n;
-  if (c->gt_n != (cons ? c->cons_n : c->last_n))
-    return fail(c, "assign_ground_truth: ground truth of %d images, the last post-process holds %d", c->gt_n, cons ? c->cons_n : c->last_n);
+  if (int rc = gt_covers_run(c, "assign_ground_truth", c->gt.n, true)) return rc;
   if (m.max_output_size > kAssignMaxM) return fail(c, "assign_ground_truth: max_output_size %d above %d", m.max_output_size, kAssignMaxM);
   if (int rc = settle_detections(c)) return rc;
-  const int n = c->gt_n, M = m.max_output_size, G = c->gt_G, C = m.enable_softmax ? m.num_classes : 0;
+  const int n = c->gt.n, M = m.max_output_size, G = c->gt.G, C = m.enable_softmax ? m.num_classes : 0;
   if (C)
     if (int rc = ensure_probs(c, n * M)) return rc;
-  const AssignPack pack(c->d_asg_pack, (size_t)n, (size_t)G);
+  const AssignPack pack(c->asg.d, (size_t)n, (size_t)G);
   HIPC(c, hipMemsetAsync(pack.err(), 0, sizeof(int32_t), c->stream));
   AssignArgs a{};
   a.det_boxes = c->d_oboxes; a.det_stride = box_cols_of(m, UDA_POST_GLOBAL);
-  a.gt_boxes = c->d_gt_boxes; a.gt_classes = c->d_gt_classes;
-  a.det_index = pack.det_index(); a.iou = pack.iou(); a.count = pack.count(); a.err = pack.err();
-  a.n = n; a.M = M; a.G = G; a.method = method; a.keep = keep;
+  a.gt_boxes = c->gt.d[0]; a.gt_classes = c->gt.d[1];
+  pack.fill(a, M, method, keep);
   launch_assign_gt(a, c->stream);
   AssignRowsArgs r{};
   r.det_index = pack.det_index(); r.count = pack.count();
   r.boxes = c->d_oboxes; r.scores = c->d_oscores; r.classes = c->d_oclasses;
   r.logits = c->d_ologits; r.probs = c->d_oprobs; r.entropy = c->d_oentropy;
-  r.rows = c->d_asg_rows;
+  r.rows = (float*)c->asg.aux;
   r.n = n; r.M = M; r.G = G; r.bc = a.det_stride; r.cc = cls_cols_of(m, UDA_POST_GLOBAL); r.C = C; r.cols = assigned_row_cols_of(m);
   launch_gather_assigned(r, c->stream);
   HIPC(c, hipGetLastError());
-  c->asg_n = n; c->asg_G = G; c->asg_rows = -1;
+  c->asg_n = n; c->asg_G = G; c->asg.fetched = false;
   return 0;
 }
 
-// The first reader of an assignment waits for it and brings the packed results over in one copy.
+// The host copy of the last assignment's pack (fetch_result), its error word checked and its matched rows counted.
 static int fetch_assignment(uda_ctx* c) {
-  if (c->asg_rows >= 0) return 0;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));
   AssignPack h(nullptr, (size_t)c->asg_n, (size_t)c->asg_G);
-  c->h_asg.resize(h.bytes());
-  h.base = c->h_asg.data();
-  HIPC(c, hipMemcpy(h.base, c->d_asg_pack, h.bytes(), hipMemcpyDeviceToHost));
+  if (int rc = fetch_result(c, c->asg, h.bytes())) return rc;
+  h.base = c->asg.h.data();
   if (int rc = h.copy_out(c, "assign_ground_truth", c->model.max_output_size, nullptr, nullptr, nullptr)) return rc;      // (the error word)
   c->asg_rows = std::accumulate(h.count(), h.count() + h.n, (int64_t)0);
   return 0;
@@ -248,7 +319,7 @@ extern "C" int uda_get_assignment(uda_ctx_t* c, int32_t* det_index, double* iou,
   if (!c) return 1;
   if (c->asg_n < 1) return fail(c, "get_assignment: no assignment (uda_assign_ground_truth)");
   if (int rc = fetch_assignment(c)) return rc;
-  return AssignPack(c->h_asg.data(), (size_t)c->asg_n, (size_t)c->asg_G)
+  return AssignPack(c->asg.h.data(), (size_t)c->asg_n, (size_t)c->asg_G)
       .copy_out(c, "assign_ground_truth", c->model.max_output_size, det_index, iou, count);
 }
 
@@ -260,7 +331,7 @@ extern "C" int uda_get_assigned_rows(uda_ctx_t* c, float* rows, int64_t n_floats
   if (n_floats != want) return fail(c, "get_assigned_rows: the %lld matched rows take %lld floats, not %lld", (long long)c->asg_rows, (long long)want, (long long)n_floats);
   if (want && !rows) return fail(c, "get_assigned_rows: NULL output");
   HIPC(c, hipSetDevice(c->device));
-  if (want) HIPC(c, hipMemcpy(rows, c->d_asg_rows, (size_t)want * sizeof(float), hipMemcpyDeviceToHost));
+  if (want) HIPC(c, hipMemcpy(rows, c->asg.aux, (size_t)want * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -280,13 +351,10 @@ extern "C" int uda_assign_gt_np(int32_t device, const float* det_boxes, const fl
   AssignPack pack(nullptr, (size_t)n, (size_t)G);
   pack.base = s.alloc<char>(pack.bytes());
   s.zero(pack.count(), ((size_t)n + 1) * sizeof(int32_t));
-  a.det_index = pack.det_index(); a.iou = pack.iou(); a.count = pack.count(); a.err = pack.err();
-  a.n = n; a.M = M; a.G = G; a.method = method; a.keep = keep;
+  pack.fill(a, M, method, keep);
   if (s.ok()) launch_assign_gt(a, nullptr);
-  s.sync();
-  std::vector<char> h(pack.bytes());
-  s.download(h.data(), pack.base, h.size());
-  if (!s.ok()) return hip_failed(nullptr, "uda_assign_gt_np", s.err);
+  std::vector<char> h;
+  if (int rc = fetch_pack("uda_assign_gt_np", s, pack.base, pack.bytes(), h)) return rc;
   return AssignPack(h.data(), pack.n, pack.G).copy_out(nullptr, "uda_assign_gt_np", M, det_index, iou, count);
 }
 
@@ -316,6 +384,55 @@ static unsigned score_desc_sources(const uda_score_desc_t* d, const char** why) 
   return mask;
 }
 
+// the refusal when the model does not emit a source the descriptor reads; null when it emits them all
+static const char* score_sources_missing(const uda_model_t& m, unsigned need) {
+  if ((need & (1u << UDA_SCORE_ENTROPY)) && !m.enable_softmax) return "the model emits no entropy (enable_softmax is off)";
+  if ((need & (1u << UDA_SCORE_ALBOX)) && !(m.has_uncert && m.loss_attenuation))
+    return "the model emits no aleatoric box uncertainty (no loss attenuation)";
+  if ((need & (1u << UDA_SCORE_MCBOX)) && !(m.has_uncert && m.box_stacked))
+    return "the model emits no epistemic box uncertainty (no MC dropout on the box head)";
+  if ((need & (1u << UDA_SCORE_MCCLASS)) && !(m.has_uncert && m.cls_stacked))
+    return "the model emits no epistemic class uncertainty (no MC dropout on the class head)";
+  return nullptr;
+}
+
+// The problem a descriptor poses on the run resident in the handle: the columns of the global post-process as its sources (after
+// ensure_probs where it reads the entropy), every image of the last run.
+static int resident_score_sources(uda_ctx* c, unsigned need, const uda_score_desc_t* desc, float min_score, ScoreArgs<float>& a) {
+  const uda_model_t& m = c->model;
+  a.n = c->last_n; a.M = m.max_output_size; a.C = m.num_classes; a.min_score = min_score; a.desc = *desc;
+  if (need & (1u << UDA_SCORE_ENTROPY))
+    if (int rc = ensure_probs(c, a.n * a.M)) return rc;
+  const int bc = box_cols_of(m, UDA_POST_GLOBAL), cc = cls_cols_of(m, UDA_POST_GLOBAL);
+  a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses; a.entropy = c->d_oentropy;
+  a.albox = c->d_oboxes + 4;                                               // box | aleatoric std | MC std, as each exists
+  a.mcbox = c->d_oboxes + ((m.has_uncert && m.loss_attenuation) ? 8 : 4);
+  a.mcclass = c->d_oclasses + 1;
+  a.box_stride = a.al_stride = a.mc_stride = bc; a.cls_stride = a.mcc_stride = cc; a.mcc_w = cc - 1;
+  return 0;
+}
+
+// The same problem on host columns [n, M, width]: refuses a source the descriptor reads and the caller did not give, then
+// uploads what is given.  host: boxes, scores, classes, entropy, albox, mcbox, mcclass (mcw columns).
+template <typename T>
+static int upload_score_sources(const char* who, DevScratch& s, unsigned need, const T* const (&host)[7], int n, int M, int C, int mcw,
+                                const uda_score_desc_t* desc, T min_score, ScoreArgs<T>& a) {
+  static const char* names[] = {"boxes", "scores", "classes", "entropy", "albox", "mcbox", "mcclass"};
+  static const int source[] = {-1, UDA_SCORE_DET_SCORE, -1, UDA_SCORE_ENTROPY, UDA_SCORE_ALBOX, UDA_SCORE_MCBOX, UDA_SCORE_MCCLASS};
+  const size_t nm = (size_t)n * M, widths[] = {4, 1, 1, 1, 4, 4, (size_t)(mcw > 0 ? mcw : 0)};
+  for (int k = 0; k < 7; ++k)
+    if (source[k] >= 0 && (need & (1u << source[k])) && nm && !host[k])
+      return fail(nullptr, "%s: the descriptor reads %s, which is not given", who, names[k]);
+  if ((need & (1u << UDA_SCORE_MCCLASS)) && mcw < 1) return fail(nullptr, "%s: mcclass_cols must be at least 1", who);
+  const T* dev[7] = {};
+  for (int k = 0; k < 7; ++k)
+    if (nm * widths[k]) dev[k] = s.upload(host[k], nm * widths[k]);
+  a.boxes = dev[0]; a.scores = dev[1]; a.classes = dev[2]; a.entropy = dev[3]; a.albox = dev[4]; a.mcbox = dev[5]; a.mcclass = dev[6];
+  a.box_stride = a.al_stride = a.mc_stride = 4; a.cls_stride = 1; a.mcc_stride = a.mcc_w = (int)widths[6];
+  a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
+  return 0;
+}
+
 extern "C" int uda_score_images(uda_ctx_t* c, const uda_score_desc_t* desc, float min_score) {
   if (!c) return 1;
   const uda_model_t& m = c->model;
@@ -323,38 +440,23 @@ extern "C" int uda_score_images(uda_ctx_t* c, const uda_score_desc_t* desc, floa
   const unsigned need = score_desc_sources(desc, &why);
   if (why) return fail(c, "score_images: %s", why);
   if (int rc = resident_ready(c, "score_images", "the scores read")) return rc;
-  if ((need & (1u << UDA_SCORE_ENTROPY)) && !m.enable_softmax)
-    return fail(c, "score_images: the model emits no entropy (enable_softmax is off)");
-  if ((need & (1u << UDA_SCORE_ALBOX)) && !(m.has_uncert && m.loss_attenuation))
-    return fail(c, "score_images: the model emits no aleatoric box uncertainty (no loss attenuation)");
-  if ((need & (1u << UDA_SCORE_MCBOX)) && !(m.has_uncert && m.box_stacked))
-    return fail(c, "score_images: the model emits no epistemic box uncertainty (no MC dropout on the box head)");
-  if ((need & (1u << UDA_SCORE_MCCLASS)) && !(m.has_uncert && m.cls_stacked))
-    return fail(c, "score_images: the model emits no epistemic class uncertainty (no MC dropout on the class head)");
+  if (const char* lacks = score_sources_missing(m, need)) return fail(c, "score_images: %s", lacks);
   if (m.max_output_size > kScoreMaxM) return fail(c, "score_images: max_output_size %d above %d", m.max_output_size, kScoreMaxM);
   if (m.num_classes < 1 || m.num_classes > kScoreMaxC) return fail(c, "score_images: num_classes %d outside 1..%d", m.num_classes, kScoreMaxC);
   if (int rc = settle_detections(c)) return rc;
-  const int n = c->last_n, M = m.max_output_size, C = m.num_classes, nc = desc->n_comp;
-  if (!c->d_score_pack) HIPC(c, dalloc(&c->d_score_pack, ScorePack(nullptr, (size_t)m.max_images, UDA_SCORE_MAX_COMP, (size_t)C).bytes()));
+  const int n = c->last_n, nc = desc->n_comp;
+  if (!c->score.d) HIPC(c, dalloc(&c->score.d, ScorePack(nullptr, (size_t)m.max_images, UDA_SCORE_MAX_COMP, (size_t)m.num_classes).bytes()));
   {
     ProfScope ps(c, 19);
-    if (need & (1u << UDA_SCORE_ENTROPY))
-      if (int rc = ensure_probs(c, n * M)) return rc;
-    const int bc = box_cols_of(m, UDA_POST_GLOBAL), cc = cls_cols_of(m, UDA_POST_GLOBAL);
+    const ScorePack pack(c->score.d, (size_t)n, (size_t)nc, (size_t)m.num_classes);
     ScoreArgs<float> a{};
-    a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses; a.entropy = c->d_oentropy;
-    a.albox = c->d_oboxes + 4;                                               // box | aleatoric std | MC std, as each exists
-    a.mcbox = c->d_oboxes + ((m.has_uncert && m.loss_attenuation) ? 8 : 4);
-    a.mcclass = c->d_oclasses + 1;
-    a.box_stride = a.al_stride = a.mc_stride = bc; a.cls_stride = a.mcc_stride = cc; a.mcc_w = cc - 1;
-    const ScorePack pack(c->d_score_pack, (size_t)n, (size_t)nc, (size_t)C);
+    if (int rc = resident_score_sources(c, need, desc, min_score, a)) return rc;
     a.comp = pack.comp(); a.count = pack.count(); a.class_counts = pack.class_counts(); a.err = pack.err();
-    a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
     HIPC(c, hipMemsetAsync(a.err, 0, sizeof(int32_t), c->stream));
     launch_score_images(a, c->stream);
   }
   HIPC(c, hipGetLastError());
-  c->score_n = n; c->score_nc = nc; c->score_fetched = false;
+  c->score_n = n; c->score_nc = nc; c->score.fetched = false;
   return 0;
 }
 
@@ -368,14 +470,8 @@ extern "C" int uda_get_image_scores(uda_ctx_t* c, double* components, int32_t* c
   if (!c) return 1;
   if (c->score_n < 1) return fail(c, "get_image_scores: no scores (uda_score_images)");
   ScorePack h(nullptr, (size_t)c->score_n, (size_t)c->score_nc, (size_t)c->model.num_classes);
-  if (!c->score_fetched) {       // the first reader of a scoring waits for it and brings the pack over in one copy
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    c->h_score.resize(h.bytes());
-    HIPC(c, hipMemcpy(c->h_score.data(), c->d_score_pack, h.bytes(), hipMemcpyDeviceToHost));
-    c->score_fetched = true;
-  }
-  h.base = c->h_score.data();
+  if (int rc = fetch_result(c, c->score, h.bytes())) return rc;
+  h.base = c->score.h.data();
   return h.copy_out(c, "score_images", components, count, class_counts);
 }
 
@@ -390,34 +486,18 @@ static int score_images_np(const char* who, int32_t device, const uda_score_desc
   if (why) return fail(nullptr, "%s: %s", who, why);
   if (n < 0 || M < 0 || M > kScoreMaxM || C < 1 || C > kScoreMaxC || ((size_t)n * M && (!boxes || !scores || !classes)))
     return fail(nullptr, "%s: bad argument", who);
-  const T* srcs[] = {entropy, scores, albox, mcbox, mcclass};
-  static const char* names[] = {"entropy", "scores", "albox", "mcbox", "mcclass"};
-  for (int s = 0; s < 5; ++s)
-    if ((need & (1u << s)) && (size_t)n * M && !srcs[s]) return fail(nullptr, "%s: the descriptor reads %s, which is not given", who, names[s]);
-  if ((need & (1u << UDA_SCORE_MCCLASS)) && mcw < 1) return fail(nullptr, "%s: mcclass_cols must be at least 1", who);
-  if (n == 0) return 0;
-  const size_t nm = (size_t)n * M, nc = desc->n_comp;
-  const size_t widths[] = {4, 1, 1, 1, 4, 4, (size_t)(mcw > 0 ? mcw : 0)};
   const T* host[] = {boxes, scores, classes, entropy, albox, mcbox, mcclass};
   DevScratch s(device);
-  T* dev[7] = {};
-  for (int k = 0; k < 7; ++k)
-    if (nm * widths[k]) dev[k] = s.upload(host[k], nm * widths[k]);
-  ScorePack pack(nullptr, (size_t)n, nc, (size_t)C);
+  ScoreArgs<T> a{};
+  if (int rc = upload_score_sources(who, s, need, host, n, M, C, mcw, desc, min_score, a)) return rc;
+  if (n == 0) return 0;
+  ScorePack pack(nullptr, (size_t)n, (size_t)desc->n_comp, (size_t)C);
   pack.base = s.alloc<char>(pack.bytes());
   s.zero(pack.base, pack.bytes());
-  if (s.ok()) {
-    ScoreArgs<T> a{};
-    a.boxes = dev[0]; a.scores = dev[1]; a.classes = dev[2]; a.entropy = dev[3]; a.albox = dev[4]; a.mcbox = dev[5]; a.mcclass = dev[6];
-    a.box_stride = a.al_stride = a.mc_stride = 4; a.cls_stride = 1; a.mcc_stride = a.mcc_w = mcw > 0 ? mcw : 0;
-    a.comp = pack.comp(); a.count = pack.count(); a.class_counts = pack.class_counts(); a.err = pack.err();
-    a.n = n; a.M = M; a.C = C; a.min_score = min_score; a.desc = *desc;
-    launch_score_images(a, nullptr);
-  }
-  s.sync();
-  std::vector<char> h(pack.bytes());
-  s.download(h.data(), pack.base, h.size());
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  a.comp = pack.comp(); a.count = pack.count(); a.class_counts = pack.class_counts(); a.err = pack.err();
+  if (s.ok()) launch_score_images(a, nullptr);
+  std::vector<char> h;
+  if (int rc = fetch_pack(who, s, pack.base, pack.bytes(), h)) return rc;
   return ScorePack(h.data(), pack.n, pack.nc, pack.C).copy_out(nullptr, who, components, count, class_counts);
 }
 
@@ -458,77 +538,56 @@ extern "C" int uda_pseudo_rows(uda_ctx_t* c, const uda_score_desc_t* desc, int32
   if (!why) why = pseudo_args_bad(desc, invert, gate, tau, max_rows);
   if (why) return fail(c, "pseudo_rows: %s", why);
   if (int rc = resident_ready(c, "pseudo_rows", "the pseudo-labels read")) return rc;
-  if ((need & (1u << UDA_SCORE_ENTROPY)) && !m.enable_softmax)
-    return fail(c, "pseudo_rows: the model emits no entropy (enable_softmax is off)");
-  if ((need & (1u << UDA_SCORE_ALBOX)) && !(m.has_uncert && m.loss_attenuation))
-    return fail(c, "pseudo_rows: the model emits no aleatoric box uncertainty (no loss attenuation)");
-  if ((need & (1u << UDA_SCORE_MCBOX)) && !(m.has_uncert && m.box_stacked))
-    return fail(c, "pseudo_rows: the model emits no epistemic box uncertainty (no MC dropout on the box head)");
-  if ((need & (1u << UDA_SCORE_MCCLASS)) && !(m.has_uncert && m.cls_stacked))
-    return fail(c, "pseudo_rows: the model emits no epistemic class uncertainty (no MC dropout on the class head)");
+  if (const char* lacks = score_sources_missing(m, need)) return fail(c, "pseudo_rows: %s", lacks);
   if (m.max_output_size > kScoreMaxM) return fail(c, "pseudo_rows: max_output_size %d above %d", m.max_output_size, kScoreMaxM);
   if (m.num_classes < 1) return fail(c, "pseudo_rows: num_classes %d below 1", m.num_classes);
   if (int rc = settle_detections(c)) return rc;
   const int n = c->last_n, M = m.max_output_size, cap = std::min(M, max_rows);
-  if (!c->d_pseudo_pack) {
-    HIPC(c, dalloc(&c->d_pseudo_pack, PseudoPack(nullptr, (size_t)m.max_images, (size_t)M).bytes()));
-    HIPC(c, dalloc(&c->d_pseudo_slots, (size_t)m.max_images * M * sizeof(PseudoRecord)));
+  if (!c->pseudo.d) {
+    HIPC(c, dalloc(&c->pseudo.d, PseudoPack(nullptr, (size_t)m.max_images, (size_t)M).bytes()));
+    HIPC(c, hipMalloc(&c->pseudo.aux, (size_t)m.max_images * M * sizeof(PseudoRecord)));
   }
   {
     ProfScope ps(c, 21);
-    if (need & (1u << UDA_SCORE_ENTROPY))
-      if (int rc = ensure_probs(c, n * M)) return rc;
-    const int bc = box_cols_of(m, UDA_POST_GLOBAL), cc = cls_cols_of(m, UDA_POST_GLOBAL);
+    const PseudoPack pack(c->pseudo.d, (size_t)n, (size_t)cap);
     PseudoArgs<float> a{};
-    a.s.boxes = c->d_oboxes; a.s.scores = c->d_oscores; a.s.classes = c->d_oclasses; a.s.entropy = c->d_oentropy;
-    a.s.albox = c->d_oboxes + 4;                                             // box | aleatoric std | MC std, as each exists
-    a.s.mcbox = c->d_oboxes + ((m.has_uncert && m.loss_attenuation) ? 8 : 4);
-    a.s.mcclass = c->d_oclasses + 1;
-    a.s.box_stride = a.s.al_stride = a.s.mc_stride = bc; a.s.cls_stride = a.s.mcc_stride = cc; a.s.mcc_w = cc - 1;
-    const PseudoPack pack(c->d_pseudo_pack, (size_t)n, (size_t)cap);
-    a.s.err = pack.err(); a.s.n = n; a.s.M = M; a.s.C = m.num_classes; a.s.min_score = min_score; a.s.desc = *desc;
+    if (int rc = resident_score_sources(c, need, desc, min_score, a.s)) return rc;
+    a.s.err = pack.err();
     a.tau = tau; a.invert = invert; a.gate = gate; a.max_rows = max_rows; a.cap = cap;
     a.minmax = pack.minmax(); a.kept = pack.kept(); a.cand = pack.cand(); a.records = pack.rec();
-    a.slots = (PseudoRecord*)c->d_pseudo_slots;
+    a.slots = (PseudoRecord*)c->pseudo.aux;
     HIPC(c, hipMemsetAsync(a.s.err, 0, sizeof(int32_t), c->stream));
     launch_pseudo_rows(a, c->stream);
   }
   HIPC(c, hipGetLastError());
-  c->pseudo_n = n; c->pseudo_cap = cap; c->pseudo_fetched = false;
+  c->pseudo_n = n; c->pseudo_cap = cap; c->pseudo.fetched = false;
   return 0;
 }
 
-// The first reader of a run waits for it and brings the pack's head over in one copy.
+// The host copy of the pack's head (fetch_result): the records stay on the device until uda_get_pseudo_rows asks for the used ones.
 static int fetch_pseudo(uda_ctx* c, const char* who) {
   if (c->pseudo_n < 1) return fail(c, "%s: no pseudo-label rows (uda_pseudo_rows)", who);
-  if (c->pseudo_fetched) return 0;
-  const PseudoPack h(nullptr, (size_t)c->pseudo_n, (size_t)c->pseudo_cap);
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  c->h_pseudo.resize(h.head_bytes());
-  HIPC(c, hipMemcpy(c->h_pseudo.data(), c->d_pseudo_pack, h.head_bytes(), hipMemcpyDeviceToHost));
-  c->pseudo_fetched = true;
-  return 0;
+  return fetch_result(c, c->pseudo, PseudoPack(nullptr, (size_t)c->pseudo_n, (size_t)c->pseudo_cap).head_bytes());
 }
 
 extern "C" int uda_pseudo_rows_shape(uda_ctx_t* c, int32_t* n, int64_t* K) {
   if (!c || !n || !K) return 1;
   if (int rc = fetch_pseudo(c, "pseudo_rows_shape")) return rc;
   *n = c->pseudo_n;
-  *K = PseudoPack(c->h_pseudo.data(), (size_t)c->pseudo_n, (size_t)c->pseudo_cap).total();
+  *K = PseudoPack(c->pseudo.h.data(), (size_t)c->pseudo_n, (size_t)c->pseudo_cap).total();
   return 0;
 }
 
 extern "C" int uda_get_pseudo_rows(uda_ctx_t* c, void* records, int64_t n_records, double* minmax, int32_t* kept, int32_t* cand) {
   if (!c) return 1;
   if (int rc = fetch_pseudo(c, "get_pseudo_rows")) return rc;
-  const PseudoPack h(c->h_pseudo.data(), (size_t)c->pseudo_n, (size_t)c->pseudo_cap);
+  const PseudoPack h(c->pseudo.h.data(), (size_t)c->pseudo_n, (size_t)c->pseudo_cap);
   if (int rc = h.copy_out(c, "pseudo_rows", c->model.num_classes, nullptr, nullptr, 0, minmax, kept, cand)) return rc;
   if (!records) return 0;
   if (n_records != h.total()) return fail(c, "pseudo_rows: %lld candidate records, not %lld", (long long)h.total(), (long long)n_records);
   // the used records only, straight into the caller's array (the stream was waited for when the head was fetched)
   if (n_records)
-    HIPC(c, hipMemcpy(records, PseudoPack(c->d_pseudo_pack, h.n, h.cap).rec(), (size_t)n_records * sizeof(PseudoRecord), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(records, PseudoPack(c->pseudo.d, h.n, h.cap).rec(), (size_t)n_records * sizeof(PseudoRecord), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -545,38 +604,23 @@ static int pseudo_rows_np(const char* who, int32_t device, const uda_score_desc_
   if (why) return fail(nullptr, "%s: %s", who, why);
   if (n < 0 || M < 0 || M > kScoreMaxM || C < 1 || ((size_t)n * M && (!boxes || !scores || !classes)) || (records && !n_records))
     return fail(nullptr, "%s: bad argument", who);
-  const T* srcs[] = {entropy, scores, albox, mcbox, mcclass};
-  static const char* names[] = {"entropy", "scores", "albox", "mcbox", "mcclass"};
-  for (int s = 0; s < 5; ++s)
-    if ((need & (1u << s)) && (size_t)n * M && !srcs[s]) return fail(nullptr, "%s: the descriptor reads %s, which is not given", who, names[s]);
-  if ((need & (1u << UDA_SCORE_MCCLASS)) && mcw < 1) return fail(nullptr, "%s: mcclass_cols must be at least 1", who);
-  if (n_records) *n_records = 0;
-  if (n == 0) return 0;
-  const size_t nm = (size_t)n * M, cap = (size_t)std::min(M, max_rows);
-  const size_t widths[] = {4, 1, 1, 1, 4, 4, (size_t)(mcw > 0 ? mcw : 0)};
   const T* host[] = {boxes, scores, classes, entropy, albox, mcbox, mcclass};
   DevScratch s(device);
-  T* dev[7] = {};
-  for (int k = 0; k < 7; ++k)
-    if (nm * widths[k]) dev[k] = s.upload(host[k], nm * widths[k]);
+  PseudoArgs<T> a{};
+  if (int rc = upload_score_sources(who, s, need, host, n, M, C, mcw, desc, min_score, a.s)) return rc;
+  if (n_records) *n_records = 0;
+  if (n == 0) return 0;
+  const size_t cap = (size_t)std::min(M, max_rows);
   PseudoPack pack(nullptr, (size_t)n, cap);
   pack.base = s.alloc<char>(pack.bytes());
   s.zero(pack.base, pack.bytes());
-  PseudoRecord* slots = s.alloc<PseudoRecord>((size_t)n * cap);
-  if (s.ok()) {
-    PseudoArgs<T> a{};
-    a.s.boxes = dev[0]; a.s.scores = dev[1]; a.s.classes = dev[2]; a.s.entropy = dev[3]; a.s.albox = dev[4]; a.s.mcbox = dev[5];
-    a.s.mcclass = dev[6];
-    a.s.box_stride = a.s.al_stride = a.s.mc_stride = 4; a.s.cls_stride = 1; a.s.mcc_stride = a.s.mcc_w = mcw > 0 ? mcw : 0;
-    a.s.err = pack.err(); a.s.n = n; a.s.M = M; a.s.C = C; a.s.min_score = min_score; a.s.desc = *desc;
-    a.tau = tau; a.invert = invert; a.gate = gate; a.max_rows = max_rows; a.cap = (int)cap;
-    a.minmax = pack.minmax(); a.kept = pack.kept(); a.cand = pack.cand(); a.records = pack.rec(); a.slots = slots;
-    launch_pseudo_rows(a, nullptr);
-  }
-  s.sync();
-  std::vector<char> h(pack.head_bytes());
-  s.download(h.data(), pack.base, h.size());
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  a.s.err = pack.err();
+  a.tau = tau; a.invert = invert; a.gate = gate; a.max_rows = max_rows; a.cap = (int)cap;
+  a.minmax = pack.minmax(); a.kept = pack.kept(); a.cand = pack.cand(); a.records = pack.rec();
+  a.slots = s.alloc<PseudoRecord>((size_t)n * cap);
+  if (s.ok()) launch_pseudo_rows(a, nullptr);
+  std::vector<char> h;
+  if (int rc = fetch_pack(who, s, pack.base, pack.head_bytes(), h)) return rc;
   const PseudoPack hp(h.data(), pack.n, pack.cap);
   const int64_t K = hp.total();
   std::vector<char> recs;
@@ -620,36 +664,31 @@ extern "C" int uda_label_check(uda_ctx_t* c, float min_score, double iou_consist
   if (!c) return 1;
   const uda_model_t& m = c->model;
   if (const char* why = label_check_args_bad(methods, md_rule)) return fail(c, "label_check: %s", why);
-  if (c->gt_n < 1) return fail(c, "label_check: no ground truth is set (uda_set_ground_truth)");
+  if (c->gt.n < 1) return fail(c, "label_check: no ground truth is set (uda_set_ground_truth)");
   if (int rc = resident_ready(c, "label_check", "the label check reads")) return rc;
-  // after a consistency run the handle holds 4n images, the n originals first: the ground truth belongs to those
-  const bool cons = c->noise_from >= 0 && c->cons_n > 0 && c->last_n == 4 * c->cons_n;
-  if (c->gt_n != (cons ? c->cons_n : c->last_n))
-    return fail(c, "label_check: ground truth of %d images, the last post-process holds %d", c->gt_n, cons ? c->cons_n : c->last_n);
+  if (int rc = gt_covers_run(c, "label_check", c->gt.n, true)) return rc;
+  const bool cons = holds_consistency_run(c);
   if ((methods & (LC_MD | LC_NOISY)) && !cons)
     return fail(c, "label_check: md and noisy read cons_iou, and the resident run is not a consistency run (uda_run_consistency)");
   if (m.max_output_size > kAssignMaxM) return fail(c, "label_check: max_output_size %d above %d", m.max_output_size, kAssignMaxM);
   if (int rc = settle_detections(c)) return rc;
-  const int n = c->gt_n, M = m.max_output_size, G = c->gt_G;
-  if (!c->d_lc_pack || G > c->lc_cap) {
+  const int n = c->gt.n, M = m.max_output_size, G = c->gt.G;
+  if (!c->lc.d || G > c->lc.cap) {
     HIPC(c, hipStreamSynchronize(c->stream));              // (growing is rare: nothing may still read the old buffer)
-    if (c->d_lc_pack) hipFree(c->d_lc_pack);
-    c->d_lc_pack = nullptr; c->lc_cap = 0; c->lc_n = 0;
-    const size_t cap = (size_t)std::max(G, 1);
-    HIPC(c, dalloc(&c->d_lc_pack, LabelPack(nullptr, (size_t)m.max_images, cap, (size_t)M).bytes()));
-    c->lc_cap = (int)cap;
+    c->lc.release();
+    c->lc_n = 0;
+    const int cap = std::max(G, 1);
+    HIPC(c, dalloc(&c->lc.d, LabelPack(nullptr, (size_t)m.max_images, (size_t)cap, (size_t)M).bytes()));
+    c->lc.cap = cap;
   }
   LabelCheckArgs<float> a{};
   a.det_boxes = c->d_oboxes; a.det_stride = box_cols_of(m, UDA_POST_GLOBAL); a.scores = c->d_oscores;
   a.cons_iou = cons ? c->d_cons_iou : nullptr;
-  a.gt_boxes = c->d_gt_boxes; a.gt_classes = c->d_gt_classes;
-  LabelPack(c->d_lc_pack, (size_t)n, (size_t)G, (size_t)M).fill(a);
-  a.n = n; a.M = M; a.G = G; a.methods = methods; a.md_rule = md_rule;
-  a.min_score = min_score; a.correct_score = correct_score;
-  a.iou_consist = iou_consist; a.md_max_inter = md_max_inter; a.correct_max_inter = correct_max_inter;
+  a.gt_boxes = c->gt.d[0]; a.gt_classes = c->gt.d[1];
+  LabelPack(c->lc.d, (size_t)n, (size_t)G, (size_t)M).fill(a, methods, md_rule, min_score, correct_score, iou_consist, md_max_inter, correct_max_inter);
   launch_label_check(a, c->stream);
   HIPC(c, hipGetLastError());
-  c->lc_n = n; c->lc_G = G; c->lc_fetched = false;
+  c->lc_n = n; c->lc_G = G; c->lc.fetched = false;
   return 0;
 }
 
@@ -658,14 +697,8 @@ extern "C" int uda_get_label_check(uda_ctx_t* c, int32_t* det_rank, double* iou,
   if (!c) return 1;
   if (c->lc_n < 1) return fail(c, "get_label_check: no label check (uda_label_check)");
   LabelPack h(nullptr, (size_t)c->lc_n, (size_t)c->lc_G, (size_t)c->model.max_output_size);
-  if (!c->lc_fetched) {          // the first reader of a check waits for it and brings the pack over in one copy
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    c->h_lc.resize(h.copy_bytes());
-    HIPC(c, hipMemcpy(c->h_lc.data(), c->d_lc_pack, h.copy_bytes(), hipMemcpyDeviceToHost));
-    c->lc_fetched = true;
-  }
-  h.base = c->h_lc.data();
+  if (int rc = fetch_result(c, c->lc, h.copy_bytes())) return rc;
+  h.base = c->lc.h.data();
   h.copy_out(det_rank, iou, gt_flags, gt_boxes_out, det_flags, det_max_iou, counts);
   return 0;
 }
@@ -691,15 +724,10 @@ static int label_check_np(const char* who, int32_t device, const T* boxes, const
   a.gt_boxes = s.upload(gt_boxes, ng * 4); a.gt_classes = s.upload(gt_classes, ng);
   LabelPack pack(nullptr, (size_t)n, (size_t)G, (size_t)M);
   pack.base = s.alloc<char>(pack.bytes());
-  LabelPack(pack.base, pack.n, pack.G, pack.M).fill(a);
-  a.n = n; a.M = M; a.G = G; a.methods = methods; a.md_rule = md_rule;
-  a.min_score = min_score; a.correct_score = correct_score;
-  a.iou_consist = iou_consist; a.md_max_inter = md_max_inter; a.correct_max_inter = correct_max_inter;
+  pack.fill(a, methods, md_rule, min_score, correct_score, iou_consist, md_max_inter, correct_max_inter);
   if (s.ok()) launch_label_check(a, nullptr);
-  s.sync();
-  std::vector<char> h(pack.copy_bytes());
-  s.download(h.data(), pack.base, h.size());
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
+  std::vector<char> h;
+  if (int rc = fetch_pack(who, s, pack.base, pack.copy_bytes(), h)) return rc;
   LabelPack(h.data(), pack.n, pack.G, pack.M).copy_out(det_rank, iou, gt_flags, gt_boxes_out, det_flags, det_max_iou, counts);
   return 0;
 }
@@ -738,56 +766,36 @@ extern "C" int uda_set_eval_ground_truth(uda_ctx_t* c, const float* gt, int32_t 
   const uda_model_t& m = c->model;
   if (n < 1 || n > m.max_images) return fail(c, "set_eval_ground_truth: %d images, the handle holds 1..%d", n, m.max_images);
   if (G < 0 || G > COCO_MAX_G) return fail(c, "set_eval_ground_truth: %d ground-truth rows per image, at most %d", G, (int)COCO_MAX_G);
-  HIPC(c, hipSetDevice(c->device));
-  if (!c->egt_ev) HIPC(c, hipEventCreateWithFlags(&c->egt_ev, hipEventDisableTiming));
-  else HIPC(c, hipEventSynchronize(c->egt_ev));         // the previous upload has left the staging buffer
-  if (G > c->egt_cap || !c->d_egt) {
-    HIPC(c, hipStreamSynchronize(c->stream));            // (growing is rare: nothing may still read the old buffer)
-    if (c->d_egt) hipFree(c->d_egt);
-    if (c->h_egt) hipHostFree(c->h_egt);
-    c->d_egt = c->h_egt = nullptr; c->egt_cap = 0; c->egt_n = 0;
-    const size_t cap = (size_t)std::max(G, 1), rows = (size_t)m.max_images * cap;
-    HIPC(c, dalloc(&c->d_egt, rows * 7));
-    HIPC(c, hipHostMalloc((void**)&c->h_egt, rows * 7 * sizeof(float)));
-    c->egt_cap = (int)cap;
-  }
-  const size_t floats = (size_t)n * G * 7;
-  if (floats) {
-    memcpy(c->h_egt, gt, floats * sizeof(float));
-    HIPC(c, hipMemcpyAsync(c->d_egt, c->h_egt, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPC(c, hipEventRecord(c->egt_ev, c->stream));
-  c->egt_n = n; c->egt_G = G;
-  return 0;
+  const float* src[] = {gt, nullptr};
+  return stage_ground_truth(c, c->egt, src, n, G);
 }
 
 extern "C" int uda_eval_match(uda_ctx_t* c, const double* iou_thrs, int32_t T) {
   if (!c) return 1;
   const uda_model_t& m = c->model;
   if (const char* why = eval_thrs_bad(iou_thrs, T)) return fail(c, "eval_match: %s", why);
-  if (c->egt_n < 1) return fail(c, "eval_match: no ground truth is set (uda_set_eval_ground_truth)");
+  if (c->egt.n < 1) return fail(c, "eval_match: no ground truth is set (uda_set_eval_ground_truth)");
   if (int rc = resident_ready(c, "eval_match", nullptr)) return rc;
-  if (c->egt_n != c->last_n)
-    return fail(c, "eval_match: ground truth of %d images, the last post-process holds %d", c->egt_n, c->last_n);
+  if (int rc = gt_covers_run(c, "eval_match", c->egt.n, false)) return rc;
   if (m.max_output_size > COCO_MAX_M) return fail(c, "eval_match: max_output_size %d above %d", m.max_output_size, (int)COCO_MAX_M);
   if (m.num_classes < 1 || m.num_classes > kEvalMaxC) return fail(c, "eval_match: num_classes %d outside 1..%d", m.num_classes, kEvalMaxC);
   if (int rc = settle_detections(c)) return rc;
   const int n = c->last_n, M = m.max_output_size, C = m.num_classes;
-  if (!c->d_eval_pack) HIPC(c, dalloc(&c->d_eval_pack, EvalPack(nullptr, (size_t)m.max_images, (size_t)M, (size_t)C).bytes()));
+  if (!c->eval.d) HIPC(c, dalloc(&c->eval.d, EvalPack(nullptr, (size_t)m.max_images, (size_t)M, (size_t)C).bytes()));
   {
     ProfScope ps(c, 20);
     CocoMatchArgs a{};
     a.boxes = c->d_oboxes; a.scores = c->d_oscores; a.classes = c->d_oclasses;
     a.box_stride = box_cols_of(m, c->last_post_mode); a.cls_stride = cls_cols_of(m, c->last_post_mode);
-    a.gt = c->d_egt;
-    const EvalPack pack(c->d_eval_pack, (size_t)n, (size_t)M, (size_t)C);
+    a.gt = c->egt.d[0];
+    const EvalPack pack(c->eval.d, (size_t)n, (size_t)M, (size_t)C);
     a.rec = pack.rec(); a.npig = pack.npig(); a.used = pack.used();
-    a.n = n; a.M = M; a.G = c->egt_G; a.C = C; a.T = T; a.legacy = 0;
+    a.n = n; a.M = M; a.G = c->egt.G; a.C = C; a.T = T; a.legacy = 0;
     for (int t = 0; t < T; ++t) a.thr[t] = iou_thrs[t];
     launch_coco_match(a, c->stream);
   }
   HIPC(c, hipGetLastError());
-  c->eval_n = n; c->eval_fetched = false;
+  c->eval_n = n; c->eval.fetched = false;
   return 0;
 }
 
@@ -795,14 +803,8 @@ extern "C" int uda_get_eval_records(uda_ctx_t* c, void* records, int32_t* npig, 
   if (!c) return 1;
   if (c->eval_n < 1) return fail(c, "get_eval_records: no match (uda_eval_match)");
   EvalPack h(nullptr, (size_t)c->eval_n, (size_t)c->model.max_output_size, (size_t)c->model.num_classes);
-  if (!c->eval_fetched) {        // the first reader of a match waits for it and brings the pack over in one copy
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    c->h_eval.resize(h.bytes());
-    HIPC(c, hipMemcpy(c->h_eval.data(), c->d_eval_pack, h.bytes(), hipMemcpyDeviceToHost));
-    c->eval_fetched = true;
-  }
-  h.base = c->h_eval.data();
+  if (int rc = fetch_result(c, c->eval, h.bytes())) return rc;
+  h.base = c->eval.h.data();
   h.copy_out(records, npig, used);
   return 0;
 }
@@ -827,10 +829,8 @@ extern "C" int uda_eval_match_np(int32_t device, const float* det_rows, const fl
   a.n = n; a.M = M; a.G = G; a.C = num_classes; a.T = T; a.legacy = 1;
   for (int t = 0; t < T; ++t) a.thr[t] = iou_thrs[t];
   if (s.ok()) launch_coco_match(a, nullptr);
-  s.sync();
-  std::vector<char> h(pack.bytes());
-  s.download(h.data(), pack.base, h.size());
-  if (!s.ok()) return hip_failed(nullptr, "uda_eval_match_np", s.err);
+  std::vector<char> h;
+  if (int rc = fetch_pack("uda_eval_match_np", s, pack.base, pack.bytes(), h)) return rc;
   EvalPack(h.data(), pack.n, pack.M, pack.C).copy_out(records, npig, used);
   return 0;
 }
@@ -885,8 +885,7 @@ extern "C" int uda_thr_objective_np(int32_t device, const double* uncerts, const
       if (auc) auc[o] = h[3 * q + 2];
     }
   }
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
-  return 0;
+  return scratch_done(nullptr, who, s);
 }
 
 // the neighbour rows of the pruning step: host hashes in, four passes with a launch boundary between them (max, count, scan,
@@ -947,8 +946,7 @@ extern "C" int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int
   if (s.ok()) launch_prune_fill(a, nullptr);
   s.sync();
   s.download(idx, a.idx, (size_t)tot * sizeof(int32_t));
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
-  return 0;
+  return scratch_done(nullptr, who, s);
 }
 
 // the neighbour search of the set-similarity analysis: B ragged problems in, one launch over a table of (problem, row block,
@@ -998,8 +996,7 @@ extern "C" int uda_nn_dist2_np(int32_t device, int32_t D, int32_t B, const doubl
   if (s.ok()) launch_knn_min(a, nullptr);
   s.sync();
   s.download(d2, a.d2_bits, (size_t)a.total * sizeof(double));
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
-  return 0;
+  return scratch_done(nullptr, who, s);
 }
 
 // the pseudo-label audit: B ragged images in, one block each, the results in ONE device allocation, each array the caller asked
@@ -1026,48 +1023,30 @@ extern "C" int uda_pseudo_audit_np(int32_t device, int32_t B, const double* gt_b
   }
   const size_t NG = (size_t)gt_off[B], ND = (size_t)det_off[B];
   if ((NG && !gt_boxes) || (ND && !det_boxes)) return fail(nullptr, "%s: NULL boxes", who);
-  // the pack: float64 [NG | ND | ND | ND], int32 [NG | NG | ND | ND | B], uint8 [NG | ND]
-  const size_t n64 = NG + 3 * ND, n32 = 2 * NG + 2 * ND + (size_t)B, n8 = NG + ND;
-  const size_t bytes = n64 * sizeof(double) + n32 * sizeof(int32_t) + n8;
   DevScratch s(device);
   AuditArgs a{};
   a.B = B; a.max_g = (int)max_g; a.max_d = (int)max_d; a.gt_iou_thr = gt_iou_thr;
   a.gt_boxes = s.upload(gt_boxes, NG * 4); a.det_boxes = s.upload(det_boxes, ND * 4);
   a.gt_off = s.upload(gt_off, (size_t)B + 1); a.det_off = s.upload(det_off, (size_t)B + 1);
-  char* pack = s.alloc<char>(bytes);
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
-  auto lay = [&](char* base) {
-    double* f = (double*)base;
-    int32_t* i = (int32_t*)(f + n64);
-    uint8_t* u = (uint8_t*)(i + n32);
-    AuditArgs o{};
-    o.gt_max_iou = f; o.det_max_iou = f + NG; o.det_alloc_miou = f + NG + ND; o.det_alloc_pair_iou = f + NG + 2 * ND;
-    o.gt_best_det = i; o.gt_alloc_det = i + NG; o.det_best_gt = i + 2 * NG; o.det_alloc_gt = i + 2 * NG + ND;
-    o.n_matches = i + 2 * NG + 2 * ND;
-    o.gt_flags = u; o.det_flags = u + NG;
-    return o;
-  };
-  const AuditArgs dv = lay(pack);
-  a.gt_max_iou = dv.gt_max_iou; a.det_max_iou = dv.det_max_iou; a.det_alloc_miou = dv.det_alloc_miou;
-  a.det_alloc_pair_iou = dv.det_alloc_pair_iou; a.gt_best_det = dv.gt_best_det; a.gt_alloc_det = dv.gt_alloc_det;
-  a.det_best_gt = dv.det_best_gt; a.det_alloc_gt = dv.det_alloc_gt; a.n_matches = dv.n_matches; a.gt_flags = dv.gt_flags;
-  a.det_flags = dv.det_flags;
+  AuditPack pack(nullptr, NG, ND, (size_t)B);
+  pack.base = s.alloc<char>(pack.bytes());
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  pack.fill(a);
   launch_pseudo_audit(a, nullptr);
   s.sync();
   // every array the caller asked for, straight from its place in the pack (no staging copy on the host)
-  s.download(gt_max_iou, dv.gt_max_iou, gt_max_iou ? NG * sizeof(double) : 0);
-  s.download(gt_best_det, dv.gt_best_det, gt_best_det ? NG * sizeof(int32_t) : 0);
-  s.download(gt_alloc_det, dv.gt_alloc_det, gt_alloc_det ? NG * sizeof(int32_t) : 0);
-  s.download(gt_flags, dv.gt_flags, gt_flags ? NG : 0);
-  s.download(det_max_iou, dv.det_max_iou, det_max_iou ? ND * sizeof(double) : 0);
-  s.download(det_best_gt, dv.det_best_gt, det_best_gt ? ND * sizeof(int32_t) : 0);
-  s.download(det_alloc_gt, dv.det_alloc_gt, det_alloc_gt ? ND * sizeof(int32_t) : 0);
-  s.download(det_alloc_miou, dv.det_alloc_miou, det_alloc_miou ? ND * sizeof(double) : 0);
-  s.download(det_alloc_pair_iou, dv.det_alloc_pair_iou, det_alloc_pair_iou ? ND * sizeof(double) : 0);
-  s.download(det_flags, dv.det_flags, det_flags ? ND : 0);
-  s.download(n_matches, dv.n_matches, n_matches ? (size_t)B * sizeof(int32_t) : 0);
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
-  return 0;
+  s.download(gt_max_iou, a.gt_max_iou, gt_max_iou ? NG * sizeof(double) : 0);
+  s.download(gt_best_det, a.gt_best_det, gt_best_det ? NG * sizeof(int32_t) : 0);
+  s.download(gt_alloc_det, a.gt_alloc_det, gt_alloc_det ? NG * sizeof(int32_t) : 0);
+  s.download(gt_flags, a.gt_flags, gt_flags ? NG : 0);
+  s.download(det_max_iou, a.det_max_iou, det_max_iou ? ND * sizeof(double) : 0);
+  s.download(det_best_gt, a.det_best_gt, det_best_gt ? ND * sizeof(int32_t) : 0);
+  s.download(det_alloc_gt, a.det_alloc_gt, det_alloc_gt ? ND * sizeof(int32_t) : 0);
+  s.download(det_alloc_miou, a.det_alloc_miou, det_alloc_miou ? ND * sizeof(double) : 0);
+  s.download(det_alloc_pair_iou, a.det_alloc_pair_iou, det_alloc_pair_iou ? ND * sizeof(double) : 0);
+  s.download(det_flags, a.det_flags, det_flags ? ND : 0);
+  s.download(n_matches, a.n_matches, n_matches ? (size_t)B * sizeof(int32_t) : 0);
+  return scratch_done(nullptr, who, s);
 }
 
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,
@@ -1101,8 +1080,7 @@ extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32
   if (s.ok()) launch_calib(a, c->stream);
   s.sync(c->stream);
   s.download(out, d_out, rows * 4 * sizeof(float));
-  if (!s.ok()) return hip_failed(c, "calibrate_box", s.err);
-  return 0;
+  return scratch_done(c, "calibrate_box", s);
 }
 
 extern "C" int uda_calibrate_class(uda_ctx_t* c, int32_t mode, int32_t n_tables, const int32_t* tab_off, const double* xs,
@@ -1262,8 +1240,7 @@ extern "C" int uda_nms(uda_ctx_t* c, const float* boxes, const float* scores, in
   s.download(idx, a.sel_idx, NM * sizeof(int32_t));
   s.download(out_scores, a.sel_score, NM * sizeof(float));
   (void)pad;  // slots >= valid already hold index 0 / score 0.0 (the padded form); callers slice when pad == 0
-  if (!s.ok()) return hip_failed(c, "uda_nms", s.err);
-  return 0;
+  return scratch_done(c, "uda_nms", s);
 }
 
 // ------------------------------------------------------------------------------------ standalone 1x1 conv
@@ -1341,8 +1318,7 @@ static int run_nmsnp(const char* who, int device, const std::vector<T>& dets, co
   s.sync();
   s.download(out.data(), a.out, total * 5 * sizeof(T));
   s.download(n_out.data(), a.n_out, (size_t)problems * sizeof(int32_t));
-  if (!s.ok()) return hip_failed(nullptr, who, s.err);
-  return 0;
+  return scratch_done(nullptr, who, s);
 }
 
 // rows sorted by score, descending (what `dets[:, 4].argsort()[::-1]` yields for distinct scores; ties: later index first)

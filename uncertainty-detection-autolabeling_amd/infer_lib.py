@@ -174,6 +174,14 @@ class ServingDriver:
             self._seed_counter += 1
         self._ck(self._lib.uda_set_dropout_seed(self._h, C.c_uint64(seed)), "uda_set_dropout_seed")
 
+    def _run(self, fn, name, n, *args):
+        """Queue one run of the batch that is set - `fn` is uda_run, uda_run_consistency or uda_predict - with the next dropout
+        seed; afterwards the handle holds the results of `n` images."""
+        self._next_seed()
+        self._run_id += 1
+        self._ck(fn(self._h, *args), name)
+        self._last_n = n
+
     # ------------------------------------------------------------------ serve / predict
     def _as_u8_batch(self, image_arrays):
         """uint8 [N,h,w,3] (an array, or a list of equally sized images as the reference stacks them, infer_lib.py:139-151)."""
@@ -358,10 +366,7 @@ class ServingDriver:
         """uint8 images -> preprocess + network for this driver's samples, no post-process: the head outputs stay in the handle
         (`head_outputs`, `head_outputs_device`).  Returns the image count."""
         n = self._feed(image_arrays)
-        self._next_seed()
-        self._run_id += 1
-        self._ck(self._lib.uda_run(self._h, -1, 0), "uda_run")
-        self._last_n = n
+        self._run(self._lib.uda_run, "uda_run", n, -1, 0)
         return n
 
     def serve(self, image_arrays, post_mode=None):
@@ -373,10 +378,7 @@ class ServingDriver:
         output in that mode is corrupted by a variable overwrite (:659-666), so none is returned."""
         mode = self._mode(post_mode)
         n = self._feed(image_arrays)
-        self._next_seed()
-        self._run_id += 1
-        self._ck(self._lib.uda_run(self._h, mode, 1), "uda_run")
-        self._last_n = n
+        self._run(self._lib.uda_run, "uda_run", n, mode, 1)
         return self._collect(n, mode)
 
     def serve_consistency(self, image_arrays, post_mode=None):
@@ -395,10 +397,7 @@ class ServingDriver:
                              "(its handle is planned for the 3 variants of every image)")
         mode = self._mode(post_mode)
         n = self._feed(image_arrays)
-        self._next_seed()
-        self._run_id += 1
-        self._ck(self._lib.uda_run_consistency(self._h, mode), "uda_run_consistency")
-        self._last_n = 4 * n
+        self._run(self._lib.uda_run_consistency, "uda_run_consistency", 4 * n, mode)
         det = self._collect(4 * n, mode)
         iou = np.empty((n, self.M), np.float64)
         agree = np.empty((n, self.M), np.uint8)
@@ -492,10 +491,7 @@ class ServingDriver:
         if gb.shape[0] != n:
             raise ValueError("ground truth of %d images for a batch of %d" % (gb.shape[0], n))
         mc, kc = self._queue_assignment(gb, gc, method, keep)
-        self._next_seed()
-        self._run_id += 1
-        self._ck(self._lib.uda_run(self._h, capi.POST_GLOBAL, 1), "uda_run")
-        self._last_n = n
+        self._run(self._lib.uda_run, "uda_run", n, capi.POST_GLOBAL, 1)
         self._ck(self._lib.uda_assign_ground_truth(self._h, mc, kc), "uda_assign_ground_truth")
         det = self._collect(n, capi.POST_GLOBAL)
         return det, self._fetch_assignment(gb, gc, keep)
@@ -650,10 +646,7 @@ class ServingDriver:
         if gb.shape[0] != n:
             raise ValueError("ground truth of %d images for a batch of %d" % (gb.shape[0], n))
         self._ck(self._lib.uda_set_ground_truth(self._h, _ptr(gb), _ptr(gc), n, gb.shape[1]), "uda_set_ground_truth")
-        self._next_seed()
-        self._run_id += 1
-        self._ck(self._lib.uda_run_consistency(self._h, capi.POST_GLOBAL), "uda_run_consistency")
-        self._last_n = 4 * n
+        self._run(self._lib.uda_run_consistency, "uda_run_consistency", 4 * n, capi.POST_GLOBAL)
         self._queue_label_check(args)
         return self._fetch_label_check(gb, gc, methods, missing_boxes, names)
 
@@ -704,10 +697,7 @@ class ServingDriver:
         `class_probs`) - what the multi-GPU layer runs before its device-resident gather.  Returns the image count."""
         mode = self._mode(post_mode)
         n = self._feed(image_arrays)
-        self._next_seed()
-        self._run_id += 1
-        self._ck(self._lib.uda_run(self._h, mode, 1), "uda_run")
-        self._last_n = n
+        self._run(self._lib.uda_run, "uda_run", n, mode, 1)
         return n
 
     def serve_files(self, paths, post_mode=None):
@@ -793,10 +783,7 @@ class ServingDriver:
             raise ValueError("predict() takes float images [N,%d,%d,3], got %s" % (H, W, a.shape))
         if a.shape[0] > self._cap:
             raise ValueError("batch of %d images exceeds batch_size=%d" % (a.shape[0], self._cap))
-        self._next_seed()
-        self._run_id += 1
-        self._ck(self._lib.uda_predict(self._h, _ptr(a), a.shape[0]), "uda_predict")
-        self._last_n = a.shape[0]
+        self._run(self._lib.uda_predict, "uda_predict", a.shape[0], _ptr(a), a.shape[0])
         return a.shape[0]
 
     def predict(self, image_arrays):

@@ -185,41 +185,9 @@ def select_detections(columns, strategy, tau, min_score=0.1, params=None, opt_pa
     columns, strategy (a string or a `Selection`), params, num_classes, as_float32: as `active_learning.score_detections`
     takes them; box columns may hold zero sides (IEEE: inf / NaN values), the other columns must be finite.
     Returns (records [K] RECORD_DTYPE in (image, rank) order, minmax [n, 2] float64, kept [n] int32, cand [n] int32)."""
-    dt = np.float32 if as_float32 else np.float64
     tau = _check_tau(tau)
-    cols = {k: v for k, v in columns.items() if v is not None}
-    if not isinstance(strategy, Selection):
-        if params is None:
-            present = {src for src in ("entropy", "albox", "mcbox", "mcclass") if any(k == src or k.endswith("_" + src) for k in cols)}
-            strategy = resolve_selection(strategy, dict.fromkeys(present), opt_params)
-        else:
-            strategy = resolve_selection(strategy, params, opt_params)
-    scores = np.asarray(cols["scores"])
-    if scores.ndim != 2:
-        raise ValueError("scores must be [n, M], got %s" % (scores.shape,))
-    n, M = scores.shape
-    scores = al._column(scores, (n, M), "scores", dt)
-    boxes = al._column(np.asarray(cols["boxes"])[..., :4], (n, M, 4), "boxes", dt)
-    classes = al._column(cols["classes"], (n, M), "classes", dt)
-    if num_classes is None:
-        num_classes = int((params or {}).get("num_classes") or max(int(classes.max()) if classes.size else 1, 1))
-    arrays = {"entropy": None, "albox": None, "mcbox": None, "mcclass": None}
-    mcw = 0
-    for src in strategy.sources():
-        if src == "det_score":
-            continue
-        key = strategy.columns[src]
-        if key not in cols:
-            raise ValueError("strategy %r reads the column %r, which is not given" % (strategy.name, key))
-        a = np.asarray(cols[key])
-        finite = not as_float32 or src == "entropy"
-        if src == "mcclass":
-            if a.ndim == 2:
-                a = a[..., None]
-            mcw = a.shape[-1]
-            arrays[src] = al._column(a, (n, M, mcw), key, dt, finite)
-        else:
-            arrays[src] = al._column(a, (n, M) if src == "entropy" else (n, M, 4), key, dt, finite)
+    strategy, arrays, n, M, mcw, num_classes = al.detection_columns(columns, strategy, resolve_selection, params, opt_params, num_classes,
+                                                                    as_float32)
     if int(max_rows) < 1:
         raise ValueError("max_rows must be at least 1")
     rec = np.zeros((n * min(M, int(max_rows)),), RECORD_DTYPE)
@@ -231,12 +199,8 @@ def select_detections(columns, strategy, tau, min_score=0.1, params=None, opt_pa
     p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
     desc = strategy.desc()
     fn, what = (lib.uda_pseudo_rows_np_f32, "uda_pseudo_rows_np_f32") if as_float32 else (lib.uda_pseudo_rows_np, "uda_pseudo_rows_np")
-    rc = fn(int(device), C.byref(desc), float(min_score), p(boxes), p(scores), p(classes), p(arrays["entropy"]), p(arrays["albox"]),
-            p(arrays["mcbox"]), p(arrays["mcclass"]), n, M, int(num_classes), int(mcw), strategy.invert, strategy.gate, tau,
-            int(max_rows), p(rec), C.byref(K), p(minmax), p(kept), p(cand))
-    if rc != 0:
-        msg = lib.uda_last_error(None).decode()
-        raise (ValueError if "class id outside" in msg else capi.UdaError)("%s failed: %s" % (what, msg))
+    al.raise_from_rc(fn(int(device), C.byref(desc), float(min_score), *[p(a) for a in arrays], n, M, num_classes, mcw, strategy.invert,
+                        strategy.gate, tau, int(max_rows), p(rec), C.byref(K), p(minmax), p(kept), p(cand)), lib, what)
     return rec[:K.value].copy(), minmax, kept, cand
 
 
