@@ -32,6 +32,8 @@
  *                            Similarity.calculate_set_similarity (active_learning_eval.py:481-487, 946-1029)
  *   uda_pseudo_audit_np   <- the matching, allocation and by-value tallies of Parent_SSL.extract_pseudo_gt_data and
  *                            _percls_analysis (ssl_utils/parent.py:1567-1813), read by ThreeDproblem.corrected_pseudo (3d.py:80-255)
+ *   uda_uncert_report_np  <- the tallies of ValidUncertPlot.__init__ (utils_extra.py:378-445), RegressionCalib._conf_all
+ *                            (calibrate_regression.py:231-349) and calc_ece / calc_nll / calc_rmse (utils_box.py:17-102)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -636,6 +638,52 @@ int uda_pseudo_audit_np(int32_t device, int32_t B, const double* gt_boxes, const
                         const int64_t* det_off, double gt_iou_thr, double* gt_max_iou, int32_t* gt_best_det, int32_t* gt_alloc_det,
                         uint8_t* gt_flags, double* det_max_iou, int32_t* det_best_gt, int32_t* det_alloc_gt, double* det_alloc_miou,
                         double* det_alloc_pair_iou, uint8_t* det_flags, int32_t* n_matches);
+
+/* Validation uncertainty report: the tallies from which the reference judges a box sigma - the header numbers and the ECE of
+ * ValidUncertPlot.__init__ (utils_extra.py:378-445: % missing detections, misclassification rate, mIoU, RMSE, ECE), the line of
+ * RegressionCalib._conf_all (calibrate_regression.py:231-349: share of rows inside +-sigma, ECE, NLL, RMSUE, sharpness) and
+ * _relative_calc_ece (:46-61) - for B ragged segments of matched rows and K sigma columns in one call, without a handle.  The
+ * divisions, square roots, roundings and the text are the caller's (uncertainty_report.py).
+ *   segments   segment b is rows off[b] .. off[b + 1] of gt [rows, 4], pred [rows, 4], gt_class [rows], cls [rows] (all float64)
+ *              and of every column of sigma [K, rows, 4]; rows = off[B].  A caller makes one segment per class, or one of all rows
+ *   levels     z [L], computed by the caller as norm.ppf((1 - p_m) / 2); for np.linspace(0, 1, 100) z[0] = 0 and z[99] = -inf
+ *   seg_counts [B, 4] int64: n_rows | n_iou_zero, the rows with calc_iou_np(gt, pred) == 0 (utils_box.py:56-89 in float64: (areaA +
+ *              areaB) - inter, 0 where the union is 0; never fused) | n_misclassified, the rows with gt_class != cls |
+ *              n_gt_nonzero, the ELEMENTS with gt != 0 (the mask of calc_rmse)
+ *   col_counts [B, K, 3] int64: covered_all, the rows where all four coordinates have pred - sigma <= gt && gt <= pred + sigma
+ *              (_conf_all:258-265) | n_res_nonzero, the elements with |gt - pred| != 0 (the mask of calc_rmse(residuals, sigma)) |
+ *              n_degenerate, the sigma elements that are 0 or not finite
+ *   ece_count  [B, K, 4, L] int64: for coordinate c and level i the rows with fabs(pred - gt) <= fabs(sigma * z[i]), evaluated
+ *              in IEEE float64 level by level, the product rounded on its own.  NaN rule: a comparison with a NaN is false, as
+ *              in numpy - sigma = 0 with z = -inf, an infinite sigma with z = 0 and a NaN sigma count for nothing.  Nothing is
+ *              inferred from the order of the levels.  emp_conf = count / n and np.mean(np.abs(emp_conf - p_m)) are calc_ece's
+ *              bit for bit, over the four coordinates together for its flattened form
+ *   sums       float64.  Every sum is the root of a perfect binary tree over the segment's per-row terms, the sequence zero-
+ *              padded to a power of two, a node being left + right (numpy: b = b[0::2] + b[1::2] until one value is left); a
+ *              row's term is (t0 + t1) + (t2 + t3) of its four coordinates.  The result does not depend on how rows are dealt
+ *              to waves, blocks or launches.  Apart from the log every operation is one correctly rounded IEEE operation
+ *   seg_sums   [B, 2]: S_iou (a row's term is its IoU) | S_sqerr = sum (pred - gt)^2 [gt != 0]
+ *   col_sums   [B, K, 3]: S_sigma2 = sum sigma^2 | S_ue = sum (sigma - |gt - pred|)^2 [|gt - pred| != 0] | S_nll = sum ((y * y / 2 +
+ *              log(sigma)) + 0.9189385332046727) with y = |gt - pred| / sigma, over the elements that are not degenerate
+ *   degenerate the reference's calc_nll turns sigma = 0 into +-1.8e308 through nan_to_num, an overflow artefact; here an element
+ *              whose sigma is 0 or not finite is left out of S_nll and counted in n_degenerate.  A negative sigma is not
+ *              degenerate: its log is NaN, as scipy's
+ *   empty      an empty segment gives zeros and is not an error
+ *   outputs    caller-allocated; any of them may be NULL
+ *   limits     1 <= B <= UDA_REPORT_MAX_B, 1 <= K <= UDA_REPORT_MAX_K, 1 <= L <= UDA_REPORT_MAX_L, off ascending from 0, at most
+ *              UDA_REPORT_MAX_ROWS rows; off and z not NULL, nor any input array when there are rows.  Anything else is refused
+ *              with a "uda_uncert_report_np: " message, never truncated, and the outputs stay untouched
+ *   scratch    allocated and freed inside the call: the inputs, (80 + 32 K) bytes a row, 16 (B + 1) + 8 L + 12 bytes a run of
+ *              UDA_REPORT_ROWS rows; the results, 8 * B * (6 + K * (6 + 4 L)) bytes; and the run roots, 8 * (2 + 3 K) bytes for
+ *              every slot - a segment has as many slots as runs, rounded up to a power of two. */
+#define UDA_REPORT_ROWS 256          /* rows a block takes: an aligned run counted from the segment's start */
+#define UDA_REPORT_MAX_K 16          /* sigma columns */
+#define UDA_REPORT_MAX_L 128         /* levels */
+#define UDA_REPORT_MAX_B 4096        /* segments */
+#define UDA_REPORT_MAX_ROWS 4194304  /* rows per call, 2^22 */
+int uda_uncert_report_np(int32_t device, int32_t B, int32_t K, int32_t L, const int64_t* off, const double* gt, const double* pred,
+                         const double* gt_class, const double* cls, const double* sigma, const double* z, int64_t* seg_counts,
+                         int64_t* col_counts, int64_t* ece_count, double* seg_sums, double* col_sums);
 
 /* Label correction (GLC): the verdicts of the reference's ground-truth label correction (AdvancedLabels, src/ssl_utils/glc.py) -
  * which ground-truth boxes are mistakes, which detections are missing labels, which noisy boxes are replaced by their detection -

@@ -572,6 +572,36 @@ struct AuditArgs {
 };
 void launch_pseudo_audit(const AuditArgs& a, hipStream_t s);
 
+// validation uncertainty report (reference utils_extra.py:378-445, calibrate_regression.py:231-349, utils_box.py:17-102): B ragged
+// segments of matched rows x K sigma columns (kernels_report.hip).  The host cuts every segment into runs of REPORT_ROWS rows counted
+// from the segment's start; a block takes one (run, column).  Counters meet by integer atomics; a float64 sum is the root of the
+// zero-padded pairwise tree over the segment's rows: the block leaves the root of its run in `partials`, the second kernel folds
+// the segment's runs (padded to a power of two, slots pbase[b] .. pbase[b + 1]) in place.
+enum { REPORT_ROWS = UDA_REPORT_ROWS, REPORT_MAX_L = UDA_REPORT_MAX_L, REPORT_SEG_SUMS = 2, REPORT_COL_SUMS = 3 };
+struct ReportItem {
+  int32_t seg, row0, slot;      // rows [row0, row0 + REPORT_ROWS) of the segment; slot: where its partial sums go
+};
+struct ReportArgs {
+  const double* gt;             // [rows, 4]
+  const double* pred;           // [rows, 4]
+  const double* gt_class;       // [rows]
+  const double* cls;            // [rows]
+  const double* sigma;          // [K, rows, 4]
+  const double* z;              // [L]
+  const int64_t* off;           // [B + 1]
+  const int64_t* pbase;         // [B + 1] first partial slot of a segment; a segment holds a power of two of them, or none
+  const ReportItem* items;      // [n_items]
+  unsigned long long* seg_counts;   // [B, 4]      n_rows (the host's) | n_iou_zero | n_misclassified | n_gt_nonzero
+  unsigned long long* col_counts;   // [B, K, 3]   covered_all | n_res_nonzero | n_degenerate
+  unsigned long long* ece_count;    // [B, K, 4, L]
+  double* seg_sums;             // [B, 2]      S_iou | S_sqerr
+  double* col_sums;             // [B, K, 3]   S_sigma2 | S_ue | S_nll
+  double* partials;             // [2 + 3 K, slots], zeroed
+  int64_t rows, slots;
+  int B, K, L, n_items;
+};
+void launch_uncert_report(const ReportArgs& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

@@ -1,6 +1,6 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
 // COCO matching, the label check and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
-// on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, the pseudo-label audit, uda_nms, uda_debug_pw,
+// on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, the pseudo-label audit, the uncertainty report, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
 //
@@ -1047,6 +1047,71 @@ extern "C" int uda_pseudo_audit_np(int32_t device, int32_t B, const double* gt_b
   s.download(det_flags, a.det_flags, det_flags ? ND : 0);
   s.download(n_matches, a.n_matches, n_matches ? (size_t)B * sizeof(int32_t) : 0);
   return scratch_done(nullptr, who, s);
+}
+
+// the validation uncertainty report: B ragged segments x K sigma columns in, two launches (run x column blocks, then the fold of
+// the run roots), the results in ONE zeroed device allocation; its own allocations
+extern "C" int uda_uncert_report_np(int32_t device, int32_t B, int32_t K, int32_t L, const int64_t* off, const double* gt,
+                                    const double* pred, const double* gt_class, const double* cls, const double* sigma,
+                                    const double* z, int64_t* seg_counts, int64_t* col_counts, int64_t* ece_count, double* seg_sums,
+                                    double* col_sums) {
+  const char* who = "uda_uncert_report_np";
+  if (B < 1 || B > UDA_REPORT_MAX_B) return fail(nullptr, "%s: %d segments, 1..%d are taken", who, B, (int)UDA_REPORT_MAX_B);
+  if (K < 1 || K > UDA_REPORT_MAX_K) return fail(nullptr, "%s: %d sigma columns, 1..%d are taken", who, K, (int)UDA_REPORT_MAX_K);
+  if (L < 1 || L > UDA_REPORT_MAX_L) return fail(nullptr, "%s: %d levels, 1..%d are taken", who, L, (int)UDA_REPORT_MAX_L);
+  if (!off || !z) return fail(nullptr, "%s: NULL offsets or levels", who);
+  if (off[0] != 0) return fail(nullptr, "%s: offsets start at %lld, not at 0", who, (long long)off[0]);
+  for (int b = 0; b < B; ++b) {
+    if (off[b + 1] < off[b]) return fail(nullptr, "%s: the offsets of segment %d do not ascend", who, b);
+    if (off[b + 1] > UDA_REPORT_MAX_ROWS)
+      return fail(nullptr, "%s: %lld rows up to segment %d, at most %d a call", who, (long long)off[b + 1], b, (int)UDA_REPORT_MAX_ROWS);
+  }
+  const size_t rows = (size_t)off[B];
+  if (rows && (!gt || !pred || !gt_class || !cls || !sigma)) return fail(nullptr, "%s: NULL input array", who);
+  // the runs of every segment and where their roots go: a segment holds a power of two of slots, an empty one none
+  std::vector<int64_t> pbase((size_t)B + 1, 0);
+  std::vector<ReportItem> items;
+  items.reserve(rows / REPORT_ROWS + (size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = off[b + 1] - off[b], runs = (n + REPORT_ROWS - 1) / REPORT_ROWS;
+    int64_t slots = runs ? 1 : 0;
+    while (slots < runs) slots <<= 1;
+    for (int64_t r = 0; r < runs; ++r) items.push_back(ReportItem{b, (int32_t)(r * REPORT_ROWS), (int32_t)(pbase[b] + r)});
+    pbase[b + 1] = pbase[b] + slots;
+  }
+  const size_t n_sums = REPORT_SEG_SUMS + (size_t)REPORT_COL_SUMS * K;
+  const size_t n_seg = (size_t)B * 4, n_col = (size_t)B * K * 3, n_ece = (size_t)B * K * 4 * L, n_ssum = (size_t)B * REPORT_SEG_SUMS,
+               n_csum = (size_t)B * K * REPORT_COL_SUMS;
+  DevScratch s(device);
+  ReportArgs a{};
+  a.B = B; a.K = K; a.L = L; a.n_items = (int)items.size(); a.rows = (int64_t)rows; a.slots = pbase[B];
+  a.gt = s.upload(gt, rows * 4); a.pred = s.upload(pred, rows * 4);
+  a.gt_class = s.upload(gt_class, rows); a.cls = s.upload(cls, rows);
+  a.sigma = s.upload(sigma, rows * 4 * K); a.z = s.upload(z, (size_t)L);
+  a.off = s.upload(off, (size_t)B + 1); a.pbase = s.upload(pbase.data(), pbase.size());
+  a.items = s.upload(items.data(), items.size());
+  // int64 seg_counts | col_counts | ece_count, then float64 seg_sums | col_sums: zeroed, so that an empty segment reads zeros
+  unsigned long long* pack = s.alloc<unsigned long long>(n_seg + n_col + n_ece + n_ssum + n_csum);
+  a.partials = s.alloc<double>(n_sums * (size_t)a.slots);
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  s.zero(pack, (n_seg + n_col + n_ece + n_ssum + n_csum) * sizeof(double));
+  s.zero(a.partials, std::max<size_t>(n_sums * (size_t)a.slots, 1) * sizeof(double));
+  a.seg_counts = pack; a.col_counts = pack + n_seg; a.ece_count = a.col_counts + n_col;
+  a.seg_sums = (double*)(a.ece_count + n_ece); a.col_sums = a.seg_sums + n_ssum;
+  if (s.ok()) launch_uncert_report(a, nullptr);
+  s.sync();
+  std::vector<int64_t> h_seg(seg_counts ? n_seg : 0);
+  s.download(h_seg.data(), a.seg_counts, h_seg.size() * sizeof(int64_t));
+  s.download(col_counts, a.col_counts, col_counts ? n_col * sizeof(int64_t) : 0);
+  s.download(ece_count, a.ece_count, ece_count ? n_ece * sizeof(int64_t) : 0);
+  s.download(seg_sums, a.seg_sums, seg_sums ? n_ssum * sizeof(double) : 0);
+  s.download(col_sums, a.col_sums, col_sums ? n_csum * sizeof(double) : 0);
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  for (int b = 0; seg_counts && b < B; ++b) {                  // n_rows is the host's: the offsets say it
+    h_seg[(size_t)b * 4] = off[b + 1] - off[b];
+    memcpy(seg_counts + (size_t)b * 4, h_seg.data() + (size_t)b * 4, 4 * sizeof(int64_t));
+  }
+  return 0;
 }
 
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,

@@ -240,7 +240,7 @@ def model_performance(filtered):
 
 
 def validate_to_file(driver, batches, gts, names, out_dir, box_calibrator=None, class_calibrator=None, occlusions=None,
-                     truncations=None):
+                     truncations=None, uncert_report=False):
     """The loop of `Validate.launch_val` (validate_model.py:472-735) without its `infer_augment` branches, over batches
     of images: serve (feed of the next batch hidden under this one, as in `predict_to_file`) -> ground-truth assignment on
     the resident detections (`ServingDriver.assign_ground_truth`, method model_params["assign_gt_box"]) -> calibrated
@@ -251,7 +251,11 @@ def validate_to_file(driver, batches, gts, names, out_dir, box_calibrator=None, 
       validationstep_runtime.txt    `summarize_runtimes` of the per-image serve time (batch time / images, the assignment
                                     and the writing excluded, as the reference times serve() alone, :154-158)
       model_performance.txt         only without box uncertainty (no MC box dropout, no loss attenuation), as the reference
-                                    (:706-735); `model_performance`
+                                    (:706-735); `model_performance`.  With `uncert_report` and box uncertainty: the
+                                    lines `ValidUncertPlot.__init__` appends instead (:736-794, utils_extra.py:417-445),
+                                    aleatoric first, of the second kind the ECE line alone (the file exists by then, as
+                                    it does for both kinds when a previous run left one) - `uncertainty_report`, one
+                                    device call over the matched rows; the report is returned as filtered["uncert_report"]
 
     gts: per batch (gt_boxes [n, G, 4], gt_classes [n, G]); names: per batch the n image file names; occlusions /
     truncations: per batch [n, G] label fields (None: written as 0).  Returns the matched-row arrays (`filtered`)."""
@@ -317,6 +321,16 @@ def validate_to_file(driver, batches, gts, names, out_dir, box_calibrator=None, 
         with open(os.path.join(out_dir, "model_performance.txt"), "w") as f:
             f.writelines(model_performance(filtered))
     filtered["calibrated"] = cal
+    if uncert_report and ((p.get("mc_boxheadrate") or p.get("mc_dropoutrate")) or p.get("loss_attenuation")):
+        from . import uncertainty_report
+        rep = uncertainty_report.from_filtered(filtered, calibrated=True, device=getattr(driver, "device", 0))
+        path = os.path.join(out_dir, "model_performance.txt")
+        for which, has in (("aleatoric", p.get("loss_attenuation")), ("mcdropout", p.get("mc_boxheadrate") or p.get("mc_dropoutrate"))):
+            if has:
+                lines = uncertainty_report.model_performance_lines(rep, which, p["uncert_adjust_method"], exists=os.path.exists(path))
+                with open(path, "a") as f:
+                    f.writelines(lines)
+        filtered["uncert_report"] = rep
     return filtered
 
 
