@@ -34,6 +34,8 @@
  *                            _percls_analysis (ssl_utils/parent.py:1567-1813), read by ThreeDproblem.corrected_pseudo (3d.py:80-255)
  *   uda_uncert_report_np  <- the tallies of ValidUncertPlot.__init__ (utils_extra.py:378-445), RegressionCalib._conf_all
  *                            (calibrate_regression.py:231-349) and calc_ece / calc_nll / calc_rmse (utils_box.py:17-102)
+ *   uda_class_report_np   <- the reliability bins, Brier and NLL sums of ClassificationCalib._calibr_bins and _calibr_plot
+ *                            (calibrate_classification.py:97-143, 250-440)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -684,6 +686,63 @@ int uda_pseudo_audit_np(int32_t device, int32_t B, const double* gt_boxes, const
 int uda_uncert_report_np(int32_t device, int32_t B, int32_t K, int32_t L, const int64_t* off, const double* gt, const double* pred,
                          const double* gt_class, const double* cls, const double* sigma, const double* z, int64_t* seg_counts,
                          int64_t* col_counts, int64_t* ece_count, double* seg_sums, double* col_sums);
+
+/* Classification calibration report: the tallies from which the reference draws its reliability diagrams and their titles -
+ * ClassificationCalib._calibr_bins (calibrate_classification.py:97-143) as _calibr_plot calls it (:250-440), once per class and once
+ * over the arg-max class, with ECE, MCE, Brier, NLL and SCE - for B ragged segments of rows, M probability tables (one per
+ * configuration: uncalibrated, TS all, TS per class, isotonic all, isotonic per class) and all C + 1 targets in one call, without a
+ * handle.  The divisions, roundings and the text are the caller's (class_report.py).
+ *   segments   segment b is rows off[b] .. off[b + 1] of label [rows] (int32, the true class index: the reference's one-hot y_true
+ *              is eye(C)[label]) and of every table of prob [M, rows, C] (float64); rows = off[B].  A caller makes one segment of the
+ *              reference's 20 % evaluation split, or one per shard
+ *   edges      [G, E] float64 with n_edges [G]: row g holds n_edges[g] strictly ascending edges, free of NaN (the rest of the row is
+ *              not read).  G = 1: every target bins with row 0 (the reference's np.linspace(0, 1 + 1e-8, 11)); G = B * M * (C + 1):
+ *              target t of table m of segment b bins with row (b * M + m) * (C + 1) + t (the quantile strategy; np.quantile and
+ *              np.unique are the caller's)
+ *   targets    t < C is class t: ypred = prob[m, i, t], ytrue = (label[i] == t).  t = C is the all_classes branch: a = the first
+ *              index of row i that holds a NaN if there is one, else the first maximum (numpy.argmax); ypred = prob[m, i, a],
+ *              ytrue = (label[i] == a)
+ *   bin id     the number of edges e with !(ypred < e): np.digitize(ypred, edges) for ascending edges; a NaN lands in id n_edges.
+ *              Ids run 0 .. n_edges, a (segment, table, target) has E + 1 slots; slots past n_edges stay 0.  The reference raises an
+ *              IndexError when id n_edges is populated (a value at or above the last edge, or a NaN); here it is counted, and the
+ *              caller decides
+ *   bin_count  [B, M, C + 1, E + 1] int64: the rows of the bin
+ *   bin_hits   [B, M, C + 1, E + 1] int64: the rows of the bin with ytrue set
+ *   bin_sum    [B, M, C + 1, E + 1] float64: sum ypred over the bin
+ *   brier_sum  [B, M, C] float64: sum (prob[m, i, t] - y)^2 with y = 1.0 or 0.0
+ *   nll_sum    [B, M] float64: the row term of Keras's CategoricalCrossentropy() on probabilities, restated from Keras's backend
+ *              (categorical_crossentropy, from_logits=False: output /= reduce_sum(output, axis); output = clip_by_value(output,
+ *              epsilon, 1 - epsilon) with epsilon = 1e-7; -reduce_sum(target * log(output))) for a one-hot target, in float64 where
+ *              TensorFlow would use the tensors' dtype: q = prob[m, i, label[i]] / rowsum, rowsum added left to right in class
+ *              order from 0.0; q clipped to [1e-7, 1 - 1e-7]; the term is -log(q).  A row that holds a non-finite entry, or whose
+ *              rowsum is 0, is left out of the sum.  The reference's UNCALIBRATED self.nll feeds logits to this loss, which expects
+ *              probabilities: that is not reproduced - every table here holds probabilities
+ *   tab_counts [B, M, 2] int64: the rows whose q was clipped | the rows left out of nll_sum
+ *   sums       every float64 sum is the root of the tree uda_uncert_report_np documents, over the segment's rows with +0.0 as the
+ *              term of a row outside the bin (or left out): the sequence zero-padded to a power of two, a node being left + right
+ *              (numpy: b = b[0::2] + b[1::2] until one value is left), runs of UDA_CLASSREP_ROWS rows counted from the segment's
+ *              start.  The result does not depend on how rows are dealt to waves, blocks or launches.  Apart from the log every
+ *              operation is one correctly rounded IEEE operation, never fused.  Counts and hits are integer tallies (wave ballots,
+ *              integer atomics); there are no floating-point atomics
+ *   empty      an empty segment gives zeros and is not an error
+ *   outputs    caller-allocated; any of them may be NULL
+ *   limits     1 <= B <= UDA_CLASSREP_MAX_B, 1 <= M <= UDA_CLASSREP_MAX_M, 1 <= C <= UDA_CLASSREP_MAX_C, 2 <= n_edges[g] <= E <=
+ *              UDA_CLASSREP_MAX_E, G as above, off ascending from 0, at most UDA_CLASSREP_MAX_ROWS rows, every label in [0, C); off,
+ *              edges and n_edges not NULL, nor prob and label when there are rows.  Anything else is refused with a
+ *              "uda_class_report_np: " message, never truncated, and the outputs stay untouched
+ *   scratch    allocated and freed inside the call: the inputs, (8 M C + 4) bytes a row, 8 E + 4 bytes an edge row, 16 (B + 1) bytes,
+ *              12 bytes a run and 4 bytes a segment of more than one run; the results, 8 * B * M * (3 (C + 1) (E + 1) + C + 3) bytes; and, for the segments of more than
+ *              one run only, the run roots: 8 * M * ((C + 1) (E + 1) + C + 1) bytes for every slot - such a segment has as many
+ *              slots as runs, rounded up to a power of two. */
+#define UDA_CLASSREP_ROWS 256          /* rows a block takes: an aligned run counted from the segment's start */
+#define UDA_CLASSREP_MAX_B 4096        /* segments */
+#define UDA_CLASSREP_MAX_M 8           /* probability tables */
+#define UDA_CLASSREP_MAX_C 128         /* classes */
+#define UDA_CLASSREP_MAX_E 64          /* edges a row */
+#define UDA_CLASSREP_MAX_ROWS 4194304  /* rows per call, 2^22 */
+int uda_class_report_np(int32_t device, int32_t B, int32_t M, int32_t C, int32_t G, int32_t E, const int64_t* off, const double* prob,
+                        const int32_t* label, const double* edges, const int32_t* n_edges, int64_t* bin_count, int64_t* bin_hits,
+                        double* bin_sum, double* brier_sum, double* nll_sum, int64_t* tab_counts);
 
 /* Label correction (GLC): the verdicts of the reference's ground-truth label correction (AdvancedLabels, src/ssl_utils/glc.py) -
  * which ground-truth boxes are mistakes, which detections are missing labels, which noisy boxes are replaced by their detection -

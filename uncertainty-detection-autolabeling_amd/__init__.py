@@ -11,5 +11,6 @@ Modules:
   dist            image sharding + detection gather (torch.distributed / RCCL)
   pseudo_labels   the STAC teacher's selection: candidate rows from the device, dataset-wide rule, KITTI / BDD pseudo ground truth
   uncertainty_report  the validation uncertainty report: ECE, NLL, coverage, RMSUE, sharpness of every sigma column from one device call
+  class_report    the classification calibration report: reliability bins, ECE, MCE, Brier, NLL, SCE of every probability table from one device call
   thresholding    failure-recognition weights and threshold from validation rows (roc_objective, UncertOptimal, autolabel_verdict)
 """

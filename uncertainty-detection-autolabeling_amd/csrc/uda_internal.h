@@ -602,6 +602,37 @@ struct ReportArgs {
 };
 void launch_uncert_report(const ReportArgs& a, hipStream_t s);
 
+// classification calibration report (reference calibrate_classification.py:97-143, 250-440): B ragged segments of rows x M probability
+// tables x (C + 1) targets (kernels_classrep.hip).  The host cuts every segment into runs of CLASSREP_ROWS rows counted from the
+// segment's start; a block takes one (run, table) and walks the targets.  Counters meet by integer atomics; a float64 sum is the root
+// of the zero-padded pairwise tree over the segment's rows: the block of a segment of ONE run writes the output itself (slot < 0), a
+// block of a longer segment leaves the root of its run in `partials` and the second kernel folds the segment's runs (padded to a
+// power of two, slots pbase[b] .. pbase[b + 1]; none for a segment of at most one run) in place.
+enum { CLASSREP_ROWS = UDA_CLASSREP_ROWS, CLASSREP_MAX_E = UDA_CLASSREP_MAX_E };
+struct ClassRepItem {
+  int32_t seg, row0, slot;      // rows [row0, row0 + CLASSREP_ROWS) of the segment; slot: where its partial sums go, -1: to the outputs
+};
+struct ClassRepArgs {
+  const double* prob;           // [M, rows, C]
+  const int32_t* label;         // [rows]
+  const double* edges;          // [G, E]
+  const int32_t* n_edges;       // [G]
+  const int64_t* off;           // [B + 1]
+  const int64_t* pbase;         // [B + 1] first partial slot of a segment
+  const int32_t* tree_segs;     // [n_tree] the segments of more than one run
+  const ClassRepItem* items;    // [n_items]
+  unsigned long long* bin_count;    // [B, M, C + 1, E + 1]
+  unsigned long long* bin_hits;     // [B, M, C + 1, E + 1]
+  unsigned long long* tab_counts;   // [B, M, 2]   rows whose q was clipped | rows left out of the NLL
+  double* bin_sum;              // [B, M, C + 1, E + 1]
+  double* brier_sum;            // [B, M, C]
+  double* nll_sum;              // [B, M]
+  double* partials;             // [M * ((C + 1) * (E + 1) + C + 1), slots], zeroed
+  int64_t rows, slots;
+  int B, M, C, G, E, n_items, n_tree;
+};
+void launch_class_report(const ClassRepArgs& a, hipStream_t s);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

@@ -1,6 +1,6 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
 // COCO matching, the label check and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
-// on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, the pseudo-label audit, the uncertainty report, uda_nms, uda_debug_pw,
+// on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, the pseudo-label audit, the uncertainty report, the classification report, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
 //
@@ -1112,6 +1112,84 @@ extern "C" int uda_uncert_report_np(int32_t device, int32_t B, int32_t K, int32_
     memcpy(seg_counts + (size_t)b * 4, h_seg.data() + (size_t)b * 4, 4 * sizeof(int64_t));
   }
   return 0;
+}
+
+// the classification calibration report: B ragged segments x M probability tables in, two launches (run x table blocks that walk
+// the C + 1 targets, then the fold of the run roots of the segments of more than one run), the results in ONE zeroed device
+// allocation; its own allocations
+extern "C" int uda_class_report_np(int32_t device, int32_t B, int32_t M, int32_t C, int32_t G, int32_t E, const int64_t* off,
+                                   const double* prob, const int32_t* label, const double* edges, const int32_t* n_edges,
+                                   int64_t* bin_count, int64_t* bin_hits, double* bin_sum, double* brier_sum, double* nll_sum,
+                                   int64_t* tab_counts) {
+  const char* who = "uda_class_report_np";
+  if (B < 1 || B > UDA_CLASSREP_MAX_B) return fail(nullptr, "%s: %d segments, 1..%d are taken", who, B, (int)UDA_CLASSREP_MAX_B);
+  if (M < 1 || M > UDA_CLASSREP_MAX_M) return fail(nullptr, "%s: %d probability tables, 1..%d are taken", who, M, (int)UDA_CLASSREP_MAX_M);
+  if (C < 1 || C > UDA_CLASSREP_MAX_C) return fail(nullptr, "%s: %d classes, 1..%d are taken", who, C, (int)UDA_CLASSREP_MAX_C);
+  if (E < 2 || E > UDA_CLASSREP_MAX_E) return fail(nullptr, "%s: %d edges a row, 2..%d are taken", who, E, (int)UDA_CLASSREP_MAX_E);
+  const int64_t G_each = (int64_t)B * M * (C + 1);
+  if (G != 1 && G != G_each)
+    return fail(nullptr, "%s: %d edge rows, 1 (shared) or B * M * (C + 1) = %lld (one a target) are taken", who, G, (long long)G_each);
+  if (!off || !edges || !n_edges) return fail(nullptr, "%s: NULL offsets or edges", who);
+  if (off[0] != 0) return fail(nullptr, "%s: offsets start at %lld, not at 0", who, (long long)off[0]);
+  for (int b = 0; b < B; ++b) {
+    if (off[b + 1] < off[b]) return fail(nullptr, "%s: the offsets of segment %d do not ascend", who, b);
+    if (off[b + 1] > UDA_CLASSREP_MAX_ROWS)
+      return fail(nullptr, "%s: %lld rows up to segment %d, at most %d a call", who, (long long)off[b + 1], b, (int)UDA_CLASSREP_MAX_ROWS);
+  }
+  for (int g = 0; g < G; ++g) {
+    const double* e = edges + (size_t)g * E;
+    if (n_edges[g] < 2 || n_edges[g] > E) return fail(nullptr, "%s: edge row %d holds %d edges, 2..%d are taken", who, g, n_edges[g], E);
+    for (int i = 0; i + 1 < n_edges[g]; ++i)                    // (a NaN fails the comparison too)
+      if (!(e[i] < e[i + 1])) return fail(nullptr, "%s: the edges of row %d do not ascend strictly at %d (or hold a NaN)", who, g, i);
+  }
+  const size_t rows = (size_t)off[B];
+  if (rows && (!prob || !label)) return fail(nullptr, "%s: NULL input array", who);
+  for (size_t i = 0; i < rows; ++i)
+    if (label[i] < 0 || label[i] >= C) return fail(nullptr, "%s: the label of row %lld is %d, outside 0..%d", who, (long long)i, label[i], C - 1);
+  // the runs of every segment and where their roots go: a segment of more than one run holds a power of two of slots
+  std::vector<int64_t> pbase((size_t)B + 1, 0);
+  std::vector<int32_t> tree_segs;
+  std::vector<ClassRepItem> items;
+  items.reserve(rows / CLASSREP_ROWS + (size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = off[b + 1] - off[b], runs = (n + CLASSREP_ROWS - 1) / CLASSREP_ROWS;
+    int64_t slots = runs > 1 ? 2 : 0;
+    while (slots && slots < runs) slots <<= 1;
+    for (int64_t r = 0; r < runs; ++r)
+      items.push_back(ClassRepItem{b, (int32_t)(r * CLASSREP_ROWS), runs > 1 ? (int32_t)(pbase[b] + r) : -1});
+    if (runs > 1) tree_segs.push_back(b);
+    pbase[b + 1] = pbase[b] + slots;
+  }
+  const size_t S = (size_t)(C + 1) * (E + 1) + C + 1;
+  const size_t n_bin = (size_t)B * M * (C + 1) * (E + 1), n_tab = (size_t)B * M * 2, n_bri = (size_t)B * M * C, n_nll = (size_t)B * M;
+  DevScratch s(device);
+  ClassRepArgs a{};
+  a.B = B; a.M = M; a.C = C; a.G = G; a.E = E; a.n_items = (int)items.size(); a.n_tree = (int)tree_segs.size();
+  a.rows = (int64_t)rows; a.slots = pbase[B];
+  a.prob = s.upload(prob, rows * (size_t)C * M); a.label = s.upload(label, rows);
+  a.edges = s.upload(edges, (size_t)G * E); a.n_edges = s.upload(n_edges, (size_t)G);
+  a.off = s.upload(off, (size_t)B + 1); a.pbase = s.upload(pbase.data(), pbase.size());
+  a.tree_segs = s.upload(tree_segs.data(), tree_segs.size()); a.items = s.upload(items.data(), items.size());
+  // int64 bin_count | bin_hits | tab_counts, then float64 bin_sum | brier_sum | nll_sum: zeroed, so that an empty segment and a bin
+  // slot past a row's edges read zeros
+  const size_t n_pack = 3 * n_bin + n_tab + n_bri + n_nll;
+  unsigned long long* pack = s.alloc<unsigned long long>(n_pack);
+  a.partials = s.alloc<double>(M * S * (size_t)a.slots);
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  s.zero(pack, n_pack * sizeof(double));
+  s.zero(a.partials, std::max<size_t>(M * S * (size_t)a.slots, 1) * sizeof(double));
+  a.bin_count = pack; a.bin_hits = pack + n_bin; a.tab_counts = a.bin_hits + n_bin;
+  a.bin_sum = (double*)(a.tab_counts + n_tab); a.brier_sum = a.bin_sum + n_bin; a.nll_sum = a.brier_sum + n_bri;
+  if (s.ok()) launch_class_report(a, nullptr);
+  s.sync();
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  s.download(bin_count, a.bin_count, bin_count ? n_bin * sizeof(int64_t) : 0);
+  s.download(bin_hits, a.bin_hits, bin_hits ? n_bin * sizeof(int64_t) : 0);
+  s.download(tab_counts, a.tab_counts, tab_counts ? n_tab * sizeof(int64_t) : 0);
+  s.download(bin_sum, a.bin_sum, bin_sum ? n_bin * sizeof(double) : 0);
+  s.download(brier_sum, a.brier_sum, brier_sum ? n_bri * sizeof(double) : 0);
+  s.download(nll_sum, a.nll_sum, nll_sum ? n_nll * sizeof(double) : 0);
+  return scratch_done(nullptr, who, s);
 }
 
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,

@@ -26,8 +26,8 @@ here an element whose sigma is 0 or not finite is left out of the NLL (sum and d
 reference squares in float32 for the sharpness and takes the RMSE as a TensorFlow reduction of unpinned order - here both are
 float64 sums of a stated order, the sharpness rounded to float32 at the end.
 
-Not built: the plots, the uncertainty_toolbox metrics block (`uct.metrics.get_all_metrics`), the PIT / CDF scatter of `_cdf`, the
-classification reliability bins (`_calibr_bins`) and the fitting of calibrators.
+Not built: the plots, the uncertainty_toolbox metrics block (`uct.metrics.get_all_metrics`), the PIT / CDF scatter of `_cdf` and
+the fitting of calibrators.  The classification reliability bins (`_calibr_bins`) are `class_report`.
 """
 import numpy as np
 

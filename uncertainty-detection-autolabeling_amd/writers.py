@@ -240,7 +240,7 @@ def model_performance(filtered):
 
 
 def validate_to_file(driver, batches, gts, names, out_dir, box_calibrator=None, class_calibrator=None, occlusions=None,
-                     truncations=None, uncert_report=False):
+                     truncations=None, class_report=None, uncert_report=False):
     """The loop of `Validate.launch_val` (validate_model.py:472-735) without its `infer_augment` branches, over batches
     of images: serve (feed of the next batch hidden under this one, as in `predict_to_file`) -> ground-truth assignment on
     the resident detections (`ServingDriver.assign_ground_truth`, method model_params["assign_gt_box"]) -> calibrated
@@ -258,7 +258,12 @@ def validate_to_file(driver, batches, gts, names, out_dir, box_calibrator=None, 
                                     device call over the matched rows; the report is returned as filtered["uncert_report"]
 
     gts: per batch (gt_boxes [n, G, 4], gt_classes [n, G]); names: per batch the n image file names; occlusions /
-    truncations: per batch [n, G] label fields (None: written as 0).  Returns the matched-row arrays (`filtered`)."""
+    truncations: per batch [n, G] label fields (None: written as 0).  Returns the matched-row arrays (`filtered`).
+
+    class_report: None (default: nothing changes), or the models dict a `ClassCalibrator` takes ({}: the uncalibrated table
+    alone) - then filtered["class_report"] is the classification calibration report of ALL matched rows (`class_report.
+    from_filtered(filtered, models, split=0, one_based=True)`: reliability bins, ECE, MCE, Brier, NLL, SCE of every table from
+    one device call; the models were fitted elsewhere, so no row is held back).  No file is written for it."""
     import os
     import time
     p = driver.params
@@ -331,6 +336,10 @@ def validate_to_file(driver, batches, gts, names, out_dir, box_calibrator=None, 
                 with open(path, "a") as f:
                     f.writelines(lines)
         filtered["uncert_report"] = rep
+    if class_report is not None:
+        from . import class_report as class_report_mod
+        filtered["class_report"] = class_report_mod.from_filtered(filtered, class_report, split=0, one_based=True,
+                                                                  device=getattr(driver, "device", 0))
     return filtered
 
 
