@@ -26,6 +26,8 @@
  *                            collects (custom_cocoeval.py:265-349; coco_metric.py:219-283)
  *   uda_thr_objective_np  <- roc_metrics for the candidates of UncertOptimal._extract_optimal_params
  *                            (uncertainty_analysis.py:44-152)
+ *   uda_thr_report_np     <- the curves, calc_jsd moments and removal counts of MainUncertViz._save_thr_performance and
+ *                            _collect_thresh_results (uncertainty_analysis.py:517-749; utils_extra.py:25-36)
  *   uda_hash_neighbors_np <- the distance matrix, its maximum and the rows of near-duplicates of
  *                            ActiveLearning.extract_hash_matrix (active_learning_loop.py:240-270)
  *   uda_nn_dist2_np       <- the four KD-tree queries of emp_KL_divergence for every (class, method) of
@@ -543,6 +545,44 @@ int uda_eval_match_np(int32_t device, const float* det_rows, const float* gt, in
 int uda_thr_objective_np(int32_t device, const double* uncerts, const double* ious, const uint8_t* tp_class, const int32_t* group,
                          int32_t N, int32_t U, int32_t G, const double* iou_thrs, int32_t K, const double* params, int32_t P,
                          int32_t fix_cd, double budget, double* thr, double* rate, double* auc);
+
+/* Thresholding report: the judgement the reference makes of a failure-recognition score right after the search
+ * (MainUncertViz._save_thr_performance / _collect_thresh_results, uncertainty_analysis.py:517-749, with calc_jsd,
+ * utils_extra.py:25-36) for B segments of rows x S ready score columns x K IoU thresholds in one call, without a handle.  Host
+ * arrays: scores [S, N] float64 (the caller forms the combinations), ious [N] float64, tp_class [N] uint8, iou_thrs [K], seg_lo /
+ * seg_hi [B] int32: the half-open row ranges [lo, hi) with 0 <= lo <= hi <= N, which may nest, overlap or repeat (the Python layer
+ * orders the rows by class, so "all rows" and every class are ranges).  Outputs, in the order the segments were given, any may be
+ * NULL:
+ *   roc        [B, S, K, 3] float64: thr, rate, auc of roc_metrics(scores[s, lo:hi], correct[lo:hi]) with exactly the semantics
+ *              stated for uda_thr_objective_np (labels, pos_label 0, drop_intermediate, numpy.interp, the first argmin, -0.0 as
+ *              0.0, the same kernels).  A segment of 0 or 1 rows, or with one label only, gives +inf, NaN, NaN
+ *   n_label    [B, K, 2] int64: rows of the segment with correct, rows without
+ *   moments    [B, S, K, 2, 2] float64: for the correct rows and for the wrong rows (sum, m2).  sum is the root of the tree
+ *              uda_uncert_report_np documents over the segment's rows counted from lo (numpy: b = b[0::2] + b[1::2] over the terms
+ *              zero-padded to a power of two, until one value is left); a row outside the subset contributes +0.0 and -0.0 counts
+ *              as 0.0.  m2 is the same tree over (u - mean)^2 with mean = sum / n, one IEEE division done on the device, n the
+ *              subset's size; the subtraction and the product are rounded on their own.  An empty subset gives 0, 0.  The caller
+ *              takes std = sqrt(m2 / n)
+ *   removed    [B, S, K, 3] int64, against the thr of the same (b, s, k): wrong && u >= thr (correctly removed), correct &&
+ *              u >= thr (falsely removed), wrong && u < thr (falsely remaining).  With thr = +inf nothing is removed.  Wave
+ *              ballots and popcounts; no atomics anywhere
+ *   limits     2 <= N <= UDA_THR_MAX_N, 1 <= S <= UDA_THR_REPORT_MAX_S, 1 <= K <= UDA_THR_MAX_THRS, 1 <= B <=
+ *              UDA_THR_REPORT_MAX_SEGS, ranges inside [0, N], budget strictly between 0 and 1; anything else is refused with a
+ *              "uda_thr_report_np: " message, never truncated, and the outputs stay untouched.  Values must be finite (the Python
+ *              layer checks)
+ *   cost       one upload, one download, no host synchronisation between segments.  Launches are linear in B: per segment of
+ *              n >= 2 rows the objective's sort and curve launches for ceil(S / chunk) chunks of columns, then one launch of
+ *              B * S * K blocks for counts and moments
+ *   scratch    allocated and freed inside the call.  With n the longest segment and Npad = max(2048, n rounded up to a power of
+ *              two) one column takes 12 * Npad + 8 * n * K bytes of sort and curve scratch, shared by all segments; a chunk is as
+ *              many columns as fit 64 MiB (at least one, which takes 70 MiB at the limits): never above 70 MiB whatever B and S
+ *              are.  On top: the inputs, 8 * N * (S + 1) + N + 8 * S * S + 8 * B bytes, the mask, 4 * N, and the outputs,
+ *              80 * B * S * K + 16 * B * K. */
+#define UDA_THR_REPORT_MAX_S 8
+#define UDA_THR_REPORT_MAX_SEGS 16384
+int uda_thr_report_np(int32_t device, const double* scores, const double* ious, const uint8_t* tp_class, int32_t N, int32_t S,
+                      const double* iou_thrs, int32_t K, const int32_t* seg_lo, const int32_t* seg_hi, int32_t B, int32_t fix_cd,
+                      double budget, double* roc, int64_t* n_label, double* moments, int64_t* removed);
 
 /* Dataset pruning: the quadratic part of the active-learning loop's `prune` strategies (ActiveLearning.extract_hash_matrix,
  * active_learning_loop.py:198-316) - for N image hashes the maximum Hamming distance over all pairs and, per image, the images

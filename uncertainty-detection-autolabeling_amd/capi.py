@@ -33,6 +33,7 @@ SCORE_MAX_COMP = 3
 PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS, PROF_SCORE, PROF_EVAL, PROF_PSEUDO = 16, 17, 18, 19, 20, 21
 EVAL_MAX_GT, EVAL_MAX_THRS = 256, 32
 THR_MAX_N, THR_MAX_U, THR_MAX_THRS, THR_MAX_P, THR_MAX_G = 262144, 4, 32, 65536, 8192
+THR_REPORT_MAX_S, THR_REPORT_MAX_SEGS = 8, 16384
 PRUNE_ROWS, PRUNE_COLS, PRUNE_MAX_N, PRUNE_MAX_W = 256, 512, 1048576, 4
 KNN_ROWS, KNN_COLS, KNN_MAX_D, KNN_MAX_N, KNN_MAX_B, KNN_MAX_PAIRS = 256, 512, 4, 1048576, 4096, 1 << 38
 LC_MD, LC_MISTAKES, LC_NOISY = 1, 2, 4
@@ -160,6 +161,8 @@ _SIGNATURES = {
     "uda_eval_match_np": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "uda_thr_objective_np": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32,
                                        C.c_int32, C.c_double, _P, _P, _P]),
+    "uda_thr_report_np": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32,
+                                    C.c_double, _P, _P, _P, _P]),
     "uda_hash_neighbors_np": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                         _P, _P, C.POINTER(C.c_int64)]),
     "uda_nn_dist2_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

@@ -820,6 +820,7 @@ __global__ void __launch_bounds__(THR_SORT_THREADS) thr_sort_tile_kernel(ThrArgs
   __shared__ int32_t si[THR_TILE];
   const int base = blockIdx.x * THR_TILE, p = blockIdx.y;
   const int stride = a.U * (a.G > 0 ? a.G : 1);
+  const size_t ld = a.ld ? (size_t)a.ld : (size_t)a.N;
   const double* w = a.params + (size_t)p * stride;
   for (int e = threadIdx.x; e < THR_TILE; e += THR_SORT_THREADS) {
     const int i = base + e;
@@ -827,7 +828,7 @@ __global__ void __launch_bounds__(THR_SORT_THREADS) thr_sort_tile_kernel(ThrArgs
     if (i < a.N) {
       const double* wi = a.group ? w + (size_t)a.group[i] * a.U : w;
       double u = __dmul_rn(wi[0], a.uncerts[i]);          // every product rounded on its own: a fused one moves the ties
-      for (int j = 1; j < a.U; ++j) u = __dadd_rn(u, __dmul_rn(wi[j], a.uncerts[(size_t)j * a.N + i]));
+      for (int j = 1; j < a.U; ++j) u = __dadd_rn(u, __dmul_rn(wi[j], a.uncerts[(size_t)j * ld + i]));
       key = thr_key_of(u);
     }
     sk[e] = key;

@@ -462,7 +462,7 @@ void launch_coco_match(const CocoMatchArgs& a, hipStream_t s);
 enum { THR_MAX_N = UDA_THR_MAX_N, THR_MAX_U = UDA_THR_MAX_U, THR_MAX_K = UDA_THR_MAX_THRS, THR_MAX_P = UDA_THR_MAX_P,
        THR_MAX_G = UDA_THR_MAX_G, THR_TILE = 2048, THR_MAX_CHUNK = 16384 };
 struct ThrArgs {
-  const double* uncerts;    // [U, N]
+  const double* uncerts;    // [U, N]; row j starts at uncerts + j * ld
   const double* ious;       // [N]
   const uint8_t* tp_class;  // [N]
   const int32_t* group;     // [N] values 0..G-1, or null (G = 0)
@@ -473,11 +473,30 @@ struct ThrArgs {
   int32_t* runs;            // [Pc, K, 2, N] scratch: last sorted position of every run of equal scores, positives up to it
   double* out;              // [Pc, K, 3] thr, rate, auc
   int N, Npad, U, G, K, Pc, fix_cd;
+  int ld;                   // row stride of uncerts, 0: N.  A caller that works on rows [lo, lo + N) of a wider table passes the
+                            // pointers moved by lo and the table's width here (uda_thr_report_np)
   double budget;
   double thr[THR_MAX_K];
 };
 void launch_thr_mask(const ThrArgs& a, hipStream_t s);
 void launch_thr_objective(const ThrArgs& a, hipStream_t s);
+
+// thresholding report (kernels_thrrep.hip): what the reference computes next to the curve of one (segment, score column, IoU
+// threshold) - label counts, the moments behind calc_jsd, the removal counts at the threshold the curve gave.  One block each.
+enum { THRREP_MAX_S = UDA_THR_REPORT_MAX_S, THRREP_MAX_B = UDA_THR_REPORT_MAX_SEGS, THRREP_ROWS = 256, THRREP_LEVELS = 16, THRREP_UNROLL = 8 };
+struct ThrRepArgs {
+  const double* scores;     // [S, N]
+  const uint32_t* mask;     // [N] of launch_thr_mask
+  const int32_t* seg_lo;    // [B]
+  const int32_t* seg_hi;    // [B]
+  double* roc;              // [B, S, K, 3] thr, rate, auc: filled by launch_thr_report_fill, then by the curves, read for thr
+  long long* n_label;       // [B, K, 2] rows with correct, rows without
+  double* moments;          // [B, S, K, 2, 2] (correct | wrong) x (sum, m2)
+  long long* removed;       // [B, S, K, 3] correctly removed, falsely removed, falsely remaining
+  int N, S, K, B;
+};
+void launch_thr_report_fill(const ThrRepArgs& a, hipStream_t s);
+void launch_thr_report(const ThrRepArgs& a, hipStream_t s);
 
 // dataset pruning: the neighbour rows of extract_hash_matrix (reference active_learning_loop.py:240-270) as four passes with a
 // launch boundary between them: max -> (host: limit) -> count -> scan -> (host: total, idx allocated) -> fill.  A block is

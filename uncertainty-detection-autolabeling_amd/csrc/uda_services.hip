@@ -888,6 +888,93 @@ extern "C" int uda_thr_objective_np(int32_t device, const double* uncerts, const
   return scratch_done(nullptr, who, s);
 }
 
+// the thresholding report for B row segments x S ready score columns: one packed upload, the curves of every segment through the
+// objective's kernels on offset pointers (the S columns as S unit-weight candidates: 1.0 * u + 0.0 * u' is u for finite values),
+// in chunks of columns that fit kThrScratchBytes, then one launch for counts and moments, one packed download.  All launches go
+// to the null stream in order, so segments share the sort scratch and nothing waits on the host between them
+extern "C" int uda_thr_report_np(int32_t device, const double* scores, const double* ious, const uint8_t* tp_class, int32_t N,
+                                 int32_t S, const double* iou_thrs, int32_t K, const int32_t* seg_lo, const int32_t* seg_hi,
+                                 int32_t B, int32_t fix_cd, double budget, double* roc, int64_t* n_label, double* moments,
+                                 int64_t* removed) {
+  const char* who = "uda_thr_report_np";
+  if (N < 2 || N > THR_MAX_N) return fail(nullptr, "%s: %d rows, 2..%d are taken", who, N, (int)THR_MAX_N);
+  if (S < 1 || S > THRREP_MAX_S) return fail(nullptr, "%s: %d score columns, 1..%d are taken", who, S, (int)THRREP_MAX_S);
+  if (K < 1 || K > THR_MAX_K) return fail(nullptr, "%s: %d IoU thresholds, 1..%d are taken", who, K, (int)THR_MAX_K);
+  if (B < 1 || B > THRREP_MAX_B) return fail(nullptr, "%s: %d segments, 1..%d are taken", who, B, (int)THRREP_MAX_B);
+  if (!scores || !ious || !tp_class || !iou_thrs || !seg_lo || !seg_hi) return fail(nullptr, "%s: NULL input", who);
+  if (!(budget > 0.0 && budget < 1.0)) return fail(nullptr, "%s: budget %g is not strictly between 0 and 1", who, budget);
+  int n_max = 0;
+  for (int b = 0; b < B; ++b) {
+    if (seg_lo[b] < 0 || seg_hi[b] < seg_lo[b] || seg_hi[b] > N)
+      return fail(nullptr, "%s: segment %d is [%d, %d), not a range inside [0, %d]", who, b, seg_lo[b], seg_hi[b], N);
+    n_max = std::max(n_max, seg_hi[b] - seg_lo[b]);
+  }
+  int Npad_max = THR_TILE;
+  while (Npad_max < n_max) Npad_max <<= 1;
+  const size_t n = (size_t)N, per = 12 * (size_t)Npad_max + 8 * (size_t)n_max * K;
+  const int Sc = (int)std::min<size_t>(std::max<size_t>(kThrScratchBytes / per, 1), (size_t)S);
+
+  // the inputs as one pack: float64 scores | ious | unit weights, int32 seg_lo | seg_hi, uint8 tp_class
+  const size_t o_iou = 8 * n * S, o_eye = o_iou + 8 * n, o_lo = o_eye + 8 * (size_t)S * S, o_hi = o_lo + 4 * (size_t)B,
+               o_tp = o_hi + 4 * (size_t)B, in_bytes = o_tp + n;
+  std::vector<char> in(in_bytes);
+  memcpy(in.data(), scores, o_iou);
+  memcpy(in.data() + o_iou, ious, 8 * n);
+  for (int i = 0; i < S * S; ++i) ((double*)(in.data() + o_eye))[i] = i / S == i % S ? 1.0 : 0.0;
+  memcpy(in.data() + o_lo, seg_lo, 4 * (size_t)B);
+  memcpy(in.data() + o_hi, seg_hi, 4 * (size_t)B);
+  memcpy(in.data() + o_tp, tp_class, n);
+
+  DevScratch s(device);
+  char* d_in = s.upload(in.data(), in_bytes);
+  ThrArgs t{};
+  t.mask = s.alloc<uint32_t>(n);
+  t.keys = s.alloc<uint64_t>((size_t)Sc * Npad_max); t.rows = s.alloc<int32_t>((size_t)Sc * Npad_max);
+  t.runs = s.alloc<int32_t>((size_t)Sc * K * 2 * (size_t)n_max);
+  // the outputs as one pack of 8-byte values: roc | moments | removed | n_label
+  const size_t slots = (size_t)B * S * K, n_pack = slots * (3 + 4 + 3) + (size_t)B * K * 2;
+  double* pack = s.alloc<double>(n_pack);
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  s.zero(pack, n_pack * sizeof(double));
+  const double* d_scores = (const double*)d_in;
+  const double* d_eye = (const double*)(d_in + o_eye);
+  ThrRepArgs r{};
+  r.scores = d_scores; r.mask = t.mask; r.seg_lo = (const int32_t*)(d_in + o_lo); r.seg_hi = (const int32_t*)(d_in + o_hi);
+  r.roc = pack; r.moments = pack + 3 * slots; r.removed = (long long*)(pack + 7 * slots); r.n_label = (long long*)(pack + 10 * slots);
+  r.N = N; r.S = S; r.K = K; r.B = B;
+  t.uncerts = d_scores; t.ious = (const double*)(d_in + o_iou); t.tp_class = (const uint8_t*)(d_in + o_tp);
+  t.N = N; t.K = K; t.U = S; t.G = 0; t.ld = N; t.fix_cd = fix_cd != 0; t.budget = budget;
+  for (int k = 0; k < K; ++k) t.thr[k] = iou_thrs[k];
+  if (s.ok()) {
+    launch_thr_mask(t, nullptr);
+    launch_thr_report_fill(r, nullptr);
+    const uint32_t* d_mask = t.mask;
+    for (int b = 0; b < B; ++b) {
+      const int lo = seg_lo[b], nb = seg_hi[b] - lo;
+      if (nb < 2) continue;                                 // no curve: the slot keeps +inf, NaN, NaN
+      ThrArgs c = t;
+      c.uncerts = d_scores + lo; c.mask = const_cast<uint32_t*>(d_mask) + lo; c.N = nb;
+      c.Npad = THR_TILE;
+      while (c.Npad < nb) c.Npad <<= 1;
+      for (int s0 = 0; s0 < S; s0 += Sc) {
+        c.Pc = std::min(Sc, S - s0);
+        c.params = d_eye + (size_t)s0 * S;
+        c.out = pack + (((size_t)b * S + s0) * K) * 3;
+        launch_thr_objective(c, nullptr);
+      }
+    }
+    launch_thr_report(r, nullptr);
+  }
+  std::vector<char> h;
+  if (int rc = fetch_pack(who, s, pack, n_pack * sizeof(double), h)) return rc;
+  const double* hp = (const double*)h.data();
+  if (roc) memcpy(roc, hp, 3 * slots * 8);
+  if (moments) memcpy(moments, hp + 3 * slots, 4 * slots * 8);
+  if (removed) memcpy(removed, hp + 7 * slots, 3 * slots * 8);
+  if (n_label) memcpy(n_label, hp + 10 * slots, (size_t)B * K * 2 * 8);
+  return 0;
+}
+
 // the neighbour rows of the pruning step: host hashes in, four passes with a launch boundary between them (max, count, scan,
 // fill), CSR rows out; its own allocations, the index array only once the total is known.  A grid of about kPruneBlocks blocks:
 // the columns are cut into as many spans as that takes, which decides who counts a hit and nothing about the result.
