@@ -28,6 +28,10 @@
  *                            (uncertainty_analysis.py:44-152)
  *   uda_thr_report_np     <- the curves, calc_jsd moments and removal counts of MainUncertViz._save_thr_performance and
  *                            _collect_thresh_results (uncertainty_analysis.py:517-749; utils_extra.py:25-36)
+ *   uda_heat_maps_np      <- the ten spatial maps of MainUncertViz._plot_validheat, every `mask[y1:y2, x1:x2] += value[i]` loop
+ *                            of one validation set in one launch (uncertainty_analysis.py:920-1019)
+ *   uda_thr_post_np       <- the tallies of MainUncertViz._plot_metricsspider and the per-image counts behind
+ *                            _collect_postthresholding (uncertainty_analysis.py:838-880, 1024-1068)
  *   uda_hash_neighbors_np <- the distance matrix, its maximum and the rows of near-duplicates of
  *                            ActiveLearning.extract_hash_matrix (active_learning_loop.py:240-270)
  *   uda_nn_dist2_np       <- the four KD-tree queries of emp_KL_divergence for every (class, method) of
@@ -583,6 +587,60 @@ int uda_thr_objective_np(int32_t device, const double* uncerts, const double* io
 int uda_thr_report_np(int32_t device, const double* scores, const double* ious, const uint8_t* tp_class, int32_t N, int32_t S,
                       const double* iou_thrs, int32_t K, const int32_t* seg_lo, const int32_t* seg_hi, int32_t B, int32_t fix_cd,
                       double budget, double* roc, int64_t* n_label, double* moments, int64_t* removed);
+
+/* Heat maps: the spatial maps the reference draws after thresholding (MainUncertViz._plot_validheat, uncertainty_analysis.py:920-1019:
+ * `mask[int(y1):int(y2), int(x1):int(x2)] += value[i]` once per row, ten maps over the same rows), M maps of H x W in one call,
+ * without a handle.  Host arrays: rects [R, N, 4] int32 (r0, r1, c0, c1), half-open ranges the caller has already resolved the way
+ * numpy resolves the slice (post_thresholding.box_slices), 0 <= r0, r1 <= H and 0 <= c0, c1 <= W; r1 <= r0 or c1 <= c0 covers
+ * nothing.  values [V, N] float64, finite; sel [Q, N] uint8 row selectors.  Map m reads the rectangle set map_rect[m], the value
+ * column map_value[m] (-1: every value is 1.0) and the selector map_sel[m] (-1: every row).
+ *   heat       [M, H, W] float64: heat[m, y, x] = s after `s = +0.0; for i = 0 .. N-1: if row i is selected and its rectangle covers
+ *              (y, x): s = s + v[i]` - every addition rounded on its own, in row order, which is numpy's slice += loop bit for bit.
+ *              With map_mean[m] != 0 the stored value is count ? s / count : +0.0, one IEEE division (the reference's
+ *              np.nan_to_num(mask / normalizer) for finite sums)
+ *   count      [M, H, W] int32: the number of such rows; may be NULL
+ *   limits     1 <= N <= UDA_THR_MAX_N, 1 <= M <= UDA_HEAT_MAX_MAPS, 1 <= R <= UDA_HEAT_MAX_RECTS, 0 <= V <= UDA_HEAT_MAX_VALUES,
+ *              0 <= Q <= UDA_HEAT_MAX_SELS, 1 <= H, W and H * W <= UDA_HEAT_MAX_PIXELS, every table index inside its table, every
+ *              rectangle inside the map (checked on the host inside the call); anything else is refused with a
+ *              "uda_heat_maps_np: " message, never truncated, and the outputs stay untouched
+ *   shape      one block of UDA_HEAT_CHUNK threads per (tile of UDA_HEAT_TILE_H x UDA_HEAT_TILE_W pixels, map), sums and counts in
+ *              registers; the rows go through in chunks of UDA_HEAT_CHUNK in row order, the rows whose rectangle meets the tile
+ *              are compacted into LDS in row order (ballot, popcount, prefix over the waves) and walked by all threads.  No
+ *              atomics; the result does not depend on the launch shape.  Every block reads all N rows of its map's tables
+ *   scratch    allocated and freed inside the call: the inputs, 16 * R * N + 8 * V * N + Q * N bytes, and the outputs,
+ *              8 * M * H * W (+ 4 * M * H * W with count) */
+#define UDA_HEAT_TILE_H 32
+#define UDA_HEAT_TILE_W 64
+#define UDA_HEAT_CHUNK 256
+#define UDA_HEAT_MAX_MAPS 16
+#define UDA_HEAT_MAX_RECTS 4
+#define UDA_HEAT_MAX_VALUES 16
+#define UDA_HEAT_MAX_SELS 8
+#define UDA_HEAT_MAX_PIXELS 4194304
+int uda_heat_maps_np(int32_t device, const int32_t* rects, int32_t R, const double* values, int32_t V, const uint8_t* sel, int32_t Q,
+                     int32_t N, const int32_t* map_rect, const int32_t* map_value, const int32_t* map_sel, const int32_t* map_mean,
+                     int32_t M, int32_t H, int32_t W, double* heat, int32_t* count);
+
+/* Post-thresholding tallies: what MainUncertViz._plot_metricsspider (uncertainty_analysis.py:1024-1068) and
+ * _collect_postthresholding (:838-880) count, given the thresholds uda_thr_report_np found, without a handle.  Host arrays: u [N]
+ * float64 (the combined score), ious [N] float64, tp_class [N] uint8, iou_thrs / thrs [K] float64, image [N] int32 ids in 0..I-1
+ * (read only with k_img >= 0).  correct = tp_class && iou >= iou_thrs[k]; side 0 is u >= thrs[k] (removed), side 1 is u < thrs[k]
+ * (remaining).  Outputs, any may be NULL:
+ *   counts     [K, 2, 4] int64: per side its rows, its tp_class rows, its correct rows, its wrong rows (ballots and popcounts)
+ *   iou_sum    [K, 2] float64: the sum of iou over the side's rows - the root of the zero-padded pairwise tree
+ *              uda_uncert_report_np documents, over all N rows from row 0; a row of the other side contributes +0.0 and -0.0
+ *              counts as 0.0
+ *   img_count  [I, 4] int32, at threshold k_img: the image's correctly removed (wrong, side 0), falsely removed (correct, side 0)
+ *              and falsely remaining (wrong, side 1) rows, and its rows with u >= thr
+ *   img_first  [I, 3] int32: the lowest row index of each of the three kinds, N where the image has none.  Both per-image outputs
+ *              are built with integer atomicAdd / atomicMin only; k_img = -1 skips them
+ *   limits     2 <= N <= UDA_THR_MAX_N, 1 <= K <= UDA_THR_MAX_THRS, -1 <= k_img < K, with k_img >= 0: 1 <= I <= N and every id
+ *              inside 0..I-1.  thrs may be +inf (nothing is removed); a NaN in u, ious, iou_thrs or thrs is refused.  Anything else
+ *              is refused with a "uda_thr_post_np: " message, never truncated, and the outputs stay untouched
+ *   cost       one launch of K blocks, one packed download */
+int uda_thr_post_np(int32_t device, const double* u, const double* ious, const uint8_t* tp_class, const int32_t* image, int32_t N,
+                    int32_t I, const double* iou_thrs, const double* thrs, int32_t K, int32_t k_img, int64_t* counts,
+                    double* iou_sum, int32_t* img_count, int32_t* img_first);
 
 /* Dataset pruning: the quadratic part of the active-learning loop's `prune` strategies (ActiveLearning.extract_hash_matrix,
  * active_learning_loop.py:198-316) - for N image hashes the maximum Hamming distance over all pairs and, per image, the images

@@ -34,6 +34,8 @@ PROF_AGGREGATE, PROF_NMS, PROF_PREPROCESS, PROF_SCORE, PROF_EVAL, PROF_PSEUDO = 
 EVAL_MAX_GT, EVAL_MAX_THRS = 256, 32
 THR_MAX_N, THR_MAX_U, THR_MAX_THRS, THR_MAX_P, THR_MAX_G = 262144, 4, 32, 65536, 8192
 THR_REPORT_MAX_S, THR_REPORT_MAX_SEGS = 8, 16384
+HEAT_TILE_H, HEAT_TILE_W, HEAT_CHUNK = 32, 64, 256
+HEAT_MAX_MAPS, HEAT_MAX_RECTS, HEAT_MAX_VALUES, HEAT_MAX_SELS, HEAT_MAX_PIXELS = 16, 4, 16, 8, 4194304
 PRUNE_ROWS, PRUNE_COLS, PRUNE_MAX_N, PRUNE_MAX_W = 256, 512, 1048576, 4
 KNN_ROWS, KNN_COLS, KNN_MAX_D, KNN_MAX_N, KNN_MAX_B, KNN_MAX_PAIRS = 256, 512, 4, 1048576, 4096, 1 << 38
 LC_MD, LC_MISTAKES, LC_NOISY = 1, 2, 4
@@ -163,6 +165,9 @@ _SIGNATURES = {
                                        C.c_int32, C.c_double, _P, _P, _P]),
     "uda_thr_report_np": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32,
                                     C.c_double, _P, _P, _P, _P]),
+    "uda_heat_maps_np": (C.c_int, [C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32,
+                                   C.c_int32, C.c_int32, _P, _P]),
+    "uda_thr_post_np": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "uda_hash_neighbors_np": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                         _P, _P, C.POINTER(C.c_int64)]),
     "uda_nn_dist2_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

@@ -498,6 +498,36 @@ struct ThrRepArgs {
 void launch_thr_report_fill(const ThrRepArgs& a, hipStream_t s);
 void launch_thr_report(const ThrRepArgs& a, hipStream_t s);
 
+// post-thresholding analysis (kernels_thrpost.hip): M heat maps of H x W from row rectangles in one launch, one block per (tile, map),
+// and the tallies behind the spider metrics and the image ranking, one block per IoU threshold
+enum { HEAT_TILE_H = UDA_HEAT_TILE_H, HEAT_TILE_W = UDA_HEAT_TILE_W, HEAT_CHUNK = UDA_HEAT_CHUNK, HEAT_MAX_M = UDA_HEAT_MAX_MAPS,
+       HEAT_MAX_R = UDA_HEAT_MAX_RECTS, HEAT_MAX_V = UDA_HEAT_MAX_VALUES, HEAT_MAX_Q = UDA_HEAT_MAX_SELS,
+       HEAT_MAX_PIXELS = UDA_HEAT_MAX_PIXELS };
+struct HeatArgs {
+  const int4* rects;        // [R, N] r0, r1, c0, c1: half-open ranges inside the map (validated on the host)
+  const double* values;     // [V, N]
+  const uint8_t* sel;       // [Q, N]
+  double* heat;             // [M, H, W]
+  int32_t* count;           // [M, H, W] or null
+  int N, H, W, tiles_x;
+  int map_rect[HEAT_MAX_M], map_value[HEAT_MAX_M], map_sel[HEAT_MAX_M], map_mean[HEAT_MAX_M];
+};
+void launch_heat_maps(const HeatArgs& a, int tiles, int M, hipStream_t s);
+enum { THRPOST_ROWS = 256, THRPOST_LEVELS = 16, THRPOST_UNROLL = 4 };
+struct ThrPostArgs {
+  const double* u;          // [N]
+  const double* ious;       // [N]
+  const uint8_t* tp;        // [N]
+  const int32_t* image;     // [N] ids 0..I-1 (validated on the host); read by the block of k_img only
+  long long* counts;        // [K, 2, 4] removed | remaining: rows, tp_class rows, correct, wrong
+  double* iou_sum;          // [K, 2]
+  int32_t* img_count;       // [I, 4], zeroed
+  int32_t* img_first;       // [I, 3], filled with N
+  int N, K, k_img;          // k_img < 0: no per-image outputs
+  double iou_thr[THR_MAX_K], thr[THR_MAX_K];
+};
+void launch_thr_post(const ThrPostArgs& a, hipStream_t s);
+
 // dataset pruning: the neighbour rows of extract_hash_matrix (reference active_learning_loop.py:240-270) as four passes with a
 // launch boundary between them: max -> (host: limit) -> count -> scan -> (host: total, idx allocated) -> fill.  A block is
 // PRUNE_ROWS rows and walks the chunks_per_span chunks of PRUNE_COLS columns of its span (grid.y = spans); a slot is one

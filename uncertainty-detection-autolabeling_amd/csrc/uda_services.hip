@@ -1,6 +1,6 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
 // COCO matching, the label check and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
-// on scratch device memory of their own (the *_np twins, the thresholding objective, the pruning neighbours, the pseudo-label audit, the uncertainty report, the classification report, uda_nms, uda_debug_pw,
+// on scratch device memory of their own (the *_np twins, the thresholding objective and report, the post-thresholding heat maps and tallies, the pruning neighbours, the pseudo-label audit, the uncertainty report, the classification report, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
 //
@@ -972,6 +972,109 @@ extern "C" int uda_thr_report_np(int32_t device, const double* scores, const dou
   if (moments) memcpy(moments, hp + 3 * slots, 4 * slots * 8);
   if (removed) memcpy(removed, hp + 7 * slots, 3 * slots * 8);
   if (n_label) memcpy(n_label, hp + 10 * slots, (size_t)B * K * 2 * 8);
+  return 0;
+}
+
+// the heat maps of the post-thresholding analysis: everything is checked on the host first (a rectangle outside the map would be
+// harmless to the kernel, which writes its own pixels only, but it is not what the caller meant), then one upload per table, one
+// launch of tiles x M blocks, one download per output
+extern "C" int uda_heat_maps_np(int32_t device, const int32_t* rects, int32_t R, const double* values, int32_t V, const uint8_t* sel,
+                                int32_t Q, int32_t N, const int32_t* map_rect, const int32_t* map_value, const int32_t* map_sel,
+                                const int32_t* map_mean, int32_t M, int32_t H, int32_t W, double* heat, int32_t* count) {
+  const char* who = "uda_heat_maps_np";
+  if (N < 1 || N > THR_MAX_N) return fail(nullptr, "%s: %d rows, 1..%d are taken", who, N, (int)THR_MAX_N);
+  if (M < 1 || M > HEAT_MAX_M) return fail(nullptr, "%s: %d maps, 1..%d are taken", who, M, (int)HEAT_MAX_M);
+  if (R < 1 || R > HEAT_MAX_R) return fail(nullptr, "%s: %d rectangle sets, 1..%d are taken", who, R, (int)HEAT_MAX_R);
+  if (V < 0 || V > HEAT_MAX_V) return fail(nullptr, "%s: %d value columns, 0..%d are taken", who, V, (int)HEAT_MAX_V);
+  if (Q < 0 || Q > HEAT_MAX_Q) return fail(nullptr, "%s: %d selectors, 0..%d are taken", who, Q, (int)HEAT_MAX_Q);
+  if (H < 1 || W < 1 || (int64_t)H * W > HEAT_MAX_PIXELS)
+    return fail(nullptr, "%s: a map of %d x %d, at least 1 x 1 and at most %d pixels are taken", who, H, W, (int)HEAT_MAX_PIXELS);
+  if (!rects || !map_rect || !map_value || !map_sel || !map_mean || (V > 0 && !values) || (Q > 0 && !sel))
+    return fail(nullptr, "%s: NULL input", who);
+  for (int m = 0; m < M; ++m) {
+    if (map_rect[m] < 0 || map_rect[m] >= R) return fail(nullptr, "%s: map %d reads rectangle set %d of %d", who, m, map_rect[m], R);
+    if (map_value[m] < -1 || map_value[m] >= V) return fail(nullptr, "%s: map %d reads value column %d of %d", who, m, map_value[m], V);
+    if (map_sel[m] < -1 || map_sel[m] >= Q) return fail(nullptr, "%s: map %d reads selector %d of %d", who, m, map_sel[m], Q);
+  }
+  const size_t n = (size_t)N, px = (size_t)H * W;
+  for (size_t i = 0; i < (size_t)R * n; ++i) {
+    const int32_t* q = rects + 4 * i;
+    if (q[0] < 0 || q[0] > H || q[1] < 0 || q[1] > H || q[2] < 0 || q[2] > W || q[3] < 0 || q[3] > W)
+      return fail(nullptr, "%s: rectangle %d of set %d is rows [%d, %d) x columns [%d, %d), outside the %d x %d map", who,
+                  (int)(i % n), (int)(i / n), q[0], q[1], q[2], q[3], H, W);
+  }
+  DevScratch s(device);
+  HeatArgs a{};
+  a.rects = (const int4*)s.upload(rects, 4 * (size_t)R * n);
+  a.values = V ? s.upload(values, (size_t)V * n) : nullptr;
+  a.sel = Q ? s.upload(sel, (size_t)Q * n) : nullptr;
+  a.heat = s.alloc<double>((size_t)M * px);
+  a.count = count ? s.alloc<int32_t>((size_t)M * px) : nullptr;
+  a.N = N; a.H = H; a.W = W; a.tiles_x = (W + HEAT_TILE_W - 1) / HEAT_TILE_W;
+  for (int m = 0; m < M; ++m) {
+    a.map_rect[m] = map_rect[m]; a.map_value[m] = map_value[m]; a.map_sel[m] = map_sel[m]; a.map_mean[m] = map_mean[m] != 0;
+  }
+  const int tiles = a.tiles_x * ((H + HEAT_TILE_H - 1) / HEAT_TILE_H);
+  if (s.ok()) launch_heat_maps(a, tiles, M, nullptr);
+  s.sync();
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  // (the outputs are written only from here on; a copy that fails half way is HIP's failure, not a refusal)
+  if (heat) s.download(heat, a.heat, (size_t)M * px * sizeof(double));
+  if (count) s.download(count, a.count, (size_t)M * px * sizeof(int32_t));
+  return scratch_done(nullptr, who, s);
+}
+
+// the tallies of the post-thresholding analysis: one packed upload of the float64 columns, one launch of K blocks, one packed
+// download (counts | iou_sum | img_count | img_first)
+extern "C" int uda_thr_post_np(int32_t device, const double* u, const double* ious, const uint8_t* tp_class, const int32_t* image,
+                               int32_t N, int32_t I, const double* iou_thrs, const double* thrs, int32_t K, int32_t k_img,
+                               int64_t* counts, double* iou_sum, int32_t* img_count, int32_t* img_first) {
+  const char* who = "uda_thr_post_np";
+  if (N < 2 || N > THR_MAX_N) return fail(nullptr, "%s: %d rows, 2..%d are taken", who, N, (int)THR_MAX_N);
+  if (K < 1 || K > THR_MAX_K) return fail(nullptr, "%s: %d IoU thresholds, 1..%d are taken", who, K, (int)THR_MAX_K);
+  if (k_img < -1 || k_img >= K) return fail(nullptr, "%s: k_img %d, -1..%d are taken", who, k_img, K - 1);
+  if (!u || !ious || !tp_class || !iou_thrs || !thrs) return fail(nullptr, "%s: NULL input", who);
+  const bool images = k_img >= 0;
+  if (images) {
+    if (!image) return fail(nullptr, "%s: k_img %d without image ids", who, k_img);
+    if (I < 1 || I > N) return fail(nullptr, "%s: %d images for %d rows, 1..%d are taken", who, I, N, N);
+    for (int i = 0; i < N; ++i)
+      if (image[i] < 0 || image[i] >= I) return fail(nullptr, "%s: image id %d of row %d outside 0..%d", who, image[i], i, I - 1);
+  }
+  for (int k = 0; k < K; ++k)
+    if (iou_thrs[k] != iou_thrs[k] || thrs[k] != thrs[k]) return fail(nullptr, "%s: threshold %d is NaN", who, k);
+  for (int i = 0; i < N; ++i)
+    if (u[i] != u[i] || ious[i] != ious[i]) return fail(nullptr, "%s: row %d holds NaN", who, i);
+  const size_t n = (size_t)N, ni = images ? (size_t)I : 0;
+  std::vector<double> in(2 * n);
+  memcpy(in.data(), u, 8 * n);
+  memcpy(in.data() + n, ious, 8 * n);
+  DevScratch s(device);
+  const double* d_in = s.upload(in.data(), 2 * n);
+  ThrPostArgs a{};
+  a.u = d_in; a.ious = d_in + n;
+  a.tp = s.upload(tp_class, n);
+  a.image = images ? s.upload(image, n) : nullptr;
+  // the outputs as one pack: 8-byte values counts [K, 8] | iou_sum [K, 2], then int32 img_count [I, 4] | img_first [I, 3]
+  const size_t n8 = 10 * (size_t)K, pack_bytes = 8 * n8 + 4 * 7 * ni;
+  char* pack = s.alloc<char>(pack_bytes);
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  a.counts = (long long*)pack; a.iou_sum = (double*)pack + 8 * (size_t)K;
+  a.img_count = (int32_t*)(pack + 8 * n8); a.img_first = a.img_count + 4 * ni;
+  a.N = N; a.K = K; a.k_img = k_img;
+  for (int k = 0; k < K; ++k) { a.iou_thr[k] = iou_thrs[k]; a.thr[k] = thrs[k]; }
+  if (images) {
+    s.zero(a.img_count, 4 * 4 * ni);
+    std::vector<int32_t> none(3 * ni, N);
+    if (s.ok()) s.err = hipMemcpy(a.img_first, none.data(), 4 * 3 * ni, hipMemcpyHostToDevice);
+  }
+  if (s.ok()) launch_thr_post(a, nullptr);
+  std::vector<char> h;
+  if (int rc = fetch_pack(who, s, pack, pack_bytes, h)) return rc;
+  if (counts) memcpy(counts, h.data(), 8 * 8 * (size_t)K);
+  if (iou_sum) memcpy(iou_sum, h.data() + 8 * 8 * (size_t)K, 8 * 2 * (size_t)K);
+  if (images && img_count) memcpy(img_count, h.data() + 8 * n8, 4 * 4 * ni);
+  if (images && img_first) memcpy(img_first, h.data() + 8 * n8 + 4 * 4 * ni, 4 * 3 * ni);
   return 0;
 }
 
