@@ -42,6 +42,8 @@
  *                            (calibrate_regression.py:231-349) and calc_ece / calc_nll / calc_rmse (utils_box.py:17-102)
  *   uda_class_report_np   <- the reliability bins, Brier and NLL sums of ClassificationCalib._calibr_bins and _calibr_plot
  *                            (calibrate_classification.py:97-143, 250-440)
+ *   uda_resample_np       <- every Image.resize(.., Image.LANCZOS) and paste of Parent_SSL.crop_collage, the rare-class collage
+ *                            (ssl_utils/parent.py:505-597; ssl_utils/rcc.py)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -841,6 +843,45 @@ int uda_uncert_report_np(int32_t device, int32_t B, int32_t K, int32_t L, const 
 int uda_class_report_np(int32_t device, int32_t B, int32_t M, int32_t C, int32_t G, int32_t E, const int64_t* off, const double* prob,
                         const int32_t* label, const double* edges, const int32_t* n_edges, int64_t* bin_count, int64_t* bin_hits,
                         double* bin_sum, double* brier_sum, double* nll_sum, int64_t* tab_counts);
+
+/* RCC collages: the pixel work of Parent_SSL.crop_collage (ssl_utils/parent.py:505-597) - every `img.resize(size, Image.LANCZOS)`
+ * and `paste` of a collage run - as jobs on packed RGB uint8 planes, in one call.  The decisions (which crop goes where, at which
+ * size) are the caller's (collage.py).  The result equals Pillow's 8-bit resize bit for bit.
+ *   planes     ids 0 .. S - 1 are the S ragged source planes: src_wh [S, 2] = (width, height), their pixels one after another in
+ *              src_pix (row-major, 3 bytes a pixel).  Ids S .. S + T - 1 are the T temporaries of tmp_wh [T, 2], scratch of the
+ *              call.  Ids S + T .. S + T + N - 1 are the N output planes, each H x W, out [N, H, W, 3].  Temporaries and outputs
+ *              start as zeros (Image.new)
+ *   jobs       [K, 7] int32: level, source plane, destination plane, x, y, w, h.  A job reads its WHOLE source plane and writes
+ *              its w x h resize (Image.resize((w, h), Image.LANCZOS)) into the destination at (x, y); what reaches past the
+ *              destination's right or bottom edge is dropped, as Image.paste drops it.  A job whose w x h is its source's size is
+ *              a copy, as in Pillow
+ *   levels     ascend along the list.  The jobs of a level run together, a level after the one before it on one stream without a
+ *              host synchronisation in between, so a job may read what an earlier level wrote.  Within a level no job reads a
+ *              plane that a job of the level writes, and no two jobs write the same pixel
+ *   arithmetic Pillow's (libImaging/Resample.c).  Per axis and output index xx: scale = in / out, filterscale = max(scale, 1),
+ *              support = 3 filterscale, ksize = 2 ceil(support) + 1, center = (xx + 0.5) scale, the window [xmin, xmin + xmax) =
+ *              [int(center - support + 0.5), int(center + support + 0.5)) cut to the plane; the weights sinc(x) sinc(x / 3) for
+ *              -3 <= x < 3 at x = (i - center + 0.5) / filterscale, evaluated in double with the C library's sin on the host and
+ *              divided by their running sum; each turned into fixed point by int(+-0.5 + k 2^22).  A pass accumulates
+ *              2^21 + sum pixel * k in int32, shifts right arithmetically by 22 and clamps to 0..255.  The horizontal pass comes
+ *              first and is rounded to uint8, then the vertical pass; a pass whose axis keeps its length is skipped
+ *              (Image.resize's own rule is kept: a source more than 100 times as tall as wide whose height shrinks is resampled
+ *              along y first, that result rounded to uint8, then along x)
+ *   limits     S, T, K >= 0, N >= 1, every side of every plane in 1 .. UDA_RESAMPLE_MAX_SIDE, every w and h likewise, x and y
+ *              inside the destination, the destination not a source plane; the temporaries and the horizontal passes' results
+ *              together at most UDA_RESAMPLE_MAX_SCRATCH bytes.  Anything else is refused with a "uda_resample_np: " message, and
+ *              out stays untouched
+ *   scratch    allocated and freed inside the call: the planes, w x (source height) x 3 bytes for every job that resamples both
+ *              axes ((source width) x h x 3 where y goes first), and the coefficient tables, one for each distinct (in, out) pair: 4 out (2 + ksize) bytes
+ * uda_resample_coeffs_np is host only (no device is touched): the table of one axis.  *ksize is always written; bounds [out_size,
+ * 2] = (xmin, xmax) and coeffs [out_size, ksize] (zeros past xmax) when they are not NULL, coeffs_cap being the int32 values
+ * coeffs holds. */
+#define UDA_RESAMPLE_TILE 32                       /* output positions a tile of a pass, at most */
+#define UDA_RESAMPLE_MAX_SIDE 65536                /* pixels a side, planes and jobs */
+#define UDA_RESAMPLE_MAX_SCRATCH 17179869184LL     /* bytes, 2^34 */
+int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T, const int32_t* tmp_wh,
+                    int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, uint8_t* out);
+int uda_resample_coeffs_np(int32_t in_size, int32_t out_size, int32_t* ksize, int32_t* bounds, int32_t* coeffs, int64_t coeffs_cap);
 
 /* Label correction (GLC): the verdicts of the reference's ground-truth label correction (AdvancedLabels, src/ssl_utils/glc.py) -
  * which ground-truth boxes are mistakes, which detections are missing labels, which noisy boxes are replaced by their detection -

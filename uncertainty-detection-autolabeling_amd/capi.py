@@ -47,6 +47,7 @@ AUDIT_DET_EXTRA, AUDIT_GT_NOMATCH = 1, 1
 AUDIT_MAX_G, AUDIT_MAX_D, AUDIT_MAX_B = 1024, 1024, 1048576
 REPORT_ROWS, REPORT_MAX_K, REPORT_MAX_L, REPORT_MAX_B, REPORT_MAX_ROWS = 256, 16, 128, 4096, 1 << 22
 CLASSREP_ROWS, CLASSREP_MAX_B, CLASSREP_MAX_M, CLASSREP_MAX_C, CLASSREP_MAX_E, CLASSREP_MAX_ROWS = 256, 4096, 8, 128, 64, 1 << 22
+RESAMPLE_TILE, RESAMPLE_MAX_SIDE, RESAMPLE_MAX_SCRATCH = 32, 65536, 1 << 34
 
 
 class BufDesc(C.Structure):
@@ -175,6 +176,8 @@ _SIGNATURES = {
     "uda_uncert_report_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "uda_class_report_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                       _P, _P]),
+    "uda_resample_np": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "uda_resample_coeffs_np": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.c_int64]),
     "uda_label_check": (C.c_int, [_P, C.c_float, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_float, C.c_int32]),
     "uda_get_label_check": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "uda_label_check_np": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,

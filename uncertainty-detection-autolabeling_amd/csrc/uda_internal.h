@@ -682,6 +682,25 @@ struct ClassRepArgs {
 };
 void launch_class_report(const ClassRepArgs& a, hipStream_t s);
 
+// RCC collages (reference ssl_utils/parent.py:317-686): Pillow's two-pass 8-bit Lanczos resample, many jobs per call
+// (kernels_collage.hip).  A job is one or two passes; a pass resamples one axis of a packed RGB plane with a table of
+// resample_coeffs.  Every address is a byte offset into the call's one device allocation.
+enum { RESAMPLE_THREADS = 256, RESAMPLE_TW = UDA_RESAMPLE_TILE, RESAMPLE_KCH = 16, RESAMPLE_SPAN_PER_POS = 32, RESAMPLE_LDS = 24576,
+       RESAMPLE_BITS = 22 };
+struct ResamplePass {
+  int64_t src, dst;             // first byte of the source plane / of the pass's rectangle in the destination
+  int64_t src_stride, dst_stride;   // bytes a row
+  int64_t coef_off;             // into the int32 pool: bounds [out_full, 2], then coefficients [out_full, ksize]
+  int32_t in_size, out_full;    // the axis: source length, and the length of the table (the unclipped output)
+  int32_t n_out, n_lines;       // what is written: output positions along the axis (clipped), lines across it (clipped)
+  int32_t ksize, tw;            // tw: output positions a tile, a power of two; a tile has RESAMPLE_THREADS / tw lines
+  int32_t tile0, tiles_pos;     // first block of the pass in its launch; tiles along the axis
+};
+void launch_resample_passes(const ResamplePass* passes, int n_pass, int n_tiles, bool vertical, const int32_t* pool, uint8_t* base,
+                            hipStream_t s);
+int resample_ksize(int in_size, int out_size);
+void resample_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

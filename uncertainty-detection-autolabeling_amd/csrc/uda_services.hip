@@ -1,6 +1,6 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
 // COCO matching, the label check and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
-// on scratch device memory of their own (the *_np twins, the thresholding objective and report, the post-thresholding heat maps and tallies, the pruning neighbours, the pseudo-label audit, the uncertainty report, the classification report, uda_nms, uda_debug_pw,
+// on scratch device memory of their own (the *_np twins, the thresholding objective and report, the post-thresholding heat maps and tallies, the pruning neighbours, the pseudo-label audit, the uncertainty report, the classification report, the collage resample, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
 //
@@ -12,7 +12,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <numeric>
+#include <thread>
 #include <vector>
 
 #include "dev_scratch.h"
@@ -1379,6 +1381,222 @@ extern "C" int uda_class_report_np(int32_t device, int32_t B, int32_t M, int32_t
   s.download(bin_sum, a.bin_sum, bin_sum ? n_bin * sizeof(double) : 0);
   s.download(brier_sum, a.brier_sum, brier_sum ? n_bri * sizeof(double) : 0);
   s.download(nll_sum, a.nll_sum, nll_sum ? n_nll * sizeof(double) : 0);
+  return scratch_done(nullptr, who, s);
+}
+
+// ---- RCC collages: Pillow's resize and paste as jobs on packed RGB planes (kernels_collage.hip)
+extern "C" int uda_resample_coeffs_np(int32_t in_size, int32_t out_size, int32_t* ksize, int32_t* bounds, int32_t* coeffs,
+                                      int64_t coeffs_cap) {
+  const char* who = "uda_resample_coeffs_np";
+  if (in_size < 1 || in_size > UDA_RESAMPLE_MAX_SIDE || out_size < 1 || out_size > UDA_RESAMPLE_MAX_SIDE)
+    return fail(nullptr, "%s: an axis of %d to %d pixels, 1..%d are taken", who, in_size, out_size, (int)UDA_RESAMPLE_MAX_SIDE);
+  if (!ksize) return fail(nullptr, "%s: NULL ksize", who);
+  *ksize = resample_ksize(in_size, out_size);
+  if (!bounds && !coeffs) return 0;
+  if (!bounds || !coeffs) return fail(nullptr, "%s: bounds and coeffs go together", who);
+  if (coeffs_cap < (int64_t)out_size * *ksize)
+    return fail(nullptr, "%s: coeffs holds %lld values, %lld are needed", who, (long long)coeffs_cap, (long long)out_size * *ksize);
+  resample_coeffs(in_size, out_size, bounds, coeffs);
+  return 0;
+}
+
+namespace {
+struct ResamplePlane { int64_t off; int32_t w, h; };
+struct ResampleTables {          // one table for each distinct (in, out) pair of the call, in one int32 pool
+  struct Table { int64_t key, off; };
+  std::vector<int32_t> pool;
+  std::vector<Table> index, fresh;                     // index: sorted by key; fresh: the latest, not yet merged
+  std::vector<Table> todo;                             // reserved in the pool, not yet filled
+  size_t reserved = 0;
+  // where the table of (in, out) is (or will be: fill() makes what get() reserved)
+  int64_t get(int in, int out) {
+    const int64_t key = ((int64_t)in << 32) | (uint32_t)out;
+    for (const Table& f : fresh) if (f.key == key) return f.off;
+    auto it = std::lower_bound(index.begin(), index.end(), key, [](const Table& t, int64_t k) { return t.key < k; });
+    if (it != index.end() && it->key == key) return it->off;
+    const Table t{key, (int64_t)reserved};
+    reserved += (size_t)out * (2 + (in == out ? 1 : resample_ksize(in, out)));
+    todo.push_back(t);
+    fresh.push_back(t);
+    if (fresh.size() >= 64) {
+      index.insert(index.end(), fresh.begin(), fresh.end());
+      std::sort(index.begin(), index.end(), [](const Table& a, const Table& b) { return a.key < b.key; });
+      fresh.clear();
+    }
+    return t.off;
+  }
+  // the tables are independent of each other: a few host threads share them out (thousands of sin calls a table)
+  void fill() {
+    pool.resize(reserved);
+    std::atomic<size_t> next{0};
+    auto work = [&]() {
+      for (size_t i; (i = next.fetch_add(1)) < todo.size();) {
+        const int in = (int)(todo[i].key >> 32), out = (int)(uint32_t)todo[i].key;
+        int32_t* b = pool.data() + todo[i].off;
+        if (in == out) {                               // the identity: a copy is a pass like any other
+          for (int k = 0; k < out; ++k) { b[2 * k] = k; b[2 * k + 1] = 1; b[2 * (size_t)out + k] = 1 << RESAMPLE_BITS; }
+        } else {
+          resample_coeffs(in, out, b, b + 2 * (size_t)out);
+        }
+      }
+    };
+    const unsigned hw = std::thread::hardware_concurrency();
+    const size_t n_thr = std::min<size_t>({(size_t)(hw ? hw : 1), 8, todo.size() / 16});
+    std::vector<std::thread> pool_thr;
+    for (size_t t = 0; t < n_thr; ++t) pool_thr.emplace_back(work);
+    work();
+    for (std::thread& t : pool_thr) t.join();
+    todo.clear();
+  }
+};
+}  // namespace
+
+// Image.resize's own rule (PIL/Image.py): a plane more than 100 times as tall as wide that gets shorter is resized along y first,
+// then along x - the one case where the vertical result, not the horizontal one, is what gets rounded to uint8 in between.
+static bool resample_vertical_first(int src_w, int src_h, int h) { return (int64_t)src_h > (int64_t)src_w * 100 && h < src_h; }
+
+// One pass over `in_size` -> table `out_full`, of which n_out positions and n_lines lines are written; its table is reserved.
+static ResamplePass resample_pass(ResampleTables& tabs, int64_t src, int64_t src_stride, int64_t dst, int64_t dst_stride, int in_size,
+                                  int out_full, int n_out, int n_lines) {
+  ResamplePass p{};
+  p.src = src; p.dst = dst; p.src_stride = src_stride; p.dst_stride = dst_stride;
+  p.coef_off = tabs.get(in_size, out_full);
+  p.in_size = in_size; p.out_full = out_full; p.n_out = n_out; p.n_lines = n_lines;
+  p.ksize = in_size == out_full ? 1 : resample_ksize(in_size, out_full);
+  return p;
+}
+// The tiles of a pass, once the tables are filled.  tw: the largest power of two <= RESAMPLE_TW whose every tile's span (last xmin
+// - first xmin + a chunk) fits RESAMPLE_SPAN_PER_POS * tw pixels, and no wider than the output needs.  A tile of one position
+// always fits.
+static void resample_tiles(ResamplePass& p, const ResampleTables& tabs, bool vertical, int* n_tiles) {
+  const int32_t* bounds = tabs.pool.data() + p.coef_off;
+  int tw = vertical ? 8 : RESAMPLE_TW;                 // along y a tile is wide rather than tall: its rows are runs of 3 * 256 / tw bytes
+  while (tw > 1 && tw / 2 >= p.n_out) tw /= 2;
+  for (; tw > 1; tw /= 2) {
+    bool fits = true;
+    for (int o0 = 0; o0 < p.n_out && fits; o0 += tw)
+      fits = bounds[2 * (std::min(o0 + tw, p.n_out) - 1)] - bounds[2 * o0] + RESAMPLE_KCH <= RESAMPLE_SPAN_PER_POS * tw;
+    if (fits) break;
+  }
+  p.tw = tw;
+  p.tiles_pos = (p.n_out + tw - 1) / tw;
+  const int lines = RESAMPLE_THREADS / tw;
+  p.tile0 = *n_tiles;
+  *n_tiles += p.tiles_pos * ((p.n_lines + lines - 1) / lines);
+}
+
+extern "C" int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T, const int32_t* tmp_wh,
+                               int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, uint8_t* out) {
+  const char* who = "uda_resample_np";
+  const int MAXS = UDA_RESAMPLE_MAX_SIDE;
+  if (S < 0 || T < 0 || K < 0 || N < 1) return fail(nullptr, "%s: %d source planes, %d temporaries, %d output planes, %d jobs", who, S, T, N, K);
+  if (H < 1 || H > MAXS || W < 1 || W > MAXS) return fail(nullptr, "%s: output planes of %d x %d, sides of 1..%d are taken", who, W, H, MAXS);
+  if (!out || (S && (!src_wh || !src_pix)) || (T && !tmp_wh) || (K && !jobs)) return fail(nullptr, "%s: NULL array", who);
+  const int P = S + T + N;
+  std::vector<ResamplePlane> pl((size_t)P);
+  int64_t bytes = 0;
+  for (int i = 0; i < S + T; ++i) {
+    const int32_t* wh = i < S ? src_wh + 2 * (size_t)i : tmp_wh + 2 * (size_t)(i - S);
+    if (wh[0] < 1 || wh[1] < 1 || wh[0] > MAXS || wh[1] > MAXS)
+      return fail(nullptr, "%s: plane %d is %d x %d, an empty plane or a side above %d is not taken", who, i, wh[0], wh[1], MAXS);
+    pl[i] = ResamplePlane{bytes, wh[0], wh[1]};
+    bytes += (int64_t)wh[0] * wh[1] * 3;
+  }
+  const int64_t src_bytes = S ? pl[S - 1].off + (int64_t)pl[S - 1].w * pl[S - 1].h * 3 : 0;
+  int64_t scratch = bytes - src_bytes;
+  const int64_t out_off = bytes, out_bytes = (int64_t)N * H * W * 3;
+  for (int i = 0; i < N; ++i) pl[S + T + i] = ResamplePlane{out_off + (int64_t)i * H * W * 3, W, H};
+  bytes += out_bytes;
+  // the jobs: ids, sizes, levels; per level no read of a plane the level writes, no pixel written twice
+  std::vector<int> wrote((size_t)P, -1);
+  std::vector<int> order;
+  for (int k0 = 0; k0 < K;) {
+    int k1 = k0;
+    const int level = jobs[7 * (size_t)k0];
+    if (k0 && level < jobs[7 * (size_t)(k0 - 1)]) return fail(nullptr, "%s: the level of job %d is %d after %d: levels ascend", who, k0, level, jobs[7 * (size_t)(k0 - 1)]);
+    for (; k1 < K && jobs[7 * (size_t)k1] == level; ++k1) {
+      const int32_t* j = jobs + 7 * (size_t)k1;
+      if (j[1] < 0 || j[1] >= P) return fail(nullptr, "%s: job %d reads plane %d, there are %d", who, k1, j[1], P);
+      if (j[2] < S || j[2] >= P) return fail(nullptr, "%s: job %d writes plane %d, the planes %d..%d can be written", who, k1, j[2], S, P - 1);
+      if (j[5] < 1 || j[6] < 1 || j[5] > MAXS || j[6] > MAXS) return fail(nullptr, "%s: job %d resizes to %d x %d, sides of 1..%d are taken", who, k1, j[5], j[6], MAXS);
+      const ResamplePlane& d = pl[j[2]];
+      if (j[3] < 0 || j[4] < 0 || j[3] >= d.w || j[4] >= d.h)
+        return fail(nullptr, "%s: job %d pastes at (%d, %d), outside its destination of %d x %d", who, k1, j[3], j[4], d.w, d.h);
+      wrote[j[2]] = k0;
+      const ResamplePlane& f = pl[j[1]];
+      if (j[5] != f.w && j[6] != f.h)
+        scratch += resample_vertical_first(f.w, f.h, j[6]) ? (int64_t)f.w * std::min(j[6], d.h - j[4]) * 3 : (int64_t)std::min(j[5], d.w - j[3]) * f.h * 3;
+    }
+    order.clear();
+    for (int k = k0; k < k1; ++k) {
+      if (wrote[jobs[7 * (size_t)k + 1]] == k0)
+        return fail(nullptr, "%s: job %d reads plane %d, which a job of its own level %d writes", who, k, jobs[7 * (size_t)k + 1], level);
+      order.push_back(k);
+    }
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return jobs[7 * (size_t)a + 2] < jobs[7 * (size_t)b + 2]; });
+    for (size_t a = 0; a < order.size(); ++a)
+      for (size_t b = a + 1; b < order.size() && jobs[7 * (size_t)order[b] + 2] == jobs[7 * (size_t)order[a] + 2]; ++b) {
+        const int32_t *ja = jobs + 7 * (size_t)order[a], *jb = jobs + 7 * (size_t)order[b];
+        if (ja[3] < jb[3] + jb[5] && jb[3] < ja[3] + ja[5] && ja[4] < jb[4] + jb[6] && jb[4] < ja[4] + ja[6])
+          return fail(nullptr, "%s: jobs %d and %d of level %d write the same pixels of plane %d", who, std::min(order[a], order[b]),
+                      std::max(order[a], order[b]), level, ja[2]);
+      }
+    k0 = k1;
+  }
+  if (scratch > UDA_RESAMPLE_MAX_SCRATCH)
+    return fail(nullptr, "%s: %lld bytes of scratch, at most %lld a call", who, (long long)scratch, (long long)UDA_RESAMPLE_MAX_SCRATCH);
+  // the passes, level by level: the horizontal ones of a level, then its vertical ones
+  ResampleTables tabs;
+  std::vector<ResamplePass> passes;
+  struct Launch { int first, count, tiles; bool vertical; };
+  std::vector<Launch> launches;
+  for (int k0 = 0; k0 < K;) {
+    int k1 = k0;
+    while (k1 < K && jobs[7 * (size_t)k1] == jobs[7 * (size_t)k0]) ++k1;
+    std::vector<ResamplePass> vert, late;
+    const int first = (int)passes.size();
+    for (int k = k0; k < k1; ++k) {
+      const int32_t* j = jobs + 7 * (size_t)k;
+      const ResamplePlane &s = pl[j[1]], &d = pl[j[2]];
+      const int w = j[5], h = j[6], cw = std::min(w, d.w - j[3]), ch = std::min(h, d.h - j[4]);
+      const int64_t to = d.off + ((int64_t)j[4] * d.w + j[3]) * 3;
+      if (w != s.w && h != s.h && resample_vertical_first(s.w, s.h, h)) {   // the vertical result, s.w x ch, in scratch; x after it
+        vert.push_back(resample_pass(tabs, s.off, (int64_t)s.w * 3, bytes, (int64_t)s.w * 3, s.h, h, ch, s.w));
+        late.push_back(resample_pass(tabs, bytes, (int64_t)s.w * 3, to, (int64_t)d.w * 3, s.w, w, cw, ch));
+        bytes += (int64_t)s.w * ch * 3;
+      } else if (w != s.w && h != s.h) {                // both: the horizontal result, cw x s.h, rounded to uint8 in scratch
+        passes.push_back(resample_pass(tabs, s.off, (int64_t)s.w * 3, bytes, (int64_t)cw * 3, s.w, w, cw, s.h));
+        vert.push_back(resample_pass(tabs, bytes, (int64_t)cw * 3, to, (int64_t)d.w * 3, s.h, h, ch, cw));
+        bytes += (int64_t)cw * s.h * 3;
+      } else if (h != s.h) {
+        vert.push_back(resample_pass(tabs, s.off, (int64_t)s.w * 3, to, (int64_t)d.w * 3, s.h, h, ch, cw));
+      } else {                                          // along x only, or the copy (the identity table)
+        passes.push_back(resample_pass(tabs, s.off, (int64_t)s.w * 3, to, (int64_t)d.w * 3, s.w, w, cw, ch));
+      }
+    }
+    if ((int)passes.size() > first) launches.push_back(Launch{first, (int)passes.size() - first, 0, false});
+    if (!vert.empty()) launches.push_back(Launch{(int)passes.size(), (int)vert.size(), 0, true});
+    passes.insert(passes.end(), vert.begin(), vert.end());
+    if (!late.empty()) launches.push_back(Launch{(int)passes.size(), (int)late.size(), 0, false});
+    passes.insert(passes.end(), late.begin(), late.end());
+    k0 = k1;
+  }
+  tabs.fill();
+  for (Launch& l : launches)
+    for (int i = 0; i < l.count; ++i) resample_tiles(passes[l.first + i], tabs, l.vertical, &l.tiles);
+  DevScratch s(device);
+  hipStream_t st = s.stream();
+  uint8_t* base = s.alloc<uint8_t>((size_t)bytes);
+  const ResamplePass* d_pass = s.upload(passes.data(), passes.size(), st);
+  const int32_t* d_pool = s.upload(tabs.pool.data(), tabs.pool.size(), st);
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  if (src_bytes && s.ok()) s.err = hipMemcpyAsync(base, src_pix, (size_t)src_bytes, hipMemcpyHostToDevice, st);
+  s.zero(base + src_bytes, (size_t)(out_off + out_bytes - src_bytes), st);
+  for (const Launch& l : launches)
+    if (s.ok()) launch_resample_passes(d_pass + l.first, l.count, l.tiles, l.vertical, d_pool, base, st);
+  s.sync(st);
+  if (int rc = scratch_done(nullptr, who, s)) return rc;
+  s.download(out, base + out_off, (size_t)out_bytes);
   return scratch_done(nullptr, who, s);
 }
 
