@@ -44,6 +44,9 @@
  *                            (calibrate_classification.py:97-143, 250-440)
  *   uda_resample_np       <- every Image.resize(.., Image.LANCZOS) and paste of Parent_SSL.crop_collage, the rare-class collage
  *                            (ssl_utils/parent.py:505-597; ssl_utils/rcc.py)
+ *   uda_collage_np        <- the same with Parent_SSL.apply_manual_augmentation between resize and paste: Image.transpose,
+ *                            ImageEnhance.Brightness / Contrast, ImageFilter.GaussianBlur and the noise add
+ *                            (ssl_utils/parent.py:261-315, 534-537)
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -882,6 +885,51 @@ int uda_class_report_np(int32_t device, int32_t B, int32_t M, int32_t C, int32_t
 int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T, const int32_t* tmp_wh,
                     int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, uint8_t* out);
 int uda_resample_coeffs_np(int32_t in_size, int32_t out_size, int32_t* ksize, int32_t* bounds, int32_t* coeffs, int64_t coeffs_cap);
+
+/* RCC's manual augmentations (Parent_SSL.apply_manual_augmentation, ssl_utils/parent.py:261-315, applied at :534-537): the job
+ * list of uda_resample_np with an operation per job, so that the augmentation of a resized crop runs between its resize and its
+ * paste in the same call.  Planes, levels, limits and refusals are those of uda_resample_np; every pixel equals Pillow's.
+ *   jobs       [K, 9] int32: level, source plane, destination plane, x, y, w, h, op, arg.  op 0 is the resize of uda_resample_np
+ *              (arg is not read).  For the ops 1-5 w x h must be the source plane's size; the result is written at (x, y) with
+ *              the paste's clipping
+ *   params     [P] doubles; arg indexes it for the ops 2-4.  noise: the bytes of the op-5 jobs one after another in job-list
+ *              order, 3 w h each (row-major, as the plane); noise_bytes is their total
+ *   arithmetic channels are independent.  "f32" is IEEE binary32 with every operation rounded on its own: the device code does
+ *              not contract a multiply and an add into an FMA (Pillow's x86 build does not, and a fused blend truncates
+ *              differently)
+ *     op 1  flip (Image.transpose(FLIP_LEFT_RIGHT)): dst[y, x] = src[y, w - 1 - x]
+ *     op 2  brightness (ImageEnhance.Brightness(..).enhance(params[arg])): blend(0, factor)
+ *     op 3  contrast (ImageEnhance.Contrast): blend(m, factor) with m = int(S / n + 0.5), division and addition in double on
+ *           the device, S the exact integer sum over the WHOLE source plane of L = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16
+ *           and n its pixel count
+ *           blend(deg, factor) (ImagingBlend): a = f32(factor), t = f32(deg) + a * (f32(px) - f32(deg)) in f32; for 0 <= a <= 1
+ *           the result is t truncated toward zero, otherwise 0 if t <= 0, 255 if t >= 255, else t truncated
+ *     op 4  gaussian blur (ImageFilter.GaussianBlur(params[arg]), ImagingGaussianBlur with 3 passes).  On the host (this is
+ *           uda_gauss_box_np): s2 = f32(f32(radius)^2 / 3); L = f32(sqrt(12.0 s2 + 1.0)) and l = f32(floor((L - 1.0) / 2.0)),
+ *           the insides in double; a = f32((2 l + 1) (l (l + 1) - 3 s2)), a = f32(a / f32(6 (s2 - (l + 1)^2))), all f32;
+ *           fr = f32(l + a).  Then r = int(fr), ww = uint32(f32(2^24) / (fr * 2 + 1)) (f32 division, truncated) and
+ *           fw = (2^24 - (2 r + 1) ww) / 2 (integer division).  One pass along a line of length n:
+ *             out[x] = (ww * sum_{d = -r..r} in[c(x + d)] + fw * (in[c(x - r - 1)] + in[c(x + r + 1)]) + 2^23) >> 24
+ *           in uint32 with c(i) = clamp(i, 0, n - 1) - what Pillow's running accumulator gives, its edgeA > edgeB branch for
+ *           windows wider than the line included.  Three passes along x, each rounded to uint8 and feeding the next, then
+ *           three along y.  fr = 0 (radius 0) is a copy
+ *     op 5  add bytes (np_image + noise on uint8): dst = (src + noise) mod 256; the reference's np.clip after it changes nothing
+ *   refusals   as uda_resample_np, and: an op outside 0..5, an arg outside params for the ops 2-4, a parameter that is not
+ *              finite or is negative, a radius above UDA_BLUR_MAX_RADIUS, a w x h that is not the source's size for the ops 1-5,
+ *              a noise_bytes that is not the op-5 jobs' total.  Each with a "uda_collage_np: " message; out stays untouched
+ *   scratch    as uda_resample_np, plus w x h x 3 bytes a blur job (the x stage's result, counted against
+ *              UDA_RESAMPLE_MAX_SCRATCH), the noise, and 8 bytes a contrast job
+ * A tile of the pointwise ops is UDA_AUGMENT_TILE pixels x 8 rows; a tile of a blur stage is UDA_AUGMENT_TILE positions x
+ * UDA_AUGMENT_TILE lines with a halo of 3 (r + 1) positions a side in LDS, r + 1 <= UDA_BLUR_MAX_BOX + 1 for every radius up to
+ * UDA_BLUR_MAX_RADIUS (the reference draws 1..3).
+ * uda_gauss_box_np is host only (no device is touched, no cap on the radius): the box radius and the weights of one radius. */
+#define UDA_AUGMENT_TILE 32
+#define UDA_BLUR_MAX_RADIUS 16.0                   /* gaussian radius; box radius r <= UDA_BLUR_MAX_BOX */
+#define UDA_BLUR_MAX_BOX 15
+int uda_collage_np(int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T, const int32_t* tmp_wh,
+                   int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs /* [K, 9] */, int32_t P, const double* params,
+                   int64_t noise_bytes, const uint8_t* noise, uint8_t* out);
+int uda_gauss_box_np(double radius, float* fr, uint32_t* ww, uint32_t* fw);
 
 /* Label correction (GLC): the verdicts of the reference's ground-truth label correction (AdvancedLabels, src/ssl_utils/glc.py) -
  * which ground-truth boxes are mistakes, which detections are missing labels, which noisy boxes are replaced by their detection -

@@ -19,10 +19,15 @@ to 300 pixels a side among other boxes, default margins (0.5 .. 1.0), BDD100K-si
                 `paste` of the job list with Pillow (a resized crop that is read again is pasted into an Image.new first, which the
                 reference does not need: one copy more a crop)
 
+--augment turns `manual_augmentations` on (parent.py:261-315): every resized crop gets one of the reference's five random
+augmentations before it is pasted, the call is `collage.collage_np` -> `uda_collage_np` (the noise planes are part of its
+upload), and the host loop applies Image.transpose / ImageEnhance / ImageFilter.GaussianBlur / the numpy noise add as the
+reference does.  `plan` then includes the reference's own draws (a noise plane a noisy crop).
+
 The script asserts that EVERY collage of the device equals Pillow's before it prints a time.  Wall-clock p50 / mean over --steps
 runs after --warmup.  Prints ONE JSON line.
 
-    python tools/bench_collage.py [--images 700] [--crops 3000] [--scale] [--steps 3] [--warmup 1] [--device-only]
+    python tools/bench_collage.py [--images 700] [--crops 3000] [--scale] [--augment] [--steps 3] [--warmup 1] [--device-only]
 """
 import argparse
 import io
@@ -76,15 +81,37 @@ def timed(fn, steps, warmup):
 
 
 def jobs_by_collage(plan):
-    """The jobs of every collage, in level order: a temporary belongs to the collage its pixels end in."""
+    """The jobs of every collage, in level order: a temporary belongs to the collage its pixels end in.  A job is its 7 values and,
+    from a plan with augmentations, op, arg and where its noise starts in plan.noise."""
     S, T = len(plan.crops), len(plan.tmp_wh)
     owner = {}
     for j in plan.jobs[::-1].tolist():
         owner[j[1]] = owner[j[2]] if j[2] < S + T else j[2] - S - T
     per = [[] for _ in range(plan.n)]
+    at = 0
     for j in plan.jobs.tolist():
+        if len(j) == 9:
+            j.append(at)
+            at += 3 * j[5] * j[6] if j[7] == 5 else 0
         per[owner[j[1]]].append(j)
     return per
+
+
+def pillow_augment(image, op, value, noise):
+    """parent.py:264-304 on a PIL image."""
+    from PIL import Image, ImageEnhance, ImageFilter
+    if op == 1:
+        return image.transpose(Image.FLIP_LEFT_RIGHT)
+    if op == 2:
+        return ImageEnhance.Brightness(image).enhance(value)
+    if op == 3:
+        return ImageEnhance.Contrast(image).enhance(value)
+    if op == 4:
+        return image.filter(ImageFilter.GaussianBlur(radius=value))
+    np_image = np.array(image)
+    np_image = np_image + noise.reshape(np_image.shape)
+    np_image = np.clip(np_image, 0, 255)
+    return Image.fromarray(np_image.astype("uint8"))
 
 
 def pillow_collage(jobs, crops, plan):
@@ -92,11 +119,16 @@ def pillow_collage(jobs, crops, plan):
     from PIL import Image
     S, T = len(plan.crops), len(plan.tmp_wh)
     planes = {}
-    for _, s, d, x, y, w, h in jobs:
+    for _, s, d, x, y, w, h, *aug in jobs:
         src = planes[s] if s in planes else Image.fromarray(crops[s])
         if d not in planes:
             planes[d] = Image.new("RGB", plan.tmp_wh[d - S] if d < S + T else (plan.width, plan.height))
-        planes[d].paste(src.resize((w, h), Image.LANCZOS), (x, y))
+        if aug and aug[0]:
+            op, arg, at = aug
+            new = pillow_augment(src, op, plan.params[arg] if op in (2, 3, 4) else None, plan.noise[at:at + 3 * w * h] if op == 5 else None)
+        else:
+            new = src.resize((w, h), Image.LANCZOS)
+        planes[d].paste(new, (x, y))
         out = planes[d]
     return out
 
@@ -106,6 +138,7 @@ def main():
     ap.add_argument("--images", type=int, default=700)
     ap.add_argument("--crops", type=int, default=3000)
     ap.add_argument("--scale", action="store_true", help="the four-scale variant (scale=True)")
+    ap.add_argument("--augment", action="store_true", help="manual_augmentations=True: one of five augmentations a crop")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--encode-sample", type=int, default=16)
@@ -116,7 +149,7 @@ def main():
     from uda_amd import collage
     images, classes, boxes = synthetic(a.images, a.crops)
     target = ["rider"]
-    kw = dict(dataset="BDD100K", scale=a.scale)
+    kw = dict(dataset="BDD100K", scale=a.scale, manual_augmentations=a.augment)
     t0 = time.perf_counter()
     plan = collage.plan_collage(images, classes, boxes, target, **kw)
     plan_ms = (time.perf_counter() - t0) * 1e3
@@ -127,9 +160,15 @@ def main():
     sides = np.asarray([(c.shape[1], c.shape[0]) for c in crops])
     res = dict(images=a.images, target_boxes=a.crops, crops=len(crops), crop_w_mean=round(float(sides[:, 0].mean()), 1),
                crop_h_mean=round(float(sides[:, 1].mean()), 1), collages=plan.n, temporaries=len(plan.tmp_wh), jobs=len(plan.jobs),
-               levels=int(plan.jobs[:, 0].max()) + 1, scale=bool(a.scale), plan_ms=round(plan_ms, 1), cut_ms=round(cut_ms, 1))
+               levels=int(plan.jobs[:, 0].max()) + 1, scale=bool(a.scale), augment=bool(a.augment), plan_ms=round(plan_ms, 1),
+               cut_ms=round(cut_ms, 1))
+    if a.augment:
+        res["kinds"] = {k: sum(1 for kind, _ in plan.augment if kind == k) for k in collage.AUGMENT_KINDS}
+        res["noise_bytes"] = int(plan.noise.nbytes)
 
     def device_call():
+        if a.augment:
+            return collage.collage_np(packed, plan.tmp_wh, plan.n, plan.height, plan.width, plan.jobs, plan.params, plan.noise)
         return collage.resample_np(packed, plan.tmp_wh, plan.n, plan.height, plan.width, plan.jobs)
 
     out = device_call()
@@ -150,7 +189,7 @@ def main():
     res["all_collages_equal_pillow"] = True
     res["host_ms"] = round(host_s * 1e3, 1)
 
-    up = int(sum(c.nbytes for c in packed))
+    up = int(sum(c.nbytes for c in packed)) + int(plan.noise.nbytes)
     down = int(out.nbytes)
     h_up, h_down = torch.empty(up, dtype=torch.uint8), torch.empty(down, dtype=torch.uint8)
     d_up, d_down = torch.empty(up, dtype=torch.uint8, device="cuda"), torch.empty(down, dtype=torch.uint8, device="cuda")

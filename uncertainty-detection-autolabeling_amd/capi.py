@@ -48,6 +48,7 @@ AUDIT_MAX_G, AUDIT_MAX_D, AUDIT_MAX_B = 1024, 1024, 1048576
 REPORT_ROWS, REPORT_MAX_K, REPORT_MAX_L, REPORT_MAX_B, REPORT_MAX_ROWS = 256, 16, 128, 4096, 1 << 22
 CLASSREP_ROWS, CLASSREP_MAX_B, CLASSREP_MAX_M, CLASSREP_MAX_C, CLASSREP_MAX_E, CLASSREP_MAX_ROWS = 256, 4096, 8, 128, 64, 1 << 22
 RESAMPLE_TILE, RESAMPLE_MAX_SIDE, RESAMPLE_MAX_SCRATCH = 32, 65536, 1 << 34
+AUGMENT_TILE, AUGMENT_ROWS, BLUR_MAX_RADIUS, BLUR_MAX_BOX = 32, 8, 16.0, 15
 
 
 class BufDesc(C.Structure):
@@ -178,6 +179,9 @@ _SIGNATURES = {
                                       _P, _P]),
     "uda_resample_np": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "uda_resample_coeffs_np": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.c_int64]),
+    "uda_collage_np": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P,
+                                 C.c_int64, _P, _P]),
+    "uda_gauss_box_np": (C.c_int, [C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "uda_label_check": (C.c_int, [_P, C.c_float, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_float, C.c_int32]),
     "uda_get_label_check": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "uda_label_check_np": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,

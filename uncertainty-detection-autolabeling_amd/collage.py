@@ -5,10 +5,13 @@ Lanczos filter and packed side by side into collages; the labels of every box th
 
 `plan_collage` restates the procedure as decisions - which crop, at which size, where - from the image sizes alone: the crops,
 the temporaries and a list of resample jobs in levels.  `crop_collage` cuts the crops on the host (a crop is a copy) and hands
-all the jobs to ONE device call, `uda_resample_np` (csrc/kernels_collage.hip), whose pixels are Pillow's bit for bit.  The writers
-produce the reference's files.  What the reference also offers and `rcc.py` as shipped switches off is not built and raises
-NotImplementedError naming the option: manual_augmentations, rand_augment_wholeimage, full_im, plot_final, the TFRecord creators
-and `generate_commands_and_create_dirs` (tfrecords / commands), weight_images_cls_dist (cb_weight)."""
+all the jobs to ONE device call, `uda_resample_np` (csrc/kernels_collage.hip), whose pixels are Pillow's bit for bit.  With
+`manual_augmentations` (parent.py:261-315, 534-537) every resized crop gets one of five random augmentations - flip, brightness,
+contrast, Gaussian blur, noise - before it is pasted: the planner draws them on the reference's stream and the call becomes
+`uda_collage_np` (csrc/kernels_augment.hip), again Pillow's pixels bit for bit.  The writers produce the reference's files.
+What the reference also offers and `rcc.py` as shipped switches off is not built and raises NotImplementedError naming the
+option: rand_augment_wholeimage, full_im, plot_final, the TFRecord creators and `generate_commands_and_create_dirs` (tfrecords /
+commands), weight_images_cls_dist (cb_weight)."""
 import ctypes as C
 import json
 import os
@@ -18,7 +21,10 @@ import numpy as np
 from . import capi
 
 MAX_BOXES_PER_COLLAGE = 100
-NOT_BUILT = ("manual_augmentations", "rand_augment_wholeimage", "full_im", "plot_final", "tfrecords", "commands", "cb_weight")
+# the ops of a uda_collage_np job (include/uda_hip.h); the reference's five augmentations in the order of its list
+OP_RESIZE, OP_FLIP, OP_BRIGHTNESS, OP_CONTRAST, OP_BLUR, OP_NOISE = range(6)
+AUGMENT_KINDS = ("flip", "brightness", "contrast", "blur", "noise")
+NOT_BUILT = ("rand_augment_wholeimage", "full_im", "plot_final", "tfrecords", "commands", "cb_weight")
 
 
 def _refuse(options):
@@ -37,16 +43,26 @@ class CollagePlan:
                plane k of the device call is crop k
     tmp_wh     [(w, h)] of the temporaries (plane ids S + t)
     jobs       [K, 7] int32 (level, source plane, destination plane, x, y, w, h), sorted by level; the outputs are the plane
-               ids S + T + n
+               ids S + T + n.  A plan made with manual_augmentations has [K, 9] jobs (.., op, arg) for uda_collage_np
+    params     [P] float64: the factors and radii the jobs' arg indexes;  noise: uint8, the noise of the op-5 jobs one after
+               another in job-list order;  augment: per crop (kind, parameter) - the kind's name and its factor or radius, None
+               for flip and noise.  Empty without manual_augmentations
     n, height, width   the collages
     labels     per collage [[class, [x1, y1, x2, y2]], ...] in the reference's float arithmetic
     crop_boxes, crop_classes   per crop what it carries, in crop coordinates (the two lists of a crop may differ in length)"""
 
-    def __init__(self, crops, tmp_wh, jobs, n, height, width, labels, crop_boxes=None, crop_classes=None):
+    def __init__(self, crops, tmp_wh, jobs, n, height, width, labels, crop_boxes=None, crop_classes=None, params=(), noise=(), augment=None):
         self.crops, self.tmp_wh, self.n, self.height, self.width, self.labels = crops, tmp_wh, n, height, width, labels
         self.crop_boxes, self.crop_classes = crop_boxes, crop_classes
-        jobs = np.asarray(jobs, np.int32).reshape(-1, 7)
+        jobs = np.asarray(jobs, np.int32).reshape(-1, 7 if augment is None else 9)
         self.jobs = np.ascontiguousarray(jobs[np.argsort(jobs[:, 0], kind="stable")])
+        self.params, self.augment = np.asarray(params, np.float64).reshape(-1), [] if augment is None else augment
+        if len(noise):                                               # per noise job, indexed by its arg -> job-list order
+            noise = [noise[a] for a in self.jobs[self.jobs[:, 7] == OP_NOISE, 8]]
+            self.jobs[self.jobs[:, 7] == OP_NOISE, 8] = np.arange(len(noise))
+            self.noise = np.concatenate([z.reshape(-1) for z in noise])
+        else:
+            self.noise = np.zeros(0, np.uint8)
 
     def images_used(self):
         return sorted({c[0] for c in self.crops})
@@ -59,11 +75,15 @@ def _size(image):
     return int(w), int(h)
 
 
-def plan_collage(images, classes, boxes, target_class, dataset="KITTI", scale=False, low_scale=0.5, high_scale=1.0, rng=None):
+def plan_collage(images, classes, boxes, target_class, dataset="KITTI", scale=False, low_scale=0.5, high_scale=1.0, rng=None,
+                 manual_augmentations=False):
     """parent.py:380-598 without pixels.  images: per image an array [h, w, 3] or (width, height); classes / boxes: per image the
     class names and the boxes - [x1, y1, x2, y2] for KITTI, [y1, x1, y2, x2] otherwise (swapped here, as the reference does).
     rng: None seeds numpy's global legacy stream with 42 and draws from it, as the reference does; a np.random.RandomState is
-    drawn from as it is.  Returns a CollagePlan."""
+    drawn from as it is.  manual_augmentations: per packed crop, after its resizes, `choice(5)` and the kind's own draw on the same
+    stream (parent.py:261-315); the augment job reads the resized crop from a temporary one level later.  A flip rewrites the
+    crop's boxes in place as the reference does - with the RESIZED width on boxes still in crop coordinates.  Returns a
+    CollagePlan."""
     if rng is None:
         np.random.seed(42)
         rng = np.random
@@ -117,9 +137,11 @@ def plan_collage(images, classes, boxes, target_class, dataset="KITTI", scale=Fa
         tmp_wh.append((int(w), int(h)))
         return ("t", len(tmp_wh) - 1)
 
-    def job(level, src, dst, x, y, w, h, dst_w, dst_h):
+    params, noise, augment = [], [], [] if manual_augmentations else None
+
+    def job(level, src, dst, x, y, w, h, dst_w, dst_h, op=OP_RESIZE, arg=0):
         if x < dst_w and y < dst_h:                                   # (a paste wholly outside pastes nothing)
-            jobs.append((level, src, dst, int(x), int(y), int(w), int(h)))
+            jobs.append((level, src, dst, int(x), int(y), int(w), int(h), op, arg))
 
     k, n = 0, 0
     while k < S:
@@ -135,16 +157,38 @@ def plan_collage(images, classes, boxes, target_class, dataset="KITTI", scale=Fa
                 raise ValueError("height and width must be > 0")
             level, img_w, img_h = 0, new_width, collage_height
             second = x_offset + new_width > collage_width
-            if second or scale:                                       # the resized crop is read again: a temporary
+            if second or scale or manual_augmentations:               # the resized crop is read again: a temporary
                 t = tmp(new_width, collage_height)
                 job(level, src, t, 0, 0, new_width, collage_height, new_width, collage_height)
                 src, level = t, level + 1
             if second:
                 img_w = collage_width - x_offset
-                if scale:
+                if scale or manual_augmentations:
                     t = tmp(img_w, img_h)
                     job(level, src, t, 0, 0, img_w, img_h, img_w, img_h)
                     src, level = t, level + 1
+            op, arg = OP_RESIZE, 0
+            if manual_augmentations:                                  # apply_manual_augmentation: np.random.choice of five, then its draw
+                kind = int(rng.choice(5))
+                op, value = kind + 1, None
+                if op == OP_FLIP:
+                    for box in original_boxes:                        # (the resized width, boxes in crop coordinates: the reference's own)
+                        box[0], box[2] = img_w - box[2], img_w - box[0]
+                elif op in (OP_BRIGHTNESS, OP_CONTRAST):
+                    value = float(rng.uniform(0.7, 1.3))
+                elif op == OP_BLUR:
+                    value = float(rng.uniform(1, 3))
+                else:
+                    noise.append(rng.randint(5, 20, (img_h, img_w, 3), dtype="uint8"))
+                    arg = len(noise) - 1
+                if value is not None:
+                    params.append(value)
+                    arg = len(params) - 1
+                augment.append((AUGMENT_KINDS[kind], value))
+                if scale:                                             # the quadrants read the augmented crop: one more temporary
+                    t = tmp(img_w, img_h)
+                    job(level, src, t, 0, 0, img_w, img_h, img_w, img_h, op, arg)
+                    src, level, op, arg = t, level + 1, OP_RESIZE, 0
             if scale:
                 quadrant_sizes = [(np.ceil(img_w * 0.75), np.ceil(img_h * 0.75)), (np.ceil(img_w * 0.25), np.ceil(img_h * 0.75)),
                                   (np.ceil(img_w * 0.75), np.ceil(img_h * 0.25)), (np.ceil(img_w * 0.25), np.ceil(img_h * 0.25))]
@@ -170,7 +214,7 @@ def plan_collage(images, classes, boxes, target_class, dataset="KITTI", scale=Fa
                             break                                     # (leaves the inner loop only, as in the reference)
                 job(level + 1, part, OUT - n, x_offset, 0, img_w, img_h, collage_width, collage_height)
             else:
-                job(level, src, OUT - n, x_offset, 0, img_w, img_h, collage_width, collage_height)
+                job(level, src, OUT - n, x_offset, 0, img_w, img_h, collage_width, collage_height, op, arg)
                 scale_x = img_w / original_width
                 scale_y = img_h / original_height
                 for cls, original_box in zip(original_classes, original_boxes):
@@ -189,30 +233,96 @@ def plan_collage(images, classes, boxes, target_class, dataset="KITTI", scale=Fa
             return p[1] if p[0] == "s" else S + p[1]
         return S + T + (OUT - p)
 
-    jobs = [(lv, plane(s), plane(d), x, y, w, h) for lv, s, d, x, y, w, h in jobs]
-    return CollagePlan(crops, tmp_wh, jobs, n, collage_height, collage_width, labels_all, crop_boxes, crop_classes)
+    jobs = [(lv, plane(s), plane(d)) + tuple(rest if manual_augmentations else rest[:4]) for lv, s, d, *rest in jobs]
+    return CollagePlan(crops, tmp_wh, jobs, n, collage_height, collage_width, labels_all, crop_boxes, crop_classes, params, noise, augment)
+
+
+def _call_arrays(who, src_planes, tmp_wh, n, height, width, jobs, columns):
+    planes = [np.ascontiguousarray(p, np.uint8) for p in src_planes]
+    for i, p in enumerate(planes):
+        if p.ndim != 3 or p.shape[2] != 3:
+            raise ValueError("%s: source plane %d has shape %s, [h, w, 3] is taken" % (who, i, p.shape))
+    src_wh = np.asarray([(p.shape[1], p.shape[0]) for p in planes], np.int32).reshape(-1, 2)
+    pix = np.concatenate([p.reshape(-1) for p in planes]) if planes else np.zeros(0, np.uint8)
+    tmp = np.ascontiguousarray(np.asarray(tmp_wh, np.int32).reshape(-1, 2))
+    jobs = np.ascontiguousarray(np.asarray(jobs, np.int32).reshape(-1, columns))
+    if n < 1 or height < 1 or width < 1:
+        raise ValueError("%s: %d output planes of %d x %d" % (who, n, width, height))
+    out = np.empty((int(n), int(height), int(width), 3), np.uint8)          # (the call writes all of it, or fails)
+    return planes, src_wh, pix, tmp, jobs, out
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a.size else None
 
 
 def resample_np(src_planes, tmp_wh, n, height, width, jobs, device=0):
     """uda_resample_np: src_planes a list of uint8 arrays [h, w, 3]; tmp_wh [(w, h)]; jobs [K, 7] int32 (include/uda_hip.h).
     Returns the n output planes [n, height, width, 3] uint8."""
-    planes = [np.ascontiguousarray(p, np.uint8) for p in src_planes]
-    for i, p in enumerate(planes):
-        if p.ndim != 3 or p.shape[2] != 3:
-            raise ValueError("resample_np: source plane %d has shape %s, [h, w, 3] is taken" % (i, p.shape))
-    src_wh = np.asarray([(p.shape[1], p.shape[0]) for p in planes], np.int32).reshape(-1, 2)
-    pix = np.concatenate([p.reshape(-1) for p in planes]) if planes else np.zeros(0, np.uint8)
-    tmp = np.ascontiguousarray(np.asarray(tmp_wh, np.int32).reshape(-1, 2))
-    jobs = np.ascontiguousarray(np.asarray(jobs, np.int32).reshape(-1, 7))
-    if n < 1 or height < 1 or width < 1:
-        raise ValueError("resample_np: %d output planes of %d x %d" % (n, width, height))
-    out = np.empty((int(n), int(height), int(width), 3), np.uint8)          # (the call writes all of it, or fails)
+    planes, src_wh, pix, tmp, jobs, out = _call_arrays("resample_np", src_planes, tmp_wh, n, height, width, jobs, 7)
     lib = capi.load()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None     # noqa: E731
-    rc = lib.uda_resample_np(int(device), len(planes), p(src_wh), p(pix), len(tmp), p(tmp), int(n), int(height), int(width),
-                             len(jobs), p(jobs), out.ctypes.data_as(C.c_void_p))
+    rc = lib.uda_resample_np(int(device), len(planes), _ptr(src_wh), _ptr(pix), len(tmp), _ptr(tmp), int(n), int(height), int(width),
+                             len(jobs), _ptr(jobs), out.ctypes.data_as(C.c_void_p))
     capi.check(lib, None, rc, "uda_resample_np")
     return out
+
+
+def collage_np(src_planes, tmp_wh, n, height, width, jobs, params=(), noise=None, device=0):
+    """uda_collage_np: as `resample_np` with jobs [K, 9] int32 (.., op, arg), params the doubles the ops 2-4 index and noise the
+    uint8 bytes of the op-5 jobs in job-list order (include/uda_hip.h).  Returns the n output planes [n, height, width, 3] uint8."""
+    planes, src_wh, pix, tmp, jobs, out = _call_arrays("collage_np", src_planes, tmp_wh, n, height, width, jobs, 9)
+    params = np.ascontiguousarray(np.asarray(params, np.float64).reshape(-1))
+    noise = np.zeros(0, np.uint8) if noise is None else np.ascontiguousarray(np.asarray(noise, np.uint8).reshape(-1))
+    lib = capi.load()
+    rc = lib.uda_collage_np(int(device), len(planes), _ptr(src_wh), _ptr(pix), len(tmp), _ptr(tmp), int(n), int(height), int(width),
+                            len(jobs), _ptr(jobs), len(params), _ptr(params), noise.size, _ptr(noise), out.ctypes.data_as(C.c_void_p))
+    capi.check(lib, None, rc, "uda_collage_np")
+    return out
+
+
+def gauss_box(radius):
+    """uda_gauss_box_np (host only): Pillow's box blur behind GaussianBlur(radius) -> (fr float32, ww, fw)."""
+    lib = capi.load()
+    fr, ww, fw = C.c_float(), C.c_uint32(), C.c_uint32()
+    capi.check(lib, None, lib.uda_gauss_box_np(float(radius), C.byref(fr), C.byref(ww), C.byref(fw)), "uda_gauss_box_np")
+    return np.float32(fr.value), ww.value, fw.value
+
+
+def augment_np(plane, kind, value=None, noise=None, device=0):
+    """One augmentation of one plane [h, w, 3] uint8 on the device: kind one of AUGMENT_KINDS; value the factor (brightness,
+    contrast) or the radius (blur); noise a uint8 array of the plane's shape (noise).  Returns the augmented plane."""
+    plane = np.ascontiguousarray(plane, np.uint8)
+    if kind not in AUGMENT_KINDS:
+        raise ValueError("augment_np: kind %r, one of %s is taken" % (kind, AUGMENT_KINDS))
+    op = AUGMENT_KINDS.index(kind) + 1
+    if op in (OP_BRIGHTNESS, OP_CONTRAST, OP_BLUR) and value is None:
+        raise ValueError("augment_np: %s takes a value" % kind)
+    if op == OP_NOISE and (noise is None or np.shape(noise) != plane.shape):
+        raise ValueError("augment_np: noise takes a uint8 array of the plane's shape")
+    h, w = plane.shape[:2]
+    return collage_np([plane], [], 1, h, w, [(0, 0, 1, 0, 0, w, h, op, 0)], [value] if value is not None else [],
+                      noise if op == OP_NOISE else None, device=device)[0]
+
+
+def apply_manual_augmentation(image, boxes, rng=None, device=0):
+    """The reference's Parent_SSL.apply_manual_augmentation (parent.py:261-315) on an array [h, w, 3] uint8: one of the five
+    augmentations drawn from `rng` (None: numpy's global legacy stream, as the reference), run on the device.  A flip rewrites
+    `boxes` ([[x1, y1, x2, y2], ...]) in place, as the reference does.  Returns (image, boxes)."""
+    rng = np.random if rng is None else rng
+    image = np.ascontiguousarray(image, np.uint8)
+    h, w = image.shape[:2]
+    kind = AUGMENT_KINDS[int(rng.choice(5))]
+    value = noise = None
+    if kind == "flip":
+        for box in boxes:
+            box[0], box[2] = w - box[2], w - box[0]
+    elif kind in ("brightness", "contrast"):
+        value = float(rng.uniform(0.7, 1.3))
+    elif kind == "blur":
+        value = float(rng.uniform(1, 3))
+    else:
+        noise = rng.randint(5, 20, (h, w, 3), dtype="uint8")
+    return augment_np(image, kind, value, noise, device=device), boxes
 
 
 def resample_coeffs(in_size, out_size):
@@ -238,13 +348,14 @@ class Collage:
 
 
 def crop_collage(images, classes, boxes, target_class, dataset="KITTI", scale=False, low_scale=0.5, high_scale=1.0, rng=None, sizes=None,
-                 resample=None, device=0, **not_built):
+                 resample=None, device=0, manual_augmentations=False, **not_built):
     """The reference's crop_collage up to the collages and their labels.
 
     images: per image a uint8 array [h, w, 3] or a path; with paths only the images that contribute a crop are decoded
     (infer_lib.read_images), and `sizes` [(width, height)] may spare opening the others for their size.  classes / boxes /
     target_class / dataset / scale / low_scale / high_scale / rng: as `plan_collage`.  resample: another implementation of
-    `resample_np` (same arguments; the tests pass a numpy mirror).  Returns a Collage."""
+    `resample_np` (same arguments; the tests pass a numpy mirror) - with manual_augmentations of `collage_np`, which is then
+    called with the plan's [K, 9] jobs, params and noise.  Returns a Collage."""
     _refuse(not_built)
     images = list(images)
     if sizes is None:
@@ -256,7 +367,7 @@ def crop_collage(images, classes, boxes, target_class, dataset="KITTI", scale=Fa
                     sizes.append(f.size)
             else:
                 sizes.append(_size(np.asarray(im)))
-    plan = plan_collage(sizes, classes, boxes, target_class, dataset, scale, low_scale, high_scale, rng)
+    plan = plan_collage(sizes, classes, boxes, target_class, dataset, scale, low_scale, high_scale, rng, manual_augmentations)
     used = plan.images_used()
     paths = [i for i in used if isinstance(images[i], (str, os.PathLike))]
     decoded = {}
@@ -267,7 +378,9 @@ def crop_collage(images, classes, boxes, target_class, dataset="KITTI", scale=Fa
     planes = [pixels[i][y0:y1, x0:x1] for i, x0, y0, x1, y1 in plan.crops]
     if plan.n == 0:
         return Collage(np.zeros((0, plan.height, plan.width, 3), np.uint8), [], plan)
-    out = (resample or resample_np)(planes, plan.tmp_wh, plan.n, plan.height, plan.width, plan.jobs, **({} if resample else {"device": device}))
+    args = (planes, plan.tmp_wh, plan.n, plan.height, plan.width, plan.jobs) + ((plan.params, plan.noise) if manual_augmentations else ())
+    run = resample or (collage_np if manual_augmentations else resample_np)
+    out = run(*args, **({} if resample else {"device": device}))
     return Collage(out, plan.labels, plan)
 
 

@@ -701,6 +701,41 @@ void launch_resample_passes(const ResamplePass* passes, int n_pass, int n_tiles,
 int resample_ksize(int in_size, int out_size);
 void resample_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk);
 
+// RCC's manual augmentations (reference ssl_utils/parent.py:261-315) between a collage's resizes and pastes: kernels_augment.hip.
+// Every address is a byte offset into the call's one device allocation, as for the resample passes.
+enum { AUG_THREADS = 256, AUG_TILE = UDA_AUGMENT_TILE, AUG_ROWS = AUG_THREADS / AUG_TILE, AUG_MEAN_PIX = 16 * AUG_THREADS,
+       BLUR_LINES = UDA_AUGMENT_TILE, BLUR_HALO = 3 * (UDA_BLUR_MAX_BOX + 1), BLUR_EXT = AUG_TILE + 2 * BLUR_HALO,
+       BLUR_LDS = 2 * BLUR_LINES * 3 * BLUR_EXT };
+enum { AUG_COPY = 0, AUG_FLIP = 1, AUG_BLEND = 2, AUG_BLEND_CLIP = 3, AUG_ADD = 4 };
+struct AugJob {                 // one pointwise job: flip, blend, add bytes (and the copy a blur of radius 0 is)
+  int64_t src, dst;             // first byte of the source plane / of the job's rectangle in the destination
+  int64_t src_stride, dst_stride;
+  int64_t noise;                // AUG_ADD: first byte of the job's noise in the call's noise array
+  int64_t n_pix;                // pixels of the source plane (the contrast mean's divisor)
+  int32_t w, cw, ch;            // the source's width; what is written (clipped)
+  int32_t kind;
+  float a;                      // AUG_BLEND*: f32(factor)
+  int32_t mean;                 // AUG_BLEND*: slot of the plane's luma sum (contrast), -1: the degenerate is black (brightness)
+  int32_t tile0, tiles_x;       // first block of the job in its launch; tiles along x
+};
+struct AugMeanJob {             // the luma sum of one contrast job's source plane
+  int64_t src, n_pix;
+  int32_t slot, tile0;
+};
+struct BlurPass {               // one stage (three box passes along one axis) of one blur job
+  int64_t src, dst, src_stride, dst_stride;
+  uint32_t ww, fw;
+  int32_t r;                    // int(fr)
+  int32_t n;                    // the line's true length
+  int32_t n_out, n_lines;       // what is written: positions 0 .. n_out - 1 (clipped), lines across (clipped)
+  int32_t tile0, tiles_pos;
+};
+void launch_augment_means(const AugMeanJob* jobs, int n_jobs, int n_tiles, unsigned long long* sums, const uint8_t* base, hipStream_t s);
+void launch_augment_points(const AugJob* jobs, int n_jobs, int n_tiles, const unsigned long long* sums, const uint8_t* noise, uint8_t* base,
+                           hipStream_t s);
+void launch_blur_stages(const BlurPass* passes, int n_pass, int n_tiles, bool vertical, uint8_t* base, hipStream_t s);
+void gauss_box(double radius, float* fr, uint32_t* ww, uint32_t* fw);
+
 struct NmsArgs {
   const float* boxes;    // [n, K, 4]
   float* stale;          // [n, K]  working scores (dead = -inf)

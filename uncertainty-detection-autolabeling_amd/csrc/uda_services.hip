@@ -1,6 +1,6 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
 // COCO matching, the label check and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
-// on scratch device memory of their own (the *_np twins, the thresholding objective and report, the post-thresholding heat maps and tallies, the pruning neighbours, the pseudo-label audit, the uncertainty report, the classification report, the collage resample, uda_nms, uda_debug_pw,
+// on scratch device memory of their own (the *_np twins, the thresholding objective and report, the post-thresholding heat maps and tallies, the pruning neighbours, the pseudo-label audit, the uncertainty report, the classification report, the collage resample and augmentations, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
 //
@@ -1485,10 +1485,22 @@ static void resample_tiles(ResamplePass& p, const ResampleTables& tabs, bool ver
   *n_tiles += p.tiles_pos * ((p.n_lines + lines - 1) / lines);
 }
 
-extern "C" int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T, const int32_t* tmp_wh,
-                               int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, uint8_t* out) {
-  const char* who = "uda_resample_np";
+extern "C" int uda_gauss_box_np(double radius, float* fr, uint32_t* ww, uint32_t* fw) {
+  const char* who = "uda_gauss_box_np";
+  if (!fr || !ww || !fw) return fail(nullptr, "%s: NULL output", who);
+  if (!std::isfinite(radius) || radius < 0) return fail(nullptr, "%s: a radius of %g, finite and >= 0 is taken", who, radius);
+  gauss_box(radius, fr, ww, fw);
+  return 0;
+}
+
+// Both collage entry points: a job row has JS = 7 values (uda_resample_np: every job is a resize) or 9 (uda_collage_np: op, arg).
+static int collage_run(const char* who, int JS, int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T,
+                       const int32_t* tmp_wh, int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, int32_t n_params,
+                       const double* params, int64_t noise_bytes, const uint8_t* noise, uint8_t* out) {
   const int MAXS = UDA_RESAMPLE_MAX_SIDE;
+  auto op_of = [&](int k) { return JS == 9 ? jobs[JS * (size_t)k + 7] : 0; };
+  if (n_params < 0 || noise_bytes < 0 || (n_params && !params) || (noise_bytes && !noise))
+    return fail(nullptr, "%s: %d parameters, %lld noise bytes, or a NULL array of them", who, n_params, (long long)noise_bytes);
   if (S < 0 || T < 0 || K < 0 || N < 1) return fail(nullptr, "%s: %d source planes, %d temporaries, %d output planes, %d jobs", who, S, T, N, K);
   if (H < 1 || H > MAXS || W < 1 || W > MAXS) return fail(nullptr, "%s: output planes of %d x %d, sides of 1..%d are taken", who, W, H, MAXS);
   if (!out || (S && (!src_wh || !src_pix)) || (T && !tmp_wh) || (K && !jobs)) return fail(nullptr, "%s: NULL array", who);
@@ -1510,12 +1522,13 @@ extern "C" int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh,
   // the jobs: ids, sizes, levels; per level no read of a plane the level writes, no pixel written twice
   std::vector<int> wrote((size_t)P, -1);
   std::vector<int> order;
+  int64_t noise_need = 0;
   for (int k0 = 0; k0 < K;) {
     int k1 = k0;
-    const int level = jobs[7 * (size_t)k0];
-    if (k0 && level < jobs[7 * (size_t)(k0 - 1)]) return fail(nullptr, "%s: the level of job %d is %d after %d: levels ascend", who, k0, level, jobs[7 * (size_t)(k0 - 1)]);
-    for (; k1 < K && jobs[7 * (size_t)k1] == level; ++k1) {
-      const int32_t* j = jobs + 7 * (size_t)k1;
+    const int level = jobs[JS * (size_t)k0];
+    if (k0 && level < jobs[JS * (size_t)(k0 - 1)]) return fail(nullptr, "%s: the level of job %d is %d after %d: levels ascend", who, k0, level, jobs[JS * (size_t)(k0 - 1)]);
+    for (; k1 < K && jobs[JS * (size_t)k1] == level; ++k1) {
+      const int32_t* j = jobs + JS * (size_t)k1;
       if (j[1] < 0 || j[1] >= P) return fail(nullptr, "%s: job %d reads plane %d, there are %d", who, k1, j[1], P);
       if (j[2] < S || j[2] >= P) return fail(nullptr, "%s: job %d writes plane %d, the planes %d..%d can be written", who, k1, j[2], S, P - 1);
       if (j[5] < 1 || j[6] < 1 || j[5] > MAXS || j[6] > MAXS) return fail(nullptr, "%s: job %d resizes to %d x %d, sides of 1..%d are taken", who, k1, j[5], j[6], MAXS);
@@ -1524,19 +1537,32 @@ extern "C" int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh,
         return fail(nullptr, "%s: job %d pastes at (%d, %d), outside its destination of %d x %d", who, k1, j[3], j[4], d.w, d.h);
       wrote[j[2]] = k0;
       const ResamplePlane& f = pl[j[1]];
-      if (j[5] != f.w && j[6] != f.h)
-        scratch += resample_vertical_first(f.w, f.h, j[6]) ? (int64_t)f.w * std::min(j[6], d.h - j[4]) * 3 : (int64_t)std::min(j[5], d.w - j[3]) * f.h * 3;
+      const int op = op_of(k1);
+      if (op < 0 || op > 5) return fail(nullptr, "%s: job %d has op %d, 0..5 are known", who, k1, op);
+      if (op && (j[5] != f.w || j[6] != f.h))
+        return fail(nullptr, "%s: job %d (op %d) writes %d x %d from a plane of %d x %d: an augmentation keeps the size", who, k1, op, j[5], j[6], f.w, f.h);
+      if (op >= 2 && op <= 4) {
+        if (j[8] < 0 || j[8] >= n_params) return fail(nullptr, "%s: job %d (op %d) has arg %d, there are %d parameters", who, k1, op, j[8], n_params);
+        const double v = params[j[8]];
+        if (!std::isfinite(v) || v < 0) return fail(nullptr, "%s: job %d (op %d) has the parameter %g, finite and >= 0 is taken", who, k1, op, v);
+        if (op == 4 && v > UDA_BLUR_MAX_RADIUS)
+          return fail(nullptr, "%s: job %d blurs with radius %g, at most %g is taken", who, k1, v, (double)UDA_BLUR_MAX_RADIUS);
+        if (op == 4) scratch += (int64_t)std::min(j[5], d.w - j[3]) * f.h * 3;
+      }
+      if (op == 5) noise_need += (int64_t)j[5] * j[6] * 3;
+      if (op == 0 && j[5] != f.w && j[6] != f.h)
+        scratch +=resample_vertical_first(f.w, f.h, j[6]) ? (int64_t)f.w * std::min(j[6], d.h - j[4]) * 3 : (int64_t)std::min(j[5], d.w - j[3]) * f.h * 3;
     }
     order.clear();
     for (int k = k0; k < k1; ++k) {
-      if (wrote[jobs[7 * (size_t)k + 1]] == k0)
-        return fail(nullptr, "%s: job %d reads plane %d, which a job of its own level %d writes", who, k, jobs[7 * (size_t)k + 1], level);
+      if (wrote[jobs[JS * (size_t)k + 1]] == k0)
+        return fail(nullptr, "%s: job %d reads plane %d, which a job of its own level %d writes", who, k, jobs[JS * (size_t)k + 1], level);
       order.push_back(k);
     }
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return jobs[7 * (size_t)a + 2] < jobs[7 * (size_t)b + 2]; });
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return jobs[JS * (size_t)a + 2] < jobs[JS * (size_t)b + 2]; });
     for (size_t a = 0; a < order.size(); ++a)
-      for (size_t b = a + 1; b < order.size() && jobs[7 * (size_t)order[b] + 2] == jobs[7 * (size_t)order[a] + 2]; ++b) {
-        const int32_t *ja = jobs + 7 * (size_t)order[a], *jb = jobs + 7 * (size_t)order[b];
+      for (size_t b = a + 1; b < order.size() && jobs[JS * (size_t)order[b] + 2] == jobs[JS * (size_t)order[a] + 2]; ++b) {
+        const int32_t *ja = jobs + JS * (size_t)order[a], *jb = jobs + JS * (size_t)order[b];
         if (ja[3] < jb[3] + jb[5] && jb[3] < ja[3] + ja[5] && ja[4] < jb[4] + jb[6] && jb[4] < ja[4] + ja[6])
           return fail(nullptr, "%s: jobs %d and %d of level %d write the same pixels of plane %d", who, std::min(order[a], order[b]),
                       std::max(order[a], order[b]), level, ja[2]);
@@ -1545,21 +1571,62 @@ extern "C" int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh,
   }
   if (scratch > UDA_RESAMPLE_MAX_SCRATCH)
     return fail(nullptr, "%s: %lld bytes of scratch, at most %lld a call", who, (long long)scratch, (long long)UDA_RESAMPLE_MAX_SCRATCH);
-  // the passes, level by level: the horizontal ones of a level, then its vertical ones
+  if (noise_need != noise_bytes)
+    return fail(nullptr, "%s: %lld noise bytes, the op-5 jobs take %lld", who, (long long)noise_bytes, (long long)noise_need);
+  // the passes, level by level: the horizontal ones of a level, then its vertical ones; then the level's augmentations - the
+  // contrast means, the pointwise jobs (which read the means), the blurs' x stages and their y stages
   ResampleTables tabs;
   std::vector<ResamplePass> passes;
-  struct Launch { int first, count, tiles; bool vertical; };
+  std::vector<AugMeanJob> means;
+  std::vector<AugJob> points;
+  std::vector<BlurPass> blurs;
+  enum { L_RESAMPLE, L_MEAN, L_POINT, L_BLUR };
+  struct Launch { int first, count, tiles; bool vertical; int what = L_RESAMPLE; };
   std::vector<Launch> launches;
+  int64_t noise_at = 0;
+  int n_means = 0;
   for (int k0 = 0; k0 < K;) {
     int k1 = k0;
-    while (k1 < K && jobs[7 * (size_t)k1] == jobs[7 * (size_t)k0]) ++k1;
+    while (k1 < K && jobs[JS * (size_t)k1] == jobs[JS * (size_t)k0]) ++k1;
     std::vector<ResamplePass> vert, late;
+    std::vector<AugMeanJob> lvl_means;
+    std::vector<AugJob> lvl_points;
+    std::vector<BlurPass> blur_x, blur_y;
     const int first = (int)passes.size();
     for (int k = k0; k < k1; ++k) {
-      const int32_t* j = jobs + 7 * (size_t)k;
+      const int32_t* j = jobs + JS * (size_t)k;
       const ResamplePlane &s = pl[j[1]], &d = pl[j[2]];
       const int w = j[5], h = j[6], cw = std::min(w, d.w - j[3]), ch = std::min(h, d.h - j[4]);
       const int64_t to = d.off + ((int64_t)j[4] * d.w + j[3]) * 3;
+      if (const int op = op_of(k)) {
+        float fr = 0.0f;
+        uint32_t ww = 0, fw = 0;
+        if (op == 4) gauss_box(params[j[8]], &fr, &ww, &fw);
+        if (op == 4 && fr != 0.0f) {                    // the x stage's result, cw x h, in scratch; the y stage reads it
+          if ((int)fr > UDA_BLUR_MAX_BOX) return fail(nullptr, "%s: job %d blurs with a box of %d, at most %d fit a tile", who, k, (int)fr, (int)UDA_BLUR_MAX_BOX);
+          BlurPass bx{s.off, bytes, (int64_t)s.w * 3, (int64_t)cw * 3, ww, fw, (int)fr, s.w, cw, s.h, 0, 0};
+          BlurPass by{bytes, to, (int64_t)cw * 3, (int64_t)d.w * 3, ww, fw, (int)fr, s.h, ch, cw, 0, 0};
+          blur_x.push_back(bx);
+          blur_y.push_back(by);
+          bytes += (int64_t)cw * s.h * 3;
+          continue;
+        }
+        AugJob a{};
+        a.src = s.off; a.dst = to; a.src_stride = (int64_t)s.w * 3; a.dst_stride = (int64_t)d.w * 3;
+        a.n_pix = (int64_t)s.w * s.h; a.w = s.w; a.cw = cw; a.ch = ch; a.mean = -1;
+        a.kind = op == 1 ? AUG_FLIP : op == 5 ? AUG_ADD : AUG_COPY;
+        if (op == 2 || op == 3) {
+          a.a = (float)params[j[8]];
+          a.kind = a.a >= 0.0f && a.a <= 1.0f ? AUG_BLEND : AUG_BLEND_CLIP;
+        }
+        if (op == 3) {
+          a.mean = n_means++;
+          lvl_means.push_back(AugMeanJob{s.off, a.n_pix, a.mean, 0});
+        }
+        if (op == 5) { a.noise = noise_at; noise_at += (int64_t)w * h * 3; }
+        lvl_points.push_back(a);
+        continue;
+      }
       if (w != s.w && h != s.h && resample_vertical_first(s.w, s.h, h)) {   // the vertical result, s.w x ch, in scratch; x after it
         vert.push_back(resample_pass(tabs, s.off, (int64_t)s.w * 3, bytes, (int64_t)s.w * 3, s.h, h, ch, s.w));
         late.push_back(resample_pass(tabs, bytes, (int64_t)s.w * 3, to, (int64_t)d.w * 3, s.w, w, cw, ch));
@@ -1579,25 +1646,79 @@ extern "C" int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh,
     passes.insert(passes.end(), vert.begin(), vert.end());
     if (!late.empty()) launches.push_back(Launch{(int)passes.size(), (int)late.size(), 0, false});
     passes.insert(passes.end(), late.begin(), late.end());
+    if (!lvl_means.empty()) {
+      Launch l{(int)means.size(), (int)lvl_means.size(), 0, false, L_MEAN};
+      for (AugMeanJob& m : lvl_means) {
+        m.tile0 = l.tiles;
+        l.tiles += (int)((m.n_pix + AUG_MEAN_PIX - 1) / AUG_MEAN_PIX);
+      }
+      means.insert(means.end(), lvl_means.begin(), lvl_means.end());
+      launches.push_back(l);
+    }
+    if (!lvl_points.empty()) {
+      Launch l{(int)points.size(), (int)lvl_points.size(), 0, false, L_POINT};
+      for (AugJob& a : lvl_points) {
+        a.tile0 = l.tiles;
+        a.tiles_x = (a.cw + AUG_TILE - 1) / AUG_TILE;
+        l.tiles += a.tiles_x * ((a.ch + AUG_ROWS - 1) / AUG_ROWS);
+      }
+      points.insert(points.end(), lvl_points.begin(), lvl_points.end());
+      launches.push_back(l);
+    }
+    for (int vertical = 0; vertical < 2; ++vertical) {
+      std::vector<BlurPass>& stage = vertical ? blur_y : blur_x;
+      if (stage.empty()) continue;
+      Launch l{(int)blurs.size(), (int)stage.size(), 0, vertical != 0, L_BLUR};
+      for (BlurPass& b : stage) {
+        b.tile0 = l.tiles;
+        b.tiles_pos = (b.n_out + AUG_TILE - 1) / AUG_TILE;
+        l.tiles += b.tiles_pos * ((b.n_lines + BLUR_LINES - 1) / BLUR_LINES);
+      }
+      blurs.insert(blurs.end(), stage.begin(), stage.end());
+      launches.push_back(l);
+    }
     k0 = k1;
   }
   tabs.fill();
   for (Launch& l : launches)
-    for (int i = 0; i < l.count; ++i) resample_tiles(passes[l.first + i], tabs, l.vertical, &l.tiles);
+    if (l.what == L_RESAMPLE)
+      for (int i = 0; i < l.count; ++i) resample_tiles(passes[l.first + i], tabs, l.vertical, &l.tiles);
   DevScratch s(device);
   hipStream_t st = s.stream();
   uint8_t* base = s.alloc<uint8_t>((size_t)bytes);
   const ResamplePass* d_pass = s.upload(passes.data(), passes.size(), st);
   const int32_t* d_pool = s.upload(tabs.pool.data(), tabs.pool.size(), st);
+  const AugMeanJob* d_means = s.upload(means.data(), means.size(), st);
+  const AugJob* d_points = s.upload(points.data(), points.size(), st);
+  const BlurPass* d_blurs = s.upload(blurs.data(), blurs.size(), st);
+  const uint8_t* d_noise = noise_bytes ? s.upload(noise, (size_t)noise_bytes, st) : nullptr;
+  unsigned long long* d_sums = n_means ? s.alloc<unsigned long long>((size_t)n_means) : nullptr;
   if (int rc = scratch_done(nullptr, who, s)) return rc;
   if (src_bytes && s.ok()) s.err = hipMemcpyAsync(base, src_pix, (size_t)src_bytes, hipMemcpyHostToDevice, st);
   s.zero(base + src_bytes, (size_t)(out_off + out_bytes - src_bytes), st);
-  for (const Launch& l : launches)
-    if (s.ok()) launch_resample_passes(d_pass + l.first, l.count, l.tiles, l.vertical, d_pool, base, st);
+  if (n_means) s.zero(d_sums, (size_t)n_means * sizeof(unsigned long long), st);
+  for (const Launch& l : launches) {
+    if (!s.ok()) break;
+    if (l.what == L_RESAMPLE) launch_resample_passes(d_pass + l.first, l.count, l.tiles, l.vertical, d_pool, base, st);
+    else if (l.what == L_MEAN) launch_augment_means(d_means + l.first, l.count, l.tiles, d_sums, base, st);
+    else if (l.what == L_POINT) launch_augment_points(d_points + l.first, l.count, l.tiles, d_sums, d_noise, base, st);
+    else launch_blur_stages(d_blurs + l.first, l.count, l.tiles, l.vertical, base, st);
+  }
   s.sync(st);
   if (int rc = scratch_done(nullptr, who, s)) return rc;
   s.download(out, base + out_off, (size_t)out_bytes);
   return scratch_done(nullptr, who, s);
+}
+
+extern "C" int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T, const int32_t* tmp_wh,
+                               int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, uint8_t* out) {
+  return collage_run("uda_resample_np", 7, device, S, src_wh, src_pix, T, tmp_wh, N, H, W, K, jobs, 0, nullptr, 0, nullptr, out);
+}
+
+extern "C" int uda_collage_np(int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T, const int32_t* tmp_wh,
+                              int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, int32_t P, const double* params,
+                              int64_t noise_bytes, const uint8_t* noise, uint8_t* out) {
+  return collage_run("uda_collage_np", 9, device, S, src_wh, src_pix, T, tmp_wh, N, H, W, K, jobs, P, params, noise_bytes, noise, out);
 }
 
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,
