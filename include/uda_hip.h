@@ -47,6 +47,8 @@
  *   uda_collage_np        <- the same with Parent_SSL.apply_manual_augmentation between resize and paste: Image.transpose,
  *                            ImageEnhance.Brightness / Contrast, ImageFilter.GaussianBlur and the noise add
  *                            (ssl_utils/parent.py:261-315, 534-537)
+ *   uda_kde_eval_np       <- the scipy.stats.gaussian_kde evaluated on a mesh by EpistemicVSAleatoric.get_plot_grid
+ *                            (uncertainty_ep_vs_al.py:361-375), for every configuration of a comparison in one call
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via
  * uda_last_error); inputs are borrowed, outputs are caller-allocated; a handle owns one
@@ -700,6 +702,40 @@ int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int32_t N, int
 #define UDA_KNN_MAX_PAIRS (1ll << 38)  /* sum of n_b * m_b per call */
 int uda_nn_dist2_np(int32_t device, int32_t D, int32_t B, const double* queries, const int64_t* q_off, const double* refs,
                     const int64_t* r_off, const uint8_t* self, double* d2);
+
+/* Gaussian KDE evaluation: the expensive step of the epistemic-vs-aleatoric comparison (EpistemicVSAleatoric.get_plot_grid,
+ * uncertainty_ep_vs_al.py:361-375: scipy.stats.gaussian_kde on a 100 x 100 mesh) and `kde.pdf` in general - for B independent
+ * problems in one call, the sum of Gaussian terms of every evaluation point over the problem's data rows, in float64, without a
+ * handle.  Whitening and normalisation are the caller's, split as scipy splits them (epal.py): rows and points arrive as
+ * solve_triangular(cho_cov, x, lower=True), and the caller multiplies the sum by (2 pi)^(-D/2) / prod(diag(cho_cov)).
+ *   problems   problem b has n_b = d_off[b + 1] - d_off[b] data rows, rows d_off[b].. of data [d_off[B], D] and of weight
+ *              [d_off[B]], and m_b = p_off[b + 1] - p_off[b] evaluation points, rows p_off[b].. of points [p_off[B], D];
+ *              d_off[0] = p_off[0] = 0
+ *   term       arg(i, j) = ((p0 - d0)^2 + (p1 - d1)^2) + ... over the D coordinates in ascending order; every subtraction,
+ *              product and sum is rounded on its own (never fused).  term(i, j) = w_i * exp(arg * -0.5), exp in float64 (within
+ *              an ulp; no fast or float variant); weight == NULL: every w_i is 1 and the multiplication is left out
+ *   sum        sum[p_off[b] + j] = the sum of term(i, j) over the rows i of problem b, in an order that is a function of n_b
+ *              alone: the rows are cut into runs of UDA_KDE_RUN, aligned to the problem's first row (the last run may be
+ *              short); a run is summed sequentially from 0.0, row by row; the run sums are folded as the zero-padded pairwise
+ *              tree of uda_uncert_report_np (numpy: b = b[0::2] + b[1::2] until one value is left).  Nothing depends on how
+ *              points or rows are dealt to threads, blocks or launches: a point gives the same bits in a call of its own,
+ *              inside a batch of other problems and at any position of `points`.  Terms that underflow count as what exp gives
+ *   limits     1 <= D <= UDA_KDE_MAX_D, 1 <= B <= UDA_KDE_MAX_B, offsets ascending from 0 with 1 <= n_b <= UDA_KDE_MAX_N and
+ *              0 <= m_b, and the sum of n_b * m_b at most UDA_KDE_MAX_PAIRS; anything else is refused, never truncated, and sum
+ *              stays untouched.  UDA_KDE_MAX_PAIRS is there so that one call does not occupy a shared card for long; the time
+ *              it corresponds to has NOT been measured.  Values must be finite (the Python layer checks)
+ *   scratch    allocated and freed inside the call: rows, weights and points, 8 * ((D + 1) * d_off[B] + D * p_off[B]) bytes, the
+ *              result, 8 * p_off[B], the run sums, 8 bytes per (run, point) of every problem - at most 8 * (UDA_KDE_MAX_PAIRS /
+ *              UDA_KDE_RUN + p_off[B]) - the offsets, 24 * (B + 1), and 16 bytes per work item and 8 per block of points.
+ * UDA_KDE_POINTS points make a block, one per thread; one run of data rows and weights is staged in LDS at a time. */
+#define UDA_KDE_POINTS 256
+#define UDA_KDE_RUN 256
+#define UDA_KDE_MAX_D 4
+#define UDA_KDE_MAX_N 1048576          /* data rows per problem */
+#define UDA_KDE_MAX_B 4096             /* problems per call */
+#define UDA_KDE_MAX_PAIRS (1ll << 36)  /* sum of n_b * m_b per call */
+int uda_kde_eval_np(int32_t device, int32_t D, int32_t B, const double* data, const int64_t* d_off, const double* weight,
+                    const double* points, const int64_t* p_off, double* sum);
 
 /* Pseudo-label audit: how the STAC teacher's pseudo labels compare with the ground truth (Parent_SSL.extract_pseudo_gt_data and
  * _percls_analysis, ssl_utils/parent.py:1567-1813; its members feed ThreeDproblem.corrected_pseudo, 3d.py:80-255, and

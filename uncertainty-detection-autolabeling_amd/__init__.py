@@ -13,5 +13,6 @@ Modules:
   uncertainty_report  the validation uncertainty report: ECE, NLL, coverage, RMSUE, sharpness of every sigma column from one device call
   class_report    the classification calibration report: reliability bins, ECE, MCE, Brier, NLL, SCE of every probability table from one device call
   thresholding    failure-recognition weights and threshold from validation rows (roc_objective, UncertOptimal, autolabel_verdict)
+  epal            the epistemic-vs-aleatoric comparison: grid search, corner detections, metric lists and the Gaussian KDE of all configurations from one device call
   post_thresholding  where the threshold acts: the heat maps, spider metrics and image lists after thresholding (heat_maps, spider_metrics, rank_images)
 """

@@ -38,6 +38,7 @@ HEAT_TILE_H, HEAT_TILE_W, HEAT_CHUNK = 32, 64, 256
 HEAT_MAX_MAPS, HEAT_MAX_RECTS, HEAT_MAX_VALUES, HEAT_MAX_SELS, HEAT_MAX_PIXELS = 16, 4, 16, 8, 4194304
 PRUNE_ROWS, PRUNE_COLS, PRUNE_MAX_N, PRUNE_MAX_W = 256, 512, 1048576, 4
 KNN_ROWS, KNN_COLS, KNN_MAX_D, KNN_MAX_N, KNN_MAX_B, KNN_MAX_PAIRS = 256, 512, 4, 1048576, 4096, 1 << 38
+KDE_POINTS, KDE_RUN, KDE_MAX_D, KDE_MAX_N, KDE_MAX_B, KDE_MAX_PAIRS = 256, 256, 4, 1048576, 4096, 1 << 36
 LC_MD, LC_MISTAKES, LC_NOISY = 1, 2, 4
 LC_MD_EQ, LC_MD_LE = 0, 1
 LC_GT_MISTAKE, LC_GT_NOISY, LC_GT_REPLACED = 1, 2, 4
@@ -173,6 +174,7 @@ _SIGNATURES = {
     "uda_hash_neighbors_np": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                         _P, _P, C.POINTER(C.c_int64)]),
     "uda_nn_dist2_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "uda_kde_eval_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "uda_pseudo_audit_np": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "uda_uncert_report_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "uda_class_report_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,

@@ -570,6 +570,32 @@ struct KnnArgs {
 };
 void launch_knn_min(const KnnArgs& a, hipStream_t s);
 
+// Gaussian KDE evaluation (reference uncertainty_ep_vs_al.py:361-375: gaussian_kde on a mesh) for B ragged problems
+// (kernels_kde.hip).  The host cuts every problem into work items: KDE_POINTS points x the runs [r0, r1) of KDE_RUN data rows; an
+// item writes the sequential sum of each of its runs to run_sums, and a second launch folds a point's run sums in the stated tree.
+// The cut into items decides who sums a run and nothing about any value.
+enum { KDE_POINTS = UDA_KDE_POINTS, KDE_RUN = UDA_KDE_RUN, KDE_MAX_D = UDA_KDE_MAX_D, KDE_MAX_ITEMS = 1 << 22 };
+struct KdeItem {
+  int32_t problem, point0, r0, r1;   // points [point0, point0 + KDE_POINTS) of the problem against its runs [r0, r1)
+};
+struct KdeTile {
+  int32_t problem, point0;           // the tree launch: points [point0, point0 + KDE_POINTS) of the problem
+};
+struct KdeArgs {
+  const double* data;       // [d_off[B], D] whitened rows
+  const double* weight;     // [d_off[B]]; null: every row counts 1 and is not multiplied
+  const double* points;     // [p_off[B], D] whitened points
+  const int64_t* d_off;     // [B + 1]
+  const int64_t* p_off;     // [B + 1]
+  const int64_t* s_off;     // [B + 1] where the problem's run sums [runs_b, m_b] begin in run_sums
+  const KdeItem* items;     // [n_items]
+  const KdeTile* tiles;     // [n_tiles]
+  double* run_sums;         // [s_off[B]]; every element is written by exactly one item before the tree launch reads it
+  double* sum;              // [p_off[B]]
+  int D, n_items, n_tiles;
+};
+void launch_kde_eval(const KdeArgs& a, hipStream_t s);
+
 // label correction (reference ssl_utils/glc.py): the three verdicts on one image's kept detections and counted ground-truth rows
 // (kernels_glc.hip).  T = float for the columns resident in a handle, double for host arrays (uda_label_check_np)
 enum { LC_MD = UDA_LC_MD, LC_MISTAKES = UDA_LC_MISTAKES, LC_NOISY = UDA_LC_NOISY };

@@ -1191,6 +1191,62 @@ extern "C" int uda_nn_dist2_np(int32_t device, int32_t D, int32_t B, const doubl
   return scratch_done(nullptr, who, s);
 }
 
+// Gaussian KDE evaluation: B ragged problems in, one launch over a table of (problem, point tile, span of runs) work items, a
+// second over the point tiles, the sums out; its own allocations.  A call with fewer point tiles than kKdeBlocks cuts every
+// problem's runs into as many spans as fill that many blocks (a 100 x 100 mesh is 40 tiles).  Every run's sum has its own slot in
+// the scratch, so the cut decides who sums a run and nothing about the result.
+static const int kKdeBlocks = 2048;
+extern "C" int uda_kde_eval_np(int32_t device, int32_t D, int32_t B, const double* data, const int64_t* d_off, const double* weight,
+                               const double* points, const int64_t* p_off, double* sum) {
+  const char* who = "uda_kde_eval_np";
+  if (D < 1 || D > KDE_MAX_D) return fail(nullptr, "%s: %d coordinates, 1..%d are taken", who, D, (int)KDE_MAX_D);
+  if (B < 1 || B > UDA_KDE_MAX_B) return fail(nullptr, "%s: %d problems, 1..%d are taken", who, B, (int)UDA_KDE_MAX_B);
+  if (!data || !d_off || !points || !p_off || !sum) return fail(nullptr, "%s: NULL input", who);
+  if (d_off[0] != 0 || p_off[0] != 0) return fail(nullptr, "%s: offsets start at %lld and %lld, not at 0", who, (long long)d_off[0], (long long)p_off[0]);
+  int64_t pairs = 0, tiles = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = d_off[b + 1] - d_off[b], m = p_off[b + 1] - p_off[b];
+    if (n < 0 || m < 0) return fail(nullptr, "%s: the offsets of problem %d descend", who, b);
+    if (n == 0) return fail(nullptr, "%s: problem %d has no data row", who, b);
+    if (n > UDA_KDE_MAX_N) return fail(nullptr, "%s: problem %d has %lld data rows, at most %d", who, b, (long long)n, (int)UDA_KDE_MAX_N);
+    if (m > UDA_KDE_MAX_PAIRS / n || (pairs += n * m) > UDA_KDE_MAX_PAIRS)
+      return fail(nullptr, "%s: more than %lld pairs of a point and a data row in one call (reached at problem %d)", who,
+                  (long long)UDA_KDE_MAX_PAIRS, b);
+    tiles += (m + KDE_POINTS - 1) / KDE_POINTS;
+  }
+  if (tiles > KDE_MAX_ITEMS) return fail(nullptr, "%s: %lld blocks of points, at most %d (internal)", who, (long long)tiles, (int)KDE_MAX_ITEMS);
+  const int64_t want_spans = tiles > 0 ? std::max<int64_t>(1, (kKdeBlocks + tiles - 1) / tiles) : 1;   // no tile: no point anywhere, nothing is launched
+  std::vector<KdeItem> items;
+  std::vector<KdeTile> tile_tab;
+  std::vector<int64_t> s_off((size_t)B + 1, 0);
+  items.reserve((size_t)std::max<int64_t>(tiles, 2 * kKdeBlocks));
+  tile_tab.reserve((size_t)tiles);
+  for (int b = 0; b < B; ++b) {
+    const int n = (int)(d_off[b + 1] - d_off[b]), m = (int)(p_off[b + 1] - p_off[b]);   // m < KDE_MAX_ITEMS * KDE_POINTS = 2^30
+    const int runs = (n + KDE_RUN - 1) / KDE_RUN;
+    const int spans = (int)std::min<int64_t>(runs, want_spans);
+    const int per = (runs + spans - 1) / spans;                // runs per span; no empty span below
+    s_off[b + 1] = s_off[b] + (int64_t)runs * m;
+    for (int point0 = 0; point0 < m; point0 += KDE_POINTS) {
+      tile_tab.push_back(KdeTile{b, point0});
+      for (int r0 = 0; r0 < runs; r0 += per) items.push_back(KdeItem{b, point0, r0, std::min(runs, r0 + per)});
+    }
+  }
+  DevScratch s(device);
+  KdeArgs a{};
+  a.D = D; a.n_items = (int)items.size(); a.n_tiles = (int)tile_tab.size();
+  a.data = s.upload(data, (size_t)d_off[B] * D); a.weight = s.upload(weight, (size_t)d_off[B]);
+  a.points = s.upload(points, (size_t)p_off[B] * D);
+  a.d_off = s.upload(d_off, (size_t)B + 1); a.p_off = s.upload(p_off, (size_t)B + 1); a.s_off = s.upload(s_off.data(), s_off.size());
+  a.items = s.upload(items.data(), items.size()); a.tiles = s.upload(tile_tab.data(), tile_tab.size());
+  a.run_sums = s.alloc<double>((size_t)s_off[B]);
+  a.sum = s.alloc<double>((size_t)p_off[B]);
+  if (s.ok()) launch_kde_eval(a, nullptr);
+  s.sync();
+  s.download(sum, a.sum, (size_t)p_off[B] * sizeof(double));
+  return scratch_done(nullptr, who, s);
+}
+
 // the pseudo-label audit: B ragged images in, one block each, the results in ONE device allocation, each array the caller asked
 // for copied out of it; its own allocations
 extern "C" int uda_pseudo_audit_np(int32_t device, int32_t B, const double* gt_boxes, const int64_t* gt_off, const double* det_boxes,

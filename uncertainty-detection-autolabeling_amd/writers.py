@@ -10,6 +10,8 @@
                         for the verdicts of a `label_correction.LabelCheck`: `write_kitti_corrected_gt`, `write_bdd_corrected_gt`
   corrected pseudo labels the KITTI label files and the BDD100K json of `ThreeDproblem.corrected_pseudo` (src/ssl_utils/3d.py:80-255)
                         for a `pseudo_audit.PseudoCorrection`: `write_kitti_corrected_pseudo`, `write_bdd_corrected_pseudo`
+  epistemic vs aleatoric  the two text files of `EpistemicVSAleatoric.save_highlow` (src/uncertainty_ep_vs_al.py:393-449) for an
+                        `epal.EpalComparison`: `write_epal_highlow`
 
 Both are read back with `ast.literal_eval(line.replace("inf", "2e308"))` (active_learning_loop.py:532,
 SSL_stac.py:345, uncertainty_analysis.py).  The reference prints numpy-1 float32 scalars, whose repr is the shortest
@@ -212,6 +214,23 @@ def write_validate_results(path, records):
     with open(path, "w") as f:
         for r in records:
             f.write(str(r) + "\n")
+
+
+def write_epal_highlow(out_dir, comparison):
+    """`EpistemicVSAleatoric.save_highlow` (uncertainty_ep_vs_al.py:393-449) without the crop montages: under
+    out_dir/compare_epal/mcdropout (or .../entropy, :479, :486) the files hal_lep_<uncert>_iou_<thr>.txt and lal_hep_..., one
+    `str(record)` line per detection of the "high AL / low EP" and of the "low AL / high EP" corner, files rewritten.  Returns the
+    two paths."""
+    import os
+    folder = os.path.join(out_dir, comparison.subdir)
+    os.makedirs(folder, exist_ok=True)
+    paths = []
+    for stem, recs in zip(("hal_lep", "lal_hep"), comparison.highlow_records()):
+        paths.append(os.path.join(folder, "%s_%s_iou_%s.txt" % (stem, comparison.uncert, str(comparison.iou_thr))))
+        with open(paths[-1], "w") as f:
+            for r in recs:
+                f.write(str(r) + "\n")
+    return tuple(paths)
 
 
 def summarize_runtimes(seconds):
