@@ -34,6 +34,8 @@
  *                            _collect_postthresholding (uncertainty_analysis.py:838-880, 1024-1068)
  *   uda_hash_neighbors_np <- the distance matrix, its maximum and the rows of near-duplicates of
  *                            ActiveLearning.extract_hash_matrix (active_learning_loop.py:240-270)
+ *   uda_phash_np          <- the hashes that matrix is built from: Image.resize((512, 256)) and imagehash.phash of every pool
+ *                            image (active_learning_loop.py:215-224)
  *   uda_nn_dist2_np       <- the four KD-tree queries of emp_KL_divergence for every (class, method) of
  *                            Similarity.calculate_set_similarity (active_learning_eval.py:481-487, 946-1029)
  *   uda_pseudo_audit_np   <- the matching, allocation and by-value tallies of Parent_SSL.extract_pseudo_gt_data and
@@ -672,6 +674,44 @@ int uda_thr_post_np(int32_t device, const double* u, const double* ious, const u
 int uda_hash_neighbors_np(int32_t device, const uint64_t* hashes, int32_t N, int32_t W, double prune_thr, int32_t max_distance,
                           int64_t cap, int32_t* max_dist, int64_t* row_off, int32_t* idx, int64_t* total);
 
+/* Dataset pruning, the hashes: what the reference computes for every pool image before the search above
+ * (active_learning_loop.py:215-224) - Image.open(..).resize((512, 256)) and imagehash.phash - from the decoded pixels on, for N
+ * ragged RGB images in one call, without a handle.  Decoding, and any image that is not RGB, stay the caller's
+ * (dataset_pruning.py).
+ *   wh, pix    wh [N, 2] int32 = (width, height); the packed RGB planes (row-major, 3 bytes a pixel) one after another in pix
+ *   recipe     1. Image.resize((512, 256)) with Pillow's default filter for RGB, BICUBIC: the passes of uda_resample_np with the
+ *                 table of uda_resample_coeffs_filter_np(.., UDA_FILTER_BICUBIC, ..) - along x first and rounded to uint8, a
+ *                 pass whose axis keeps its length skipped, along y first for a plane more than 100 times as tall as wide whose
+ *                 height shrinks.  Bit for bit Pillow's
+ *              2. convert("L"): (R 19595 + G 38470 + B 7471 + 0x8000) >> 16
+ *              3. resize((32, 32), Image.LANCZOS) of that plane, the same 8-bit arithmetic on one channel: thumb, bit for bit
+ *                 Pillow's
+ *              4. the 8 x 8 low corner of scipy.fftpack.dct (type 2, unnormalised) along axis 0 and then axis 1, in float64 as
+ *                 direct sums with T[k][i] = 2.0 * cos(M_PI * k * (2 i + 1) / 64.0) (uda_phash_table_np hands out these 8 x 32
+ *                 values; host only): a[k][j] = sum_i T[k][i] thumb[i][j], i ascending from 0.0, then low[k][l] = sum_j a[k][j]
+ *                 T[l][j], j ascending; every product rounded, then every sum, never an FMA.  Bit-equal to a numpy loop in that
+ *                 order; equal to scipy's FFT only to rounding
+ *              5. med = the mean of the two middle values of low (numpy's median), bit 8 k + l = low[k][l] > med
+ *   words      [N] uint64: the 64 bits row-major, the first bit the most significant - int(str(imagehash value), 16)
+ *   margin     [N] doubles: min over the 64 values of |low - med|.  A bit whose value lies within rounding of the median is not
+ *              determined by a direct sum or by an FFT: the caller compares margin with a bound of its own and settles such an
+ *              image from thumb (dataset_pruning.PHASH_TIE).  A constant image has margin ~ 0: its AC terms are noise here
+ *   thumb      [N, 32, 32] uint8, may be NULL;  low [N, 64] doubles, may be NULL
+ *   limits     N >= 0 (N = 0 writes nothing), every side in 1 .. UDA_RESAMPLE_MAX_SIDE, and the call's device bytes - 393 216 an
+ *              image for its 512 x 256 plane, its source, and 3 * 512 * h for the first pass's result when both axes change
+ *              (3 * w * 256 where y goes first) - at most UDA_PHASH_MAX_BYTES.  A NULL wh, pix, words or margin and anything
+ *              else is refused with a "uda_phash_np: " message, and the outputs stay untouched
+ *   cost       one allocation, one upload of the pixels, up to three launches of the resample passes and one of the tail (a
+ *              block an image, 37 648 bytes of LDS) on one stream without a host synchronisation in between, four downloads */
+#define UDA_PHASH_PRE_W 512
+#define UDA_PHASH_PRE_H 256
+#define UDA_PHASH_SIDE 32
+#define UDA_PHASH_LOW 8
+#define UDA_PHASH_MAX_BYTES 4294967296LL           /* device bytes a call, 2^32 */
+int uda_phash_np(int32_t device, int32_t N, const int32_t* wh, const uint8_t* pix, uint64_t* words, double* margin, uint8_t* thumb,
+                 double* low);
+int uda_phash_table_np(double* T);
+
 /* Set similarity: the neighbour search of the active-learning evaluation's set-similarity analysis (emp_KL_divergence,
  * active_learning_eval.py:458-492, called twice per (class, method) by empirical_jensen_shannon_divergence :495-583 under
  * Similarity.calculate_set_similarity :946-1029) - for B independent problems in one call, the squared Euclidean distance from
@@ -914,13 +954,22 @@ int uda_class_report_np(int32_t device, int32_t B, int32_t M, int32_t C, int32_t
  *              axes ((source width) x h x 3 where y goes first), and the coefficient tables, one for each distinct (in, out) pair: 4 out (2 + ksize) bytes
  * uda_resample_coeffs_np is host only (no device is touched): the table of one axis.  *ksize is always written; bounds [out_size,
  * 2] = (xmin, xmax) and coeffs [out_size, ksize] (zeros past xmax) when they are not NULL, coeffs_cap being the int32 values
- * coeffs holds. */
+ * coeffs holds.
+ * uda_resample_coeffs_filter_np is the same with the filter named (the values are Pillow's Image.LANCZOS and Image.BICUBIC):
+ * UDA_FILTER_LANCZOS gives the table of uda_resample_coeffs_np; UDA_FILTER_BICUBIC has the support 2 filterscale and the weights
+ * ((a + 2) x - (a + 3)) x x + 1 for |x| < 1, (((x - 5) x + 8) x - 4) a for |x| < 2, a = -0.5, every operation in double and
+ * rounded on its own in this order - the table of Image.resize's default filter, which uda_phash_np resizes with.  Any other
+ * filter is refused. */
+#define UDA_FILTER_LANCZOS 1
+#define UDA_FILTER_BICUBIC 3
 #define UDA_RESAMPLE_TILE 32                       /* output positions a tile of a pass, at most */
 #define UDA_RESAMPLE_MAX_SIDE 65536                /* pixels a side, planes and jobs */
 #define UDA_RESAMPLE_MAX_SCRATCH 17179869184LL     /* bytes, 2^34 */
 int uda_resample_np(int32_t device, int32_t S, const int32_t* src_wh, const uint8_t* src_pix, int32_t T, const int32_t* tmp_wh,
                     int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, uint8_t* out);
 int uda_resample_coeffs_np(int32_t in_size, int32_t out_size, int32_t* ksize, int32_t* bounds, int32_t* coeffs, int64_t coeffs_cap);
+int uda_resample_coeffs_filter_np(int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize, int32_t* bounds, int32_t* coeffs,
+                                  int64_t coeffs_cap);
 
 /* RCC's manual augmentations (Parent_SSL.apply_manual_augmentation, ssl_utils/parent.py:261-315, applied at :534-537): the job
  * list of uda_resample_np with an operation per job, so that the augmentation of a resized crop runs between its resize and its

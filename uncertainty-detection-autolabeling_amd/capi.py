@@ -49,6 +49,8 @@ AUDIT_MAX_G, AUDIT_MAX_D, AUDIT_MAX_B = 1024, 1024, 1048576
 REPORT_ROWS, REPORT_MAX_K, REPORT_MAX_L, REPORT_MAX_B, REPORT_MAX_ROWS = 256, 16, 128, 4096, 1 << 22
 CLASSREP_ROWS, CLASSREP_MAX_B, CLASSREP_MAX_M, CLASSREP_MAX_C, CLASSREP_MAX_E, CLASSREP_MAX_ROWS = 256, 4096, 8, 128, 64, 1 << 22
 RESAMPLE_TILE, RESAMPLE_MAX_SIDE, RESAMPLE_MAX_SCRATCH = 32, 65536, 1 << 34
+FILTER_LANCZOS, FILTER_BICUBIC = 1, 3
+PHASH_PRE_W, PHASH_PRE_H, PHASH_SIDE, PHASH_LOW, PHASH_MAX_BYTES = 512, 256, 32, 8, 1 << 32
 AUGMENT_TILE, AUGMENT_ROWS, BLUR_MAX_RADIUS, BLUR_MAX_BOX = 32, 8, 16.0, 15
 
 
@@ -181,6 +183,9 @@ _SIGNATURES = {
                                       _P, _P]),
     "uda_resample_np": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "uda_resample_coeffs_np": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.c_int64]),
+    "uda_resample_coeffs_filter_np": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.c_int64]),
+    "uda_phash_np": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "uda_phash_table_np": (C.c_int, [_P]),
     "uda_collage_np": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P,
                                  C.c_int64, _P, _P]),
     "uda_gauss_box_np": (C.c_int, [C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -1,5 +1,6 @@
 // RCC collages (reference ssl_utils/parent.py:317-686, Parent_SSL.crop_collage): Pillow's two-pass 8-bit Lanczos resample on
-// packed RGB uint8 planes, many jobs per call: uda_resample_np (include/uda_hip.h).  Pillow's arithmetic (src/libImaging/Resample.c,
+// packed RGB uint8 planes, many jobs per call: uda_resample_np (include/uda_hip.h).  The same passes with bicubic tables are
+// the first step of the perceptual hash (uda_phash_np; kernels_phash.hip has the rest): the kernel does not know the filter.  Pillow's arithmetic (src/libImaging/Resample.c,
 // precompute_coeffs / normalize_coeffs_8bpc / ImagingResampleHorizontal_8bpc / ImagingResampleVertical_8bpc) is integer
 // arithmetic on coefficient tables, so the result is Pillow's bit for bit.  Built without FMA contraction (csrc/Makefile): the
 // tables are made by resample_coeffs below, host code, every operation in double and rounded on its own, with the C library's sin.
@@ -110,20 +111,28 @@ static double lanczos_filter(double x) {                                // trunc
   if (-3.0 <= x && x < 3.0) return sinc_filter(x) * sinc_filter(x / 3);
   return 0.0;
 }
+static double bicubic_filter(double x) {                                // Keys' cubic with a = -0.5, Pillow's BICUBIC
+  const double a = -0.5;
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+static double filter_support(int filter) { return filter == UDA_FILTER_BICUBIC ? 2.0 : 3.0; }
 
-int resample_ksize(int in_size, int out_size) {
+int resample_ksize(int in_size, int out_size, int filter) {
   double filterscale = (double)in_size / out_size;
   if (filterscale < 1.0) filterscale = 1.0;
-  return (int)ceil(3.0 * filterscale) * 2 + 1;
+  return (int)ceil(filter_support(filter) * filterscale) * 2 + 1;
 }
 
-// precompute_coeffs and normalize_coeffs_8bpc for the whole axis [0, in_size): bounds [out_size, 2] = (xmin, xmax), kk [out_size,
-// ksize], zero past xmax
-void resample_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk) {
+// precompute_coeffs and normalize_coeffs_8bpc for the whole axis [0, in_size) with the filter UDA_FILTER_LANCZOS or
+// UDA_FILTER_BICUBIC: bounds [out_size, 2] = (xmin, xmax), kk [out_size, ksize], zero past xmax
+void resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk) {
   double filterscale, scale;
   filterscale = scale = (double)in_size / out_size;
   if (filterscale < 1.0) filterscale = 1.0;
-  const double support = 3.0 * filterscale;
+  const double support = filter_support(filter) * filterscale;
   const int ksize = (int)ceil(support) * 2 + 1;
   std::vector<double> pre(ksize);
   for (int xx = 0; xx < out_size; ++xx) {
@@ -135,7 +144,8 @@ void resample_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk) {
     if (xmax > in_size) xmax = in_size;
     xmax -= xmin;
     for (int x = 0; x < xmax; ++x) {
-      const double w = lanczos_filter((x + xmin - center + 0.5) * ss);
+      const double at = (x + xmin - center + 0.5) * ss;
+      const double w = filter == UDA_FILTER_BICUBIC ? bicubic_filter(at) : lanczos_filter(at);
       pre[x] = w;
       ww = ww + w;
     }

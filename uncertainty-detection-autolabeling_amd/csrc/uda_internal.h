@@ -724,8 +724,21 @@ struct ResamplePass {
 };
 void launch_resample_passes(const ResamplePass* passes, int n_pass, int n_tiles, bool vertical, const int32_t* pool, uint8_t* base,
                             hipStream_t s);
-int resample_ksize(int in_size, int out_size);
-void resample_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk);
+int resample_ksize(int in_size, int out_size, int filter);    // filter: UDA_FILTER_LANCZOS | UDA_FILTER_BICUBIC
+void resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk);
+
+// The perceptual hash after its first resize (kernels_phash.hip): one block an image on the image's 512 x 256 RGB plane - grey,
+// Lanczos to 32 x 32, the 8 x 8 corner of the DCT in float64, median, bits.  The tables are the call's, built on the host.
+enum { PHASH_THREADS = 256, PHASH_WAVES = PHASH_THREADS / 64, PHASH_W = UDA_PHASH_PRE_W, PHASH_H = UDA_PHASH_PRE_H,
+       PHASH_SIDE = UDA_PHASH_SIDE, PHASH_LOW = UDA_PHASH_LOW, PHASH_KX = 97, PHASH_KY = 49 };
+struct PhashTables {
+  double T[PHASH_LOW * PHASH_SIDE];                    // T[k][i] = 2 cos(pi k (2 i + 1) / 64)
+  int32_t bx[2 * PHASH_SIDE], by[2 * PHASH_SIDE];      // (xmin, xmax) of resample_coeffs(512, 32) and (256, 32), Lanczos
+  int32_t kx[PHASH_SIDE * PHASH_KX], ky[PHASH_SIDE * PHASH_KY];
+};
+void phash_dct_table(double* T);
+void launch_phash_tail(const uint8_t* pre, int n, const PhashTables* tab, unsigned long long* words, double* margin, uint8_t* thumb,
+                       double* low, hipStream_t s);
 
 // RCC's manual augmentations (reference ssl_utils/parent.py:261-315) between a collage's resizes and pastes: kernels_augment.hip.
 // Every address is a byte offset into the call's one device allocation, as for the resample passes.

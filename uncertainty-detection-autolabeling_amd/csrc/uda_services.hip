@@ -1,6 +1,6 @@
 // The services of the C ABI (include/uda_hip.h) that run beside the executor of uda_api.hip: ground-truth assignment, image scores,
 // COCO matching, the label check and the calibrations on the detections resident in a handle, and the entry points that take host arrays and work
-// on scratch device memory of their own (the *_np twins, the thresholding objective and report, the post-thresholding heat maps and tallies, the pruning neighbours, the pseudo-label audit, the uncertainty report, the classification report, the collage resample and augmentations, uda_nms, uda_debug_pw,
+// on scratch device memory of their own (the *_np twins, the thresholding objective and report, the post-thresholding heat maps and tallies, the pruning neighbours and hashes, the pseudo-label audit, the uncertainty report, the classification report, the collage resample and augmentations, uda_nms, uda_debug_pw,
 // the numpy NMS family).
 // Host code only: every kernel launched here lives in a kernels_*.hip.
 //
@@ -1441,37 +1441,47 @@ extern "C" int uda_class_report_np(int32_t device, int32_t B, int32_t M, int32_t
 }
 
 // ---- RCC collages: Pillow's resize and paste as jobs on packed RGB planes (kernels_collage.hip)
-extern "C" int uda_resample_coeffs_np(int32_t in_size, int32_t out_size, int32_t* ksize, int32_t* bounds, int32_t* coeffs,
-                                      int64_t coeffs_cap) {
-  const char* who = "uda_resample_coeffs_np";
+static int resample_coeffs_entry(const char* who, int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize, int32_t* bounds,
+                                 int32_t* coeffs, int64_t coeffs_cap) {
+  if (filter != UDA_FILTER_LANCZOS && filter != UDA_FILTER_BICUBIC)
+    return fail(nullptr, "%s: filter %d, UDA_FILTER_LANCZOS (%d) and UDA_FILTER_BICUBIC (%d) are built", who, filter, (int)UDA_FILTER_LANCZOS,
+                (int)UDA_FILTER_BICUBIC);
   if (in_size < 1 || in_size > UDA_RESAMPLE_MAX_SIDE || out_size < 1 || out_size > UDA_RESAMPLE_MAX_SIDE)
     return fail(nullptr, "%s: an axis of %d to %d pixels, 1..%d are taken", who, in_size, out_size, (int)UDA_RESAMPLE_MAX_SIDE);
   if (!ksize) return fail(nullptr, "%s: NULL ksize", who);
-  *ksize = resample_ksize(in_size, out_size);
+  *ksize = resample_ksize(in_size, out_size, filter);
   if (!bounds && !coeffs) return 0;
   if (!bounds || !coeffs) return fail(nullptr, "%s: bounds and coeffs go together", who);
   if (coeffs_cap < (int64_t)out_size * *ksize)
     return fail(nullptr, "%s: coeffs holds %lld values, %lld are needed", who, (long long)coeffs_cap, (long long)out_size * *ksize);
-  resample_coeffs(in_size, out_size, bounds, coeffs);
+  resample_coeffs(in_size, out_size, filter, bounds, coeffs);
   return 0;
+}
+extern "C" int uda_resample_coeffs_np(int32_t in_size, int32_t out_size, int32_t* ksize, int32_t* bounds, int32_t* coeffs,
+                                      int64_t coeffs_cap) {
+  return resample_coeffs_entry("uda_resample_coeffs_np", in_size, out_size, UDA_FILTER_LANCZOS, ksize, bounds, coeffs, coeffs_cap);
+}
+extern "C" int uda_resample_coeffs_filter_np(int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize, int32_t* bounds,
+                                             int32_t* coeffs, int64_t coeffs_cap) {
+  return resample_coeffs_entry("uda_resample_coeffs_filter_np", in_size, out_size, filter, ksize, bounds, coeffs, coeffs_cap);
 }
 
 namespace {
 struct ResamplePlane { int64_t off; int32_t w, h; };
-struct ResampleTables {          // one table for each distinct (in, out) pair of the call, in one int32 pool
-  struct Table { int64_t key, off; };
+struct ResampleTables {          // one table for each distinct (filter, in, out) of the call, in one int32 pool
+  struct Table { int64_t key, off; };                  // key: filter << 56 | in << 32 | out (a side is at most 2^16)
   std::vector<int32_t> pool;
   std::vector<Table> index, fresh;                     // index: sorted by key; fresh: the latest, not yet merged
   std::vector<Table> todo;                             // reserved in the pool, not yet filled
   size_t reserved = 0;
-  // where the table of (in, out) is (or will be: fill() makes what get() reserved)
-  int64_t get(int in, int out) {
-    const int64_t key = ((int64_t)in << 32) | (uint32_t)out;
+  // where the table of (in, out) under `filter` is (or will be: fill() makes what get() reserved)
+  int64_t get(int in, int out, int filter) {
+    const int64_t key = ((int64_t)filter << 56) | ((int64_t)in << 32) | (uint32_t)out;
     for (const Table& f : fresh) if (f.key == key) return f.off;
     auto it = std::lower_bound(index.begin(), index.end(), key, [](const Table& t, int64_t k) { return t.key < k; });
     if (it != index.end() && it->key == key) return it->off;
     const Table t{key, (int64_t)reserved};
-    reserved += (size_t)out * (2 + (in == out ? 1 : resample_ksize(in, out)));
+    reserved += (size_t)out * (2 + (in == out ? 1 : resample_ksize(in, out, filter)));
     todo.push_back(t);
     fresh.push_back(t);
     if (fresh.size() >= 64) {
@@ -1487,12 +1497,12 @@ struct ResampleTables {          // one table for each distinct (in, out) pair o
     std::atomic<size_t> next{0};
     auto work = [&]() {
       for (size_t i; (i = next.fetch_add(1)) < todo.size();) {
-        const int in = (int)(todo[i].key >> 32), out = (int)(uint32_t)todo[i].key;
+        const int filter = (int)(todo[i].key >> 56), in = (int)(todo[i].key >> 32) & 0xFFFFFF, out = (int)(uint32_t)todo[i].key;
         int32_t* b = pool.data() + todo[i].off;
         if (in == out) {                               // the identity: a copy is a pass like any other
           for (int k = 0; k < out; ++k) { b[2 * k] = k; b[2 * k + 1] = 1; b[2 * (size_t)out + k] = 1 << RESAMPLE_BITS; }
         } else {
-          resample_coeffs(in, out, b, b + 2 * (size_t)out);
+          resample_coeffs(in, out, filter, b, b + 2 * (size_t)out);
         }
       }
     };
@@ -1513,12 +1523,12 @@ static bool resample_vertical_first(int src_w, int src_h, int h) { return (int64
 
 // One pass over `in_size` -> table `out_full`, of which n_out positions and n_lines lines are written; its table is reserved.
 static ResamplePass resample_pass(ResampleTables& tabs, int64_t src, int64_t src_stride, int64_t dst, int64_t dst_stride, int in_size,
-                                  int out_full, int n_out, int n_lines) {
+                                  int out_full, int n_out, int n_lines, int filter = UDA_FILTER_LANCZOS) {
   ResamplePass p{};
   p.src = src; p.dst = dst; p.src_stride = src_stride; p.dst_stride = dst_stride;
-  p.coef_off = tabs.get(in_size, out_full);
+  p.coef_off = tabs.get(in_size, out_full, filter);
   p.in_size = in_size; p.out_full = out_full; p.n_out = n_out; p.n_lines = n_lines;
-  p.ksize = in_size == out_full ? 1 : resample_ksize(in_size, out_full);
+  p.ksize = in_size == out_full ? 1 : resample_ksize(in_size, out_full, filter);
   return p;
 }
 // The tiles of a pass, once the tables are filled.  tw: the largest power of two <= RESAMPLE_TW whose every tile's span (last xmin
@@ -1775,6 +1785,96 @@ extern "C" int uda_collage_np(int32_t device, int32_t S, const int32_t* src_wh, 
                               int32_t N, int32_t H, int32_t W, int32_t K, const int32_t* jobs, int32_t P, const double* params,
                               int64_t noise_bytes, const uint8_t* noise, uint8_t* out) {
   return collage_run("uda_collage_np", 9, device, S, src_wh, src_pix, T, tmp_wh, N, H, W, K, jobs, P, params, noise_bytes, noise, out);
+}
+
+// ---- the pruning step's perceptual hash: the passes of kernels_collage.hip with bicubic tables, then kernels_phash.hip
+extern "C" int uda_phash_table_np(double* T) {
+  if (!T) return fail(nullptr, "uda_phash_table_np: NULL table");
+  phash_dct_table(T);
+  return 0;
+}
+
+extern "C" int uda_phash_np(int32_t device, int32_t N, const int32_t* wh, const uint8_t* pix, uint64_t* words, double* margin,
+                            uint8_t* thumb, double* low) {
+  const char* who = "uda_phash_np";
+  const int MAXS = UDA_RESAMPLE_MAX_SIDE, PW = UDA_PHASH_PRE_W, PH = UDA_PHASH_PRE_H, F = UDA_FILTER_BICUBIC;
+  const int64_t plane = (int64_t)PW * PH * 3;
+  if (N < 0) return fail(nullptr, "%s: %d images", who, N);
+  if (N == 0) return 0;
+  if (!wh || !pix || !words || !margin) return fail(nullptr, "%s: NULL array", who);
+  // one device allocation: the N planes of 512 x 256 first (the tail reads them in 16-byte words), the sources, the first passes' results
+  const int64_t src_off = (int64_t)N * plane;
+  int64_t bytes = src_off, mid_bytes = 0;
+  for (int i = 0; i < N && bytes + mid_bytes <= UDA_PHASH_MAX_BYTES; ++i) {
+    const int w = wh[2 * (size_t)i], h = wh[2 * (size_t)i + 1];
+    if (w < 1 || h < 1 || w > MAXS || h > MAXS)
+      return fail(nullptr, "%s: image %d is %d x %d, an empty image or a side above %d is not taken", who, i, w, h, MAXS);
+    bytes += (int64_t)w * h * 3;
+    if (w != PW && h != PH) mid_bytes += resample_vertical_first(w, h, PH) ? (int64_t)w * PH * 3 : (int64_t)PW * h * 3;
+  }
+  if (bytes + mid_bytes > UDA_PHASH_MAX_BYTES)
+    return fail(nullptr, "%s: %d images take more than %lld bytes on the device (planes of %d x %d, sources, first passes): split the call",
+                who, N, (long long)UDA_PHASH_MAX_BYTES, PW, PH);
+  const int64_t src_bytes = bytes - src_off;
+  PhashTables pt;
+  if (resample_ksize(PW, PHASH_SIDE, UDA_FILTER_LANCZOS) != PHASH_KX || resample_ksize(PH, PHASH_SIDE, UDA_FILTER_LANCZOS) != PHASH_KY)
+    return fail(nullptr, "%s: the thumbnail's tables do not have %d and %d coefficients a row", who, (int)PHASH_KX, (int)PHASH_KY);
+  resample_coeffs(PW, PHASH_SIDE, UDA_FILTER_LANCZOS, pt.bx, pt.kx);
+  resample_coeffs(PH, PHASH_SIDE, UDA_FILTER_LANCZOS, pt.by, pt.ky);
+  phash_dct_table(pt.T);
+  // Image.resize((512, 256)) of every image: along x first, rounded to uint8; a pass whose axis keeps its length is skipped
+  ResampleTables tabs;
+  std::vector<ResamplePass> passes, vert, late;
+  int64_t s = src_off;
+  for (int i = 0; i < N; ++i) {
+    const int w = wh[2 * (size_t)i], h = wh[2 * (size_t)i + 1];
+    const int64_t to = (int64_t)i * plane;
+    if (w != PW && h != PH && resample_vertical_first(w, h, PH)) {
+      vert.push_back(resample_pass(tabs, s, (int64_t)w * 3, bytes, (int64_t)w * 3, h, PH, PH, w, F));
+      late.push_back(resample_pass(tabs, bytes, (int64_t)w * 3, to, (int64_t)PW * 3, w, PW, PW, PH, F));
+      bytes += (int64_t)w * PH * 3;
+    } else if (w != PW && h != PH) {
+      passes.push_back(resample_pass(tabs, s, (int64_t)w * 3, bytes, (int64_t)PW * 3, w, PW, PW, h, F));
+      vert.push_back(resample_pass(tabs, bytes, (int64_t)PW * 3, to, (int64_t)PW * 3, h, PH, PH, PW, F));
+      bytes += (int64_t)PW * h * 3;
+    } else if (h != PH) {
+      vert.push_back(resample_pass(tabs, s, (int64_t)w * 3, to, (int64_t)PW * 3, h, PH, PH, PW, F));
+    } else {                                            // along x only, or the copy (the identity table)
+      passes.push_back(resample_pass(tabs, s, (int64_t)w * 3, to, (int64_t)PW * 3, w, PW, PW, PH, F));
+    }
+    s += (int64_t)w * h * 3;
+  }
+  const int n_x = (int)passes.size(), n_y = (int)vert.size(), n_late = (int)late.size();
+  passes.insert(passes.end(), vert.begin(), vert.end());
+  passes.insert(passes.end(), late.begin(), late.end());
+  tabs.fill();
+  int tiles_x = 0, tiles_y = 0, tiles_late = 0;
+  for (int i = 0; i < n_x; ++i) resample_tiles(passes[i], tabs, false, &tiles_x);
+  for (int i = 0; i < n_y; ++i) resample_tiles(passes[n_x + i], tabs, true, &tiles_y);
+  for (int i = 0; i < n_late; ++i) resample_tiles(passes[n_x + n_y + i], tabs, false, &tiles_late);
+  DevScratch d(device);
+  hipStream_t st = d.stream();
+  uint8_t* base = d.alloc<uint8_t>((size_t)bytes);
+  const ResamplePass* d_pass = d.upload(passes.data(), passes.size(), st);
+  const int32_t* d_pool = d.upload(tabs.pool.data(), tabs.pool.size(), st);
+  const PhashTables* d_pt = d.upload(&pt, 1, st);
+  unsigned long long* d_words = d.alloc<unsigned long long>((size_t)N);
+  double* d_margin = d.alloc<double>((size_t)N);
+  uint8_t* d_thumb = d.alloc<uint8_t>((size_t)N * PHASH_SIDE * PHASH_SIDE);
+  double* d_low = d.alloc<double>((size_t)N * PHASH_LOW * PHASH_LOW);
+  if (int rc = scratch_done(nullptr, who, d)) return rc;
+  d.err = hipMemcpyAsync(base + src_off, pix, (size_t)src_bytes, hipMemcpyHostToDevice, st);
+  if (d.ok()) launch_resample_passes(d_pass, n_x, tiles_x, false, d_pool, base, st);
+  if (d.ok()) launch_resample_passes(d_pass + n_x, n_y, tiles_y, true, d_pool, base, st);
+  if (d.ok()) launch_resample_passes(d_pass + n_x + n_y, n_late, tiles_late, false, d_pool, base, st);
+  if (d.ok()) launch_phash_tail(base, N, d_pt, d_words, d_margin, d_thumb, d_low, st);
+  d.sync(st);
+  if (int rc = scratch_done(nullptr, who, d)) return rc;
+  d.download(words, d_words, (size_t)N * sizeof(uint64_t));
+  d.download(margin, d_margin, (size_t)N * sizeof(double));
+  d.download(thumb, d_thumb, thumb ? (size_t)N * PHASH_SIDE * PHASH_SIDE : 0);
+  d.download(low, d_low, low ? (size_t)N * PHASH_LOW * PHASH_LOW * sizeof(double) : 0);
+  return scratch_done(nullptr, who, d);
 }
 
 extern "C" int uda_calibrate_box(uda_ctx_t* c, int32_t col0, int32_t mode, int32_t relative, int32_t n_tables,

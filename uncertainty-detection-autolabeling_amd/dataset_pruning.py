@@ -15,6 +15,8 @@ draws, the removal and the budget stay on the host and consume numpy's legacy st
   adjust_budget       the iteration budget after pruning (:306-314)
   prune_pool          the whole method by its substring tests
   phash, hash_files   imagehash's perceptual hash restated with PIL and scipy (:215-224); host code
+  phash_device        the same recipe from the decoded pixels on - resize to (512, 256), grey, thumbnail, DCT, median, bits -
+                      for a batch of RGB images on the device (C entry point uda_phash_np); hash_files(.., device=0) uses it
 
 Two deviations: a pool without any group keeps every image, where the reference dies in `np.concatenate([])`; and the
 reference's .npy caches next to the dataset (hashes, matrix, duplicates, kept_inds) are not written or read.
@@ -26,6 +28,8 @@ import numpy as np
 from . import capi
 
 MAX_WORDS = capi.PRUNE_MAX_W
+PHASH_TIE = 1e-6                     # see phash_device
+HASH_CHUNK_BYTES = 1 << 28           # decoded pixels hash_files holds before it hands them to the device
 
 
 def _bits_to_words(bits):
@@ -202,13 +206,99 @@ def phash(image, hash_size=8, highfreq_factor=4):
     return low > np.median(low)
 
 
-def hash_files(paths, method="p"):
+def _phash_call_bytes(w, h):
+    """The device bytes uda_phash_np counts for one image (include/uda_hip.h): its 512 x 256 plane, its source, and the first
+    pass's result when both axes change."""
+    pw, ph = capi.PHASH_PRE_W, capi.PHASH_PRE_H
+    mid = 0 if w == pw or h == ph else (3 * w * ph if h > 100 * w and ph < h else 3 * pw * h)
+    return 3 * pw * ph + 3 * w * h + mid
+
+
+def phash_device(images, device=0, info=None):
+    """`phash(image.resize((512, 256)))` of every image, on the device: uint64 [N, 1] as `hash_files` packs them.  images: uint8
+    arrays [h, w, 3] or PIL images of mode RGB.  They go to uda_phash_np in as many calls as its byte cap asks for.
+
+    The result equals the host recipe for every image.  Resize, grey and thumbnail are Pillow's bit for bit; the DCT is not
+    scipy's: the device adds 32 products in a fixed order where scipy runs an FFT, and the two agree only to rounding, so a bit
+    whose coefficient lies within rounding of the median is determined by neither.  Every call therefore fetches the margin - the
+    smallest |low - median| of the image - and the 32 x 32 thumbnail (1 KB an image), and an image with margin <= PHASH_TIE gets
+    its bits on the host, from the device's thumbnail with scipy.fftpack.dct as `phash` does.  info["ties"], when a dict is
+    given, lists those images' indices; info["margin"] has every margin.
+
+    PHASH_TIE = 1e-6: |low| <= 32 * 2 * 32 * 2 * 255 ~ 1.04e6, and two sequential sums of 32 rounded products at that magnitude
+    carry at most about 64 * 2^-53 * 1.04e6 ~ 1e-8 of absolute error on the device side.  scipy's own error has no bound derived
+    here; the largest |direct sum - scipy| measured over 24 images was 9.8e-11.  1e-6 leaves a factor of 100 over the first figure
+    and 10^4 over the second.  Constant images always land here: their AC terms are exactly 0 with scipy and noise in a sum."""
+    import scipy.fftpack
+    planes = []
+    for k, im in enumerate(images):
+        if not isinstance(im, np.ndarray):
+            if getattr(im, "mode", None) != "RGB":
+                raise ValueError("image %d has mode %r: RGB PIL images or uint8 arrays [h, w, 3] are taken" % (k, getattr(im, "mode", None)))
+            im = np.asarray(im)
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError("image %d is %s %s: uint8 [h, w, 3] with h, w >= 1 is taken" % (k, im.dtype, im.shape))
+        if max(im.shape[:2]) > capi.RESAMPLE_MAX_SIDE:
+            raise ValueError("image %d is %d x %d: a side above %d is not taken" % (k, im.shape[1], im.shape[0], capi.RESAMPLE_MAX_SIDE))
+        planes.append(np.ascontiguousarray(im))
+    n = len(planes)
+    words, margin = np.zeros(n, np.uint64), np.zeros(n, np.float64)
+    thumb = np.zeros((n, capi.PHASH_SIDE, capi.PHASH_SIDE), np.uint8)
+    lib = capi.load() if n else None
+    k0 = 0
+    while k0 < n:
+        k1, need = k0, 0
+        while k1 < n and (k1 == k0 or need + _phash_call_bytes(planes[k1].shape[1], planes[k1].shape[0]) <= capi.PHASH_MAX_BYTES):
+            need += _phash_call_bytes(planes[k1].shape[1], planes[k1].shape[0])
+            k1 += 1
+        wh = np.array([(p.shape[1], p.shape[0]) for p in planes[k0:k1]], np.int32)
+        pix = np.concatenate([p.reshape(-1) for p in planes[k0:k1]])
+        rc = lib.uda_phash_np(int(device), k1 - k0, wh.ctypes.data, pix.ctypes.data, words[k0:k1].ctypes.data,
+                              margin[k0:k1].ctypes.data, thumb[k0:k1].ctypes.data, None)
+        capi.check(lib, None, rc, "uda_phash_np")
+        k0 = k1
+    ties = np.flatnonzero(margin <= PHASH_TIE)
+    for k in ties:
+        dct = scipy.fftpack.dct(scipy.fftpack.dct(thumb[k], axis=0), axis=1)
+        low = dct[:capi.PHASH_LOW, :capi.PHASH_LOW]
+        words[k] = _bits_to_words((low > np.median(low)).reshape(1, -1))[0, 0]
+    if info is not None:
+        info["ties"], info["margin"] = ties.tolist(), margin
+    return words.reshape(n, 1)
+
+
+def hash_files(paths, method="p", device=None):
     """The hashes of the pool as the reference computes them (:215-224): every file opened, resized to (512, 256) with PIL's
     default filter, then the perceptual hash.  Returns uint64 [N, 1].  method "w" (imagehash.whash) needs a wavelet package
-    (PyWavelets) this build does not depend on; the reference's own command line fixes the method to perceptual."""
+    (PyWavelets) this build does not depend on; the reference's own command line fixes the method to perceptual.
+
+    device=None is the host loop.  With a device the files that open in mode RGB are decoded here and hashed by `phash_device`,
+    HASH_CHUNK_BYTES of pixels at a time; a file of any other mode takes the host path.  The hashes are the same either way."""
     if method != "p":
         raise ValueError("hash method %r: only 'p' (perceptual) is built; 'w' needs the wavelet package PyWavelets (pywt)" % (method,))
     from PIL import Image
+    if device is not None:
+        paths = list(paths)
+        words = np.zeros((len(paths), 1), np.uint64)
+        held, where, held_bytes = [], [], 0
+
+        def flush():
+            if held:
+                words[where] = phash_device(held, device)
+            del held[:], where[:]
+        for k, p in enumerate(paths):
+            with Image.open(p) as im:
+                if im.mode == "RGB":
+                    held.append(np.asarray(im))
+                    where.append(k)
+                    held_bytes += held[-1].nbytes
+                else:
+                    words[k] = _bits_to_words(phash(im.resize((512, 256))).reshape(1, -1))
+            if held_bytes >= HASH_CHUNK_BYTES:
+                flush()
+                held_bytes = 0
+        flush()
+        return words
     bits = []
     for p in paths:
         with Image.open(p) as im:
