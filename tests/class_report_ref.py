@@ -6,21 +6,10 @@ has the signature and the result of `class_report.report_np`, so it can stand in
 `engine=`."""
 import numpy as np
 
+import tree_ref
+
 EPS = 1e-7
-
-
-def tree(terms):
-    """Root of the perfect binary tree over `terms`, zero-padded to a power of two; 0.0 for no terms."""
-    b = np.asarray(terms, np.float64).ravel()
-    if len(b) == 0:
-        return np.float64(0.0)
-    size = 1
-    while size < len(b):
-        size *= 2
-    b = np.concatenate([b, np.zeros(size - len(b))])
-    while len(b) > 1:
-        b = b[0::2] + b[1::2]
-    return b[0]
+tree = tree_ref.tree
 
 
 def uniform_edges(n_bins=10):

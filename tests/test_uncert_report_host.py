@@ -97,6 +97,13 @@ def test_tree_does_not_depend_on_the_run_length():
     assert R.tree([]) == 0.0 and R.tree([5.0]) == 5.0
 
 
+def test_the_mirrors_share_one_statement_of_the_tree():
+    import class_report_ref
+    import thr_report_ref
+    import tree_ref
+    assert R.tree is tree_ref.tree and class_report_ref.tree is tree_ref.tree and thr_report_ref.tree_sum is tree_ref.tree
+
+
 def test_per_class_segments():
     gt, pred, sig, gc, pc = inputs("n300")
     ids = [float(c) for c in GOLD["class_ids"]]

@@ -6,18 +6,9 @@ device (`report=`)."""
 import numpy as np
 
 import thr_ref
+import tree_ref
 
-
-def tree_sum(terms):
-    """The root of `b = b[0::2] + b[1::2]` over the terms, zero-padded to a power of two; 0.0 for no terms."""
-    b = np.asarray(terms, np.float64)
-    P = 1
-    while P < b.size:
-        P *= 2
-    b = np.concatenate([b, np.zeros(P - b.size)])
-    while b.size > 1:
-        b = b[0::2] + b[1::2]
-    return b[0]
+tree_sum = tree_ref.tree
 
 
 def roc_metrics(u, correct, fix_cd, budget):

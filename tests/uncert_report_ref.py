@@ -5,27 +5,16 @@ every float64 sum is the root of the zero-padded pairwise tree over the segment'
 can stand in for the device wherever that module takes `engine=`."""
 import numpy as np
 
+import tree_ref
+
 HALF_LOG_2PI = 0.9189385332046727
+tree = tree_ref.tree
 
 
 def levels_z(levels=100):
     from scipy import stats
     p_m = np.linspace(0, 1, int(levels))
     return p_m, stats.norm.ppf((1 - p_m) / 2)
-
-
-def tree(terms):
-    """Root of the perfect binary tree over `terms`, zero-padded to a power of two; 0.0 for no terms."""
-    b = np.asarray(terms, np.float64).ravel()
-    if len(b) == 0:
-        return np.float64(0.0)
-    size = 1
-    while size < len(b):
-        size *= 2
-    b = np.concatenate([b, np.zeros(size - len(b))])
-    while len(b) > 1:
-        b = b[0::2] + b[1::2]
-    return b[0]
 
 
 def row_terms(t):

@@ -37,6 +37,7 @@
 // that no index is ever taken from a comparison that failed.
 #include "box_iou.h"
 #include "uda_internal.h"
+#include "wave_fold.h"
 
 namespace uda {
 
@@ -45,15 +46,6 @@ namespace uda {
 __device__ __forceinline__ double audit_iou(const double* a, const double* b) {
   const double v = glc_iou(a, b);
   return v == v ? v : -1.0;
-}
-
-// the wave's lexicographic best of (key, lower index); every lane ends with it
-__device__ __forceinline__ void audit_wave_best(double& key, int& best) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ok = __shfl_xor(key, o);
-    const int ob = __shfl_xor(best, o);
-    if (ok > key || (ok == key && ob < best)) { key = ok; best = ob; }
-  }
 }
 
 // dynamic LDS of a block, for the call's largest image: boxes [Dm][4] f64 | win [Dm] f64 | mp [Dm] | pos [Dm] | mg [Dm] |
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(256) void pseudo_audit_kernel(AuditArgs a) {
         const double v = audit_iou(gt, box + d * 4);
         if (v > key) { key = v; best = d; }                 // (d ascends: an equal key never replaces a lower index)
       }
-      audit_wave_best(key, best);
+      wave_best_max(key, best);
       if (lane == 0) {
         a.gt_max_iou[g0 + g] = key;
         a.gt_best_det[g0 + g] = best;
@@ -138,7 +130,7 @@ __global__ __launch_bounds__(256) void pseudo_audit_kernel(AuditArgs a) {
         const double v = audit_iou(gtb + g * 4, bd);
         if (v > key) { key = v; best = g; }
       }
-      audit_wave_best(key, best);
+      wave_best_max(key, best);
       if (lane == 0) { a.det_max_iou[d0 + d] = key; a.det_best_gt[d0 + d] = best; }
     }
 
@@ -153,7 +145,7 @@ __global__ __launch_bounds__(256) void pseudo_audit_kernel(AuditArgs a) {
         const double v = audit_iou(gtb + r * 4, bi);
         if (v > key) { key = v; best = r; }
       }
-      audit_wave_best(key, best);                           // P <= G: an untaken row exists, so best < G
+      wave_best_max(key, best);                           // P <= G: an untaken row exists, so best < G
       if ((best & 63) == lane) order[best] = p;             // the lane that owns the row
       if (lane == 0) { mg[p] = best; win[p] = key; }
     }

@@ -13,12 +13,12 @@
 // NaN lands in id n_edges.
 // Counts.  `id == k` is balloted over the wave, the popcounts of the ballot and of `id == k && ytrue` go to the wave's LDS slot and
 // the block's total reaches global memory by one integer atomic a (target, bin): every count is exact however rows are dealt out.
-// Sums.  The term of a row outside the bin is +0.0; the wave folds its 64 terms with the butterfly v += shfl_xor(v, 1, 2, .. 32) -
-// adjacent lanes first, addition commutes, so every lane holds the root of the perfect tree - the block folds its four wave roots
-// (w0 + w1) + (w2 + w3), and the tree kernel folds the runs' roots, zero-padded to a power of two: `b = b[0::2] + b[1::2]` over the
-// zero-padded terms.  A bin no row of the wave falls into is skipped (its root is the +0.0 the tree of zeros gives).  A segment
-// of ONE run needs no second fold: its block writes the outputs itself.
+// Sums.  The zero-padded pairwise tree of DESIGN §21, in the statements of wave_fold.h: the wave folds its 64 terms
+// (wave_tree_sum), the block its four wave roots (fold4) and the tree kernel the runs' roots (fold_slots_in_place).  The term of
+// a row outside the bin is +0.0.  A bin no row of the wave falls into is skipped (its root is the +0.0 the tree of zeros gives).
+// A segment of ONE run needs no second fold: its block writes the outputs itself.
 #include "uda_internal.h"
+#include "wave_fold.h"
 
 namespace uda {
 
@@ -26,11 +26,6 @@ namespace uda {
 #define CLASSREP_SLOTS (CLASSREP_MAX_E + 1)
 static_assert(CLASSREP_WAVES == 4, "the block folds four wave roots: (w0 + w1) + (w2 + w3)");
 static_assert(CLASSREP_SLOTS + 1 <= CLASSREP_ROWS, "one finishing thread a bin slot and one for the Brier sum");
-
-__device__ __forceinline__ double classrep_wave_tree(double v) {
-  for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o);
-  return v;
-}
 
 // where sum r of (segment, table) goes: r < (C + 1) * (E + 1) a bin sum, then the C Brier sums, then the NLL sum
 __device__ __forceinline__ double* classrep_out(const ClassRepArgs& a, int seg, int m, int r) {
@@ -102,30 +97,27 @@ __global__ __launch_bounds__(CLASSREP_ROWS) void class_report_kernel(ClassRepArg
       double root = 0.0;
       if (mask != 0ull) {                                              // (uniform over the wave)
         c = (unsigned int)__popcll(mask);
-        h = (unsigned int)__popcll(__ballot(in && y));
-        root = classrep_wave_tree(in ? x : 0.0);
+        h = wave_count(in && y);
+        root = wave_tree_sum(in ? x : 0.0);
       }
       if (lane == 0) { sum_s[buf][k][wave] = root; cnt_s[buf][k][wave] = c; hit_s[buf][k][wave] = h; }
     }
     if (t < C) {
       const double d = x - (y ? 1.0 : 0.0);
-      const double root = classrep_wave_tree(valid ? d * d : 0.0);
+      const double root = wave_tree_sum(valid ? d * d : 0.0);
       if (lane == 0) sum_s[buf][CLASSREP_SLOTS][wave] = root;
     }
     __syncthreads();
     // ---- the block's share of target t.  The next target fills the other half of the buffers and the one after it comes behind
     // the next barrier, which these threads reach only after they have read.
     if (tid <= ne) {
-      const double root = (sum_s[buf][tid][0] + sum_s[buf][tid][1]) + (sum_s[buf][tid][2] + sum_s[buf][tid][3]);
-      *place(t * (E + 1) + tid) = root;
-      const unsigned int c = (cnt_s[buf][tid][0] + cnt_s[buf][tid][1]) + (cnt_s[buf][tid][2] + cnt_s[buf][tid][3]);
-      const unsigned int h = (hit_s[buf][tid][0] + hit_s[buf][tid][1]) + (hit_s[buf][tid][2] + hit_s[buf][tid][3]);
+      *place(t * (E + 1) + tid) = fold4(sum_s[buf][tid]);
+      const unsigned int c = fold4(cnt_s[buf][tid]), h = fold4(hit_s[buf][tid]);
       const size_t o = (sm * (C + 1) + t) * (size_t)(E + 1) + tid;
       if (c) atomicAdd(a.bin_count + o, (unsigned long long)c);
       if (h) atomicAdd(a.bin_hits + o, (unsigned long long)h);
     } else if (tid == CLASSREP_ROWS - 1 && t < C) {
-      const double* b = sum_s[buf][CLASSREP_SLOTS];
-      *place((C + 1) * (E + 1) + t) = (b[0] + b[1]) + (b[2] + b[3]);
+      *place((C + 1) * (E + 1) + t) = fold4(sum_s[buf][CLASSREP_SLOTS]);
     }
   }
 
@@ -135,20 +127,19 @@ __global__ __launch_bounds__(CLASSREP_ROWS) void class_report_kernel(ClassRepArg
   const bool clipped = valid && !out && (q < 1e-7 || q > 1.0 - 1e-7);
   const double qc = q < 1e-7 ? 1e-7 : (q > 1.0 - 1e-7 ? 1.0 - 1e-7 : q);
   const double term = (valid && !out) ? -log(qc) : 0.0;
-  const double root = classrep_wave_tree(term);
-  const unsigned int w_clip = (unsigned int)__popcll(__ballot(clipped)), w_out = (unsigned int)__popcll(__ballot(valid && out));
+  const double root = wave_tree_sum(term);
+  const unsigned int w_clip = wave_count(clipped), w_out = wave_count(valid && out);
   if (lane == 0) { nll_s[wave] = root; tab_s[0][wave] = w_clip; tab_s[1][wave] = w_out; }
   __syncthreads();
-  if (tid == 0) *place((C + 1) * (E + 1) + C) = (nll_s[0] + nll_s[1]) + (nll_s[2] + nll_s[3]);
+  if (tid == 0) *place((C + 1) * (E + 1) + C) = fold4(nll_s);
   if (tid < 2) {
-    const unsigned int c = (tab_s[tid][0] + tab_s[tid][1]) + (tab_s[tid][2] + tab_s[tid][3]);
+    const unsigned int c = fold4(tab_s[tid]);
     if (c) atomicAdd(a.tab_counts + sm * 2 + tid, (unsigned long long)c);
   }
 }
 
-// folds the slots of one (segment, sum) in place, a wave a sum: at stride s slot j (a multiple of 2 s) takes slot j + s, so no slot
-// is read by one lane and written by another between two barriers.  P is a power of two, at least 2, and the same for the four
-// sums of a block (they belong to one segment): so are the barriers.
+// folds the slots of one (segment, sum) in place, a wave a sum.  P is a power of two, at least 2, and the same for the four sums
+// of a block (they belong to one segment): so are the barriers, which a wave without a sum takes too.
 __global__ __launch_bounds__(256) void class_report_tree_kernel(ClassRepArgs a) {
   const int seg = a.tree_segs[blockIdx.y];
   const int S = (a.C + 1) * (a.E + 1) + a.C + 1;
@@ -156,11 +147,7 @@ __global__ __launch_bounds__(256) void class_report_tree_kernel(ClassRepArgs a) 
   const bool mine = sum_id < a.M * S;
   const int P = (int)(a.pbase[seg + 1] - a.pbase[seg]);
   double* buf = a.partials + (size_t)(mine ? sum_id : 0) * (size_t)a.slots + a.pbase[seg];
-  for (int s = 1; s < P; s <<= 1) {
-    if (mine)
-      for (int j = lane * 2 * s; j < P; j += 64 * 2 * s) buf[j] = buf[j] + buf[j + s];
-    __syncthreads();
-  }
+  fold_slots_in_place(buf, P, lane, 64, mine);
   if (mine && lane == 0) *classrep_out(a, seg, sum_id / S, sum_id % S) = buf[0];
 }
 

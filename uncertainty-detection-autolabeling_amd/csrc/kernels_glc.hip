@@ -29,6 +29,7 @@
 // detection's maximum at 0, and the missing-label rule is applied to that.
 #include "box_iou.h"
 #include "uda_internal.h"
+#include "wave_fold.h"
 
 namespace uda {
 
@@ -100,11 +101,7 @@ __global__ __launch_bounds__(256) void label_check_kernel(LabelCheckArgs<T> a) {
       if (v > key) { key = v; best = e; }                   // (e ascends: an equal key never replaces a lower index)
       if (v > 0.0) atomicMax(det_max + rank[e], (unsigned long long)__double_as_longlong(v));
     }
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ok = __shfl_xor(key, o);
-      const int ob = __shfl_xor(best, o);
-      if (ok > key || (ok == key && ob < best)) { key = ok; best = ob; }
-    }
+    wave_best_max(key, best);
     if (lane == 0) {
       if (best >= K) { best = 0; key = glc_iou(gt, box); }  // every IoU was NaN (non-finite input): nothing is indexed with the sentinel
       const int r = rank[best];

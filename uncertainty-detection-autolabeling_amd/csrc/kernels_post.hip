@@ -26,6 +26,7 @@
 #include <hip/hip_fp16.h>
 
 #include "post_common.h"
+#include "wave_fold.h"
 
 namespace uda {
 
@@ -258,11 +259,7 @@ __global__ __launch_bounds__(256) void assign_gt_kernel(AssignArgs a) {
         const double v = iou_np(gt, det + k * 4);
         if (v > key) { key = v; best = k; }               // (k ascends: an equal key never replaces a lower rank)
       }
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ok = __shfl_xor(key, o);
-        const int ob = __shfl_xor(best, o);
-        if (ok > key || (ok == key && ob < best)) { key = ok; best = ob; }
-      }
+      wave_best_max(key, best);
     } else if (a.method == ASSIGN_MSE) {
       float key = __builtin_inff();
       for (int k = lane; k < M; k += 64) {

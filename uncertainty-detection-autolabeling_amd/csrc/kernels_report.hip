@@ -13,24 +13,19 @@
 // only - every count is exact however rows are dealt out).  The level test is `fabs(pred - gt) <= fabs(sigma * z[i])`, level by
 // level: sigma = 0 with z = -inf gives NaN and false, an infinite sigma with z = 0 likewise - nothing is inferred from the order
 // of the levels.
-// Sums.  A row's term is (t0 + t1) + (t2 + t3); the wave folds its 64 rows with the butterfly v += shfl_xor(v, 1, 2, .. 32) -
-// addition commutes, so every lane holds the root of the perfect tree - the block folds its waves' roots the same way, and the
-// tree kernel folds the runs' roots, zero-padded to a power of two: `b = b[0::2] + b[1::2]` over the zero-padded terms, whatever
-// REPORT_ROWS is.  A lane past the segment's end contributes +0.0, the padding.
+// Sums.  The zero-padded pairwise tree of DESIGN §21, in the statements of wave_fold.h: a row's term is fold4 of its four
+// coordinates' terms, the wave folds its 64 rows (wave_tree_sum), the block its four wave roots (fold4), and the tree kernel the
+// runs' roots in their power of two of slots (fold_slots_in_place), whatever REPORT_ROWS is.  A lane past the segment's end
+// contributes +0.0, the padding.
 #include "box_iou.h"
 #include "uda_internal.h"
+#include "wave_fold.h"
 
 namespace uda {
 
 #define REPORT_WAVES (REPORT_ROWS / 64)
 #define REPORT_HALF_LOG_2PI 0.9189385332046727
 static_assert(REPORT_WAVES == 4, "the block folds four wave roots: (w0 + w1) + (w2 + w3)");
-
-__device__ __forceinline__ double report_wave_tree(double v) {
-  for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ unsigned int report_wave_count(bool p) { return (unsigned int)__popcll(__ballot(p)); }
 
 __global__ __launch_bounds__(REPORT_ROWS) void uncert_report_kernel(ReportArgs a) {
   __shared__ double z_s[REPORT_MAX_L];
@@ -71,15 +66,15 @@ __global__ __launch_bounds__(REPORT_ROWS) void uncert_report_kernel(ReportArgs a
     t_nll[c] = bad ? 0.0 : (y * y / 2.0 + log(s)) + REPORT_HALF_LOG_2PI;
   }
   double v[REPORT_COL_SUMS + REPORT_SEG_SUMS];
-  v[0] = valid ? (t_s2[0] + t_s2[1]) + (t_s2[2] + t_s2[3]) : 0.0;
-  v[1] = valid ? (t_ue[0] + t_ue[1]) + (t_ue[2] + t_ue[3]) : 0.0;
-  v[2] = valid ? (t_nll[0] + t_nll[1]) + (t_nll[2] + t_nll[3]) : 0.0;
-  const unsigned int w_cov = report_wave_count(covered);
+  v[0] = valid ? fold4(t_s2) : 0.0;
+  v[1] = valid ? fold4(t_ue) : 0.0;
+  v[2] = valid ? fold4(t_nll) : 0.0;
+  const unsigned int w_cov = wave_count(covered);
   // (4 elements a row: the element counts go through the wave as four ballots of one bit each)
   unsigned int w_res = 0, w_deg = 0;
   for (int c = 0; c < 4; ++c) {
-    w_res += report_wave_count(valid && res[c] != 0.0);
-    w_deg += report_wave_count(valid && (sg[c] == 0.0 || !(sg[c] - sg[c] == 0.0)));
+    w_res += wave_count(valid && res[c] != 0.0);
+    w_deg += wave_count(valid && (sg[c] == 0.0 || !(sg[c] - sg[c] == 0.0)));
   }
 
   // ---- per segment: column 0's blocks only (k is uniform over the block)
@@ -91,16 +86,16 @@ __global__ __launch_bounds__(REPORT_ROWS) void uncert_report_kernel(ReportArgs a
     for (int c = 0; c < 4; ++c) {
       const double d = pred[c] - gt[c];
       t_sq[c] = gt[c] != 0.0 ? d * d : 0.0;
-      w_gnz += report_wave_count(valid && gt[c] != 0.0);
+      w_gnz += wave_count(valid && gt[c] != 0.0);
     }
     v[3] = valid ? iou : 0.0;
-    v[4] = valid ? (t_sq[0] + t_sq[1]) + (t_sq[2] + t_sq[3]) : 0.0;
-    w_iou0 = report_wave_count(valid && iou == 0.0);
-    w_mis = report_wave_count(valid && a.gt_class[row] != a.cls[row]);
+    v[4] = valid ? fold4(t_sq) : 0.0;
+    w_iou0 = wave_count(valid && iou == 0.0);
+    w_mis = wave_count(valid && a.gt_class[row] != a.cls[row]);
     n_sums += REPORT_SEG_SUMS;
   }
   for (int j = 0; j < n_sums; ++j) {
-    const double root = report_wave_tree(v[j]);
+    const double root = wave_tree_sum(v[j]);
     if (lane == 0) sum_s[j][wave] = root;
   }
   if (lane == 0) {
@@ -114,11 +109,11 @@ __global__ __launch_bounds__(REPORT_ROWS) void uncert_report_kernel(ReportArgs a
     unsigned int lo = 0, hi = 0;                            // the counts of levels `lane` and `64 + lane`
     const int L0 = L < 64 ? L : 64;
     for (int i = 0; i < L0; ++i) {
-      const unsigned int pc = report_wave_count(valid && r <= fabs(s * z_s[i]));
+      const unsigned int pc = wave_count(valid && r <= fabs(s * z_s[i]));
       lo += lane == i ? pc : 0u;
     }
     for (int i = 64; i < L; ++i) {
-      const unsigned int pc = report_wave_count(valid && r <= fabs(s * z_s[i]));
+      const unsigned int pc = wave_count(valid && r <= fabs(s * z_s[i]));
       hi += lane == i - 64 ? pc : 0u;
     }
     if (lane < L && lo) atomicAdd(&ece_s[c * L + lane], lo);
@@ -128,7 +123,7 @@ __global__ __launch_bounds__(REPORT_ROWS) void uncert_report_kernel(ReportArgs a
 
   // ---- the block's share: run roots to the partials, counts to global memory
   if (tid < n_sums) {
-    const double root = (sum_s[tid][0] + sum_s[tid][1]) + (sum_s[tid][2] + sum_s[tid][3]);
+    const double root = fold4(sum_s[tid]);
     const int sum_id = tid < REPORT_COL_SUMS ? REPORT_SEG_SUMS + REPORT_COL_SUMS * k + tid : tid - REPORT_COL_SUMS;
     a.partials[(size_t)sum_id * (size_t)a.slots + it.slot] = root;
   }
@@ -142,16 +137,13 @@ __global__ __launch_bounds__(REPORT_ROWS) void uncert_report_kernel(ReportArgs a
     if (ece_s[e]) atomicAdd(ece + e, (unsigned long long)ece_s[e]);
 }
 
-// folds the slots of one (segment, sum) in place: at stride s slot j (a multiple of 2 s) takes slot j + s, so no slot is read
-// by one thread and written by another between two barriers.  P is a power of two (0: the segment is empty, its sums stay 0).
+// folds the slots of one (segment, sum) in place, the whole block on one sum.  P is a power of two (0: the segment is empty,
+// its sums stay 0) and uniform over the block: so are the barriers.
 __global__ __launch_bounds__(256) void uncert_report_tree_kernel(ReportArgs a) {
   const int b = blockIdx.x, sum_id = blockIdx.y;
   const int P = (int)(a.pbase[b + 1] - a.pbase[b]);
   double* buf = a.partials + (size_t)sum_id * (size_t)a.slots + a.pbase[b];
-  for (int s = 1; s < P; s <<= 1) {                         // (P is uniform over the block: so are the barriers)
-    for (int j = (int)threadIdx.x * 2 * s; j < P; j += 256 * 2 * s) buf[j] = buf[j] + buf[j + s];
-    __syncthreads();
-  }
+  fold_slots_in_place(buf, P, (int)threadIdx.x, 256, true);
   if (threadIdx.x == 0 && P > 0) {
     if (sum_id < REPORT_SEG_SUMS) a.seg_sums[(size_t)b * REPORT_SEG_SUMS + sum_id] = buf[0];
     else a.col_sums[(size_t)b * a.K * REPORT_COL_SUMS + (sum_id - REPORT_SEG_SUMS)] = buf[0];

@@ -17,17 +17,18 @@
 // because a chunk without survivors has only that one barrier.
 //
 // Tallies.  Counts are ballots and popcounts added to wave-uniform registers; the waves meet in LDS once.  The IoU sums are the
-// zero-padded pairwise tree of kernels_thrrep.hip over all N rows from row 0: butterfly over the wave, (w0 + w1) + (w2 + w3) over
-// the block's run, binary counter over the runs; a row of the other side contributes +0.0 and -0.0 counts as 0.0.  The per-image
+// zero-padded pairwise tree of DESIGN §21 over all N rows from row 0, in the statements of wave_fold.h and in one block, as in
+// kernels_thrrep.hip; a row of the other side contributes +0.0 and -0.0 counts as 0.0.  The per-image
 // outputs use integer atomicAdd / atomicMin only, so they do not depend on the order of arrival either.
 #include "uda_internal.h"
+#include "wave_fold.h"
 
 namespace uda {
 
 static_assert(HEAT_CHUNK == 256 && HEAT_CHUNK % HEAT_TILE_W == 0 && (HEAT_TILE_H * HEAT_TILE_W) % HEAT_CHUNK == 0,
               "a thread owns HEAT_PX pixels of one column, HEAT_YSTEP rows apart");
 static_assert(THRPOST_ROWS == 256, "the block folds four wave roots: (w0 + w1) + (w2 + w3)");
-static_assert((UDA_THR_MAX_N + THRPOST_ROWS - 1) / THRPOST_ROWS <= (1 << (THRPOST_LEVELS - 1)), "levels of the run tree");
+static_assert((UDA_THR_MAX_N + THRPOST_ROWS - 1) / THRPOST_ROWS <= (1 << (RUN_TREE_LEVELS - 1)), "levels of the run tree");
 
 constexpr int HEAT_PX = HEAT_TILE_H * HEAT_TILE_W / HEAT_CHUNK;
 constexpr int HEAT_YSTEP = HEAT_CHUNK / HEAT_TILE_W;
@@ -120,28 +121,9 @@ void launch_heat_maps(const HeatArgs& a, int tiles, int M, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- tallies
-__device__ __forceinline__ double thrpost_wave_tree(double v) {
-  for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ long long thrpost_wave_count(bool p) { return (long long)__popcll(__ballot(p)); }
-// run root number `index` (from 0) joins the tree held in stack[level]
-__device__ __forceinline__ void thrpost_push(double* stack, int index, double r) {
-  int l = 0;
-  for (int c = index; c & 1; c >>= 1, ++l) r = stack[l] + r;
-  stack[l] = r;
-}
-// after `runs` >= 1 pushes: zero roots up to a power of two, then the root
-__device__ __forceinline__ double thrpost_root(double* stack, int runs) {
-  int P = 1, top = 0;
-  while (P < runs) { P <<= 1; ++top; }
-  for (int z = runs; z < P; ++z) thrpost_push(stack, z, 0.0);
-  return stack[top];
-}
-
 __global__ __launch_bounds__(THRPOST_ROWS) void thr_post_kernel(ThrPostArgs a) {
   __shared__ double root_s[2][THRPOST_UNROLL][THRPOST_ROWS / 64];
-  __shared__ double stack_s[2][THRPOST_LEVELS];
+  __shared__ double stack_s[2][RUN_TREE_LEVELS];
   __shared__ long long cnt_s[THRPOST_ROWS / 64][8];
   const int k = blockIdx.x, N = a.N;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -165,15 +147,15 @@ __global__ __launch_bounds__(THRPOST_ROWS) void thr_post_kernel(ThrPostArgs a) {
       if (iou[r] == 0.0) iou[r] = 0.0;
       const bool valid = tp[r] != 0, hit = tp[r] == 3, correct = hit && iou[r] >= iou_thr;
       const bool side0 = valid && u[r] >= thr, side1 = valid && u[r] < thr;
-      cnt[0] += thrpost_wave_count(side0);
-      cnt[1] += thrpost_wave_count(side0 && hit);
-      cnt[2] += thrpost_wave_count(side0 && correct);
-      cnt[3] += thrpost_wave_count(side0 && !correct);
-      cnt[4] += thrpost_wave_count(side1);
-      cnt[5] += thrpost_wave_count(side1 && hit);
-      cnt[6] += thrpost_wave_count(side1 && correct);
-      cnt[7] += thrpost_wave_count(side1 && !correct);
-      const double r0 = thrpost_wave_tree(side0 ? iou[r] : 0.0), r1 = thrpost_wave_tree(side1 ? iou[r] : 0.0);
+      cnt[0] += wave_count(side0);
+      cnt[1] += wave_count(side0 && hit);
+      cnt[2] += wave_count(side0 && correct);
+      cnt[3] += wave_count(side0 && !correct);
+      cnt[4] += wave_count(side1);
+      cnt[5] += wave_count(side1 && hit);
+      cnt[6] += wave_count(side1 && correct);
+      cnt[7] += wave_count(side1 && !correct);
+      const double r0 = wave_tree_sum(side0 ? iou[r] : 0.0), r1 = wave_tree_sum(side1 ? iou[r] : 0.0);
       if (lane == 0) { root_s[0][r][wave] = r0; root_s[1][r][wave] = r1; }
       if (images && valid) {
         const int i = (run0 + r) * THRPOST_ROWS + tid, img = a.image[i];
@@ -187,17 +169,14 @@ __global__ __launch_bounds__(THRPOST_ROWS) void thr_post_kernel(ThrPostArgs a) {
     }
     __syncthreads();
     if (tid < 2)
-      for (int r = 0; r < THRPOST_UNROLL && run0 + r < runs; ++r) {
-        const double* w = root_s[tid][r];
-        thrpost_push(stack_s[tid], run0 + r, (w[0] + w[1]) + (w[2] + w[3]));
-      }
+      for (int r = 0; r < THRPOST_UNROLL && run0 + r < runs; ++r) run_tree_push(stack_s[tid], run0 + r, fold4(root_s[tid][r]));
     __syncthreads();
   }
   if (lane == 0)
     for (int j = 0; j < 8; ++j) cnt_s[wave][j] = cnt[j];
   __syncthreads();
-  if (tid < 8) a.counts[8 * k + tid] = (cnt_s[0][tid] + cnt_s[1][tid]) + (cnt_s[2][tid] + cnt_s[3][tid]);
-  if (tid < 2) a.iou_sum[2 * k + tid] = thrpost_root(stack_s[tid], runs);
+  if (tid < 8) a.counts[8 * k + tid] = fold4(&cnt_s[0][tid], 8);   // (the waves' counts of one kind lie 8 apart)
+  if (tid < 2) a.iou_sum[2 * k + tid] = run_tree_root(stack_s[tid], runs);
 }
 
 void launch_thr_post(const ThrPostArgs& a, hipStream_t s) {

@@ -11,37 +11,16 @@
 // Counts.  A predicate is balloted over the wave and the popcount added to a wave-uniform register; the four waves meet in LDS
 // once.  No atomics at all: a block owns its outputs.
 // Sums.  -0.0 counts as 0.0 (as in the curve), a row outside the subset or past the segment's end contributes +0.0.  A run of
-// THRREP_ROWS rows, counted from the segment's first row, is folded by the butterfly v += shfl_xor(v, 1, 2, .. 32) - addition
-// commutes, so every lane holds the root of the perfect tree - and its four wave roots as (w0 + w1) + (w2 + w3).  The run roots
-// are folded by a binary counter: root r waits at level l until the next root of that level arrives, the earlier one on the left;
-// zero roots are pushed until the number of runs is a power of two.  That is `b = b[0::2] + b[1::2]` over the zero-padded terms
-// until one value is left; no term is -0.0, so it does not matter how far the padding goes.
+// THRREP_ROWS rows, counted from the segment's first row, is folded over the wave (wave_tree_sum) and over its four wave roots
+// (fold4); the run roots are folded by the binary counter (run_tree_push, run_tree_root), all in one block.  That is the
+// zero-padded pairwise tree of DESIGN §21 as wave_fold.h states it; no term is -0.0, so it does not matter how far the padding goes.
 #include "uda_internal.h"
+#include "wave_fold.h"
 
 namespace uda {
 
 static_assert(THRREP_ROWS == 256, "the block folds four wave roots: (w0 + w1) + (w2 + w3)");
-static_assert((UDA_THR_MAX_N + THRREP_ROWS - 1) / THRREP_ROWS <= (1 << (THRREP_LEVELS - 1)), "levels of the run tree");
-
-__device__ __forceinline__ double thrrep_wave_tree(double v) {
-  for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ unsigned long long thrrep_wave_count(bool p) { return (unsigned long long)__popcll(__ballot(p)); }
-
-// run root number `index` (from 0) joins the tree held in stack[level]
-__device__ __forceinline__ void thrrep_push(double* stack, int index, double r) {
-  int l = 0;
-  for (int c = index; c & 1; c >>= 1, ++l) r = stack[l] + r;
-  stack[l] = r;
-}
-// after `runs` >= 1 pushes: zero roots up to a power of two, then the root
-__device__ __forceinline__ double thrrep_root(double* stack, int runs) {
-  int P = 1, top = 0;
-  while (P < runs) { P <<= 1; ++top; }
-  for (int z = runs; z < P; ++z) thrrep_push(stack, z, 0.0);
-  return stack[top];
-}
+static_assert((UDA_THR_MAX_N + THRREP_ROWS - 1) / THRREP_ROWS <= (1 << (RUN_TREE_LEVELS - 1)), "levels of the run tree");
 
 __global__ __launch_bounds__(256) void thr_report_fill_kernel(double* roc, long long n) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -54,7 +33,7 @@ __global__ __launch_bounds__(256) void thr_report_fill_kernel(double* roc, long 
 // together.  SECOND: the terms are (u - mean)^2 about the subset's mean; else u itself, and the four counts are taken
 template <bool SECOND>
 __device__ __forceinline__ void thrrep_pass(const double* u, const uint32_t* m, int n, int k, double thr, double mean0, double mean1,
-                                            double (*root_s)[THRREP_UNROLL][THRREP_ROWS / 64], double (*stack_s)[THRREP_LEVELS],
+                                            double (*root_s)[THRREP_UNROLL][THRREP_ROWS / 64], double (*stack_s)[RUN_TREE_LEVELS],
                                             unsigned long long* counts) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int runs = (n + THRREP_ROWS - 1) / THRREP_ROWS;
@@ -79,27 +58,24 @@ __device__ __forceinline__ void thrrep_pass(const double* u, const uint32_t* m, 
         t1 = __dmul_rn(d1, d1);
       } else {
         t0 = t1 = v[r];
-        counts[0] += thrrep_wave_count(cor);
-        counts[1] += thrrep_wave_count(wrong && v[r] >= thr);
-        counts[2] += thrrep_wave_count(cor && v[r] >= thr);
-        counts[3] += thrrep_wave_count(wrong && v[r] < thr);
+        counts[0] += wave_count(cor);
+        counts[1] += wave_count(wrong && v[r] >= thr);
+        counts[2] += wave_count(cor && v[r] >= thr);
+        counts[3] += wave_count(wrong && v[r] < thr);
       }
-      const double r0 = thrrep_wave_tree(cor ? t0 : 0.0), r1 = thrrep_wave_tree(wrong ? t1 : 0.0);
+      const double r0 = wave_tree_sum(cor ? t0 : 0.0), r1 = wave_tree_sum(wrong ? t1 : 0.0);
       if (lane == 0) { root_s[0][r][wave] = r0; root_s[1][r][wave] = r1; }
     }
     __syncthreads();
     if (tid < 2)
-      for (int r = 0; r < THRREP_UNROLL && run0 + r < runs; ++r) {
-        const double* w = root_s[tid][r];
-        thrrep_push(stack_s[tid], run0 + r, (w[0] + w[1]) + (w[2] + w[3]));
-      }
+      for (int r = 0; r < THRREP_UNROLL && run0 + r < runs; ++r) run_tree_push(stack_s[tid], run0 + r, fold4(root_s[tid][r]));
     __syncthreads();
   }
 }
 
 __global__ __launch_bounds__(THRREP_ROWS) void thr_report_kernel(ThrRepArgs a) {
   __shared__ double root_s[2][THRREP_UNROLL][THRREP_ROWS / 64];
-  __shared__ double stack_s[2][THRREP_LEVELS];
+  __shared__ double stack_s[2][RUN_TREE_LEVELS];
   __shared__ double mean_s[2];
   __shared__ unsigned long long cnt_s[THRREP_ROWS / 64][4];
   const int k = blockIdx.x, s = blockIdx.y, b = blockIdx.z;
@@ -118,15 +94,15 @@ __global__ __launch_bounds__(THRREP_ROWS) void thr_report_kernel(ThrRepArgs a) {
   if (lane == 0)
     for (int j = 0; j < 4; ++j) cnt_s[wave][j] = c[j];
   __syncthreads();
-  const unsigned long long n_cor = (cnt_s[0][0] + cnt_s[1][0]) + (cnt_s[2][0] + cnt_s[3][0]);
+  const unsigned long long n_cor = fold4(&cnt_s[0][0], 4);  // (the waves' counts of one kind lie 4 apart)
   const unsigned long long n_sub = tid == 0 ? n_cor : (unsigned long long)n - n_cor;      // read by threads 0 and 1
   if (tid < 2) {
-    const double sum = n_sub ? thrrep_root(stack_s[tid], runs) : 0.0;
+    const double sum = n_sub ? run_tree_root(stack_s[tid], runs) : 0.0;
     mean_s[tid] = n_sub ? sum / (double)n_sub : 0.0;
     a.moments[slot * 4 + 2 * tid] = sum;
   } else if (tid < 5) {
     const int j = tid - 1;
-    a.removed[slot * 3 + (j - 1)] = (long long)((cnt_s[0][j] + cnt_s[1][j]) + (cnt_s[2][j] + cnt_s[3][j]));
+    a.removed[slot * 3 + (j - 1)] = (long long)fold4(&cnt_s[0][j], 4);
   } else if (tid < 7 && s == 0) {
     a.n_label[((size_t)b * a.K + k) * 2 + (tid - 5)] = (long long)(tid == 5 ? n_cor : (unsigned long long)n - n_cor);
   }
@@ -134,7 +110,7 @@ __global__ __launch_bounds__(THRREP_ROWS) void thr_report_kernel(ThrRepArgs a) {
 
   // ---- pass 2: the sums of (u - mean)^2, each subset about its own mean
   thrrep_pass<true>(u, m, n, k, thr, mean_s[0], mean_s[1], root_s, stack_s, c);
-  if (tid < 2) a.moments[slot * 4 + 2 * tid + 1] = n_sub ? thrrep_root(stack_s[tid], runs) : 0.0;
+  if (tid < 2) a.moments[slot * 4 + 2 * tid + 1] = n_sub ? run_tree_root(stack_s[tid], runs) : 0.0;
 }
 
 void launch_thr_report_fill(const ThrRepArgs& a, hipStream_t s) {

@@ -483,7 +483,7 @@ void launch_thr_objective(const ThrArgs& a, hipStream_t s);
 
 // thresholding report (kernels_thrrep.hip): what the reference computes next to the curve of one (segment, score column, IoU
 // threshold) - label counts, the moments behind calc_jsd, the removal counts at the threshold the curve gave.  One block each.
-enum { THRREP_MAX_S = UDA_THR_REPORT_MAX_S, THRREP_MAX_B = UDA_THR_REPORT_MAX_SEGS, THRREP_ROWS = 256, THRREP_LEVELS = 16, THRREP_UNROLL = 8 };
+enum { THRREP_MAX_S = UDA_THR_REPORT_MAX_S, THRREP_MAX_B = UDA_THR_REPORT_MAX_SEGS, THRREP_ROWS = 256, THRREP_UNROLL = 8 };
 struct ThrRepArgs {
   const double* scores;     // [S, N]
   const uint32_t* mask;     // [N] of launch_thr_mask
@@ -513,7 +513,7 @@ struct HeatArgs {
   int map_rect[HEAT_MAX_M], map_value[HEAT_MAX_M], map_sel[HEAT_MAX_M], map_mean[HEAT_MAX_M];
 };
 void launch_heat_maps(const HeatArgs& a, int tiles, int M, hipStream_t s);
-enum { THRPOST_ROWS = 256, THRPOST_LEVELS = 16, THRPOST_UNROLL = 4 };
+enum { THRPOST_ROWS = 256, THRPOST_UNROLL = 4 };
 struct ThrPostArgs {
   const double* u;          // [N]
   const double* ious;       // [N]

@@ -7,7 +7,8 @@
 // What the services share is stated once, ahead of them: the checks of the resident run (resident_ready, gt_covers_run), the
 // pinned staging of per-image ground truth (stage_ground_truth), the result packs with their first-reader fetch (fetch_result
 // over a ResultSlot of uda_ctx.h), the sources of a score descriptor (score_sources_missing, resident_score_sources,
-// upload_score_sources) and the tail of the entry points that own a DevScratch (scratch_done, fetch_pack).
+// upload_score_sources), the tail of the entry points that own a DevScratch (scratch_done, fetch_pack) and the slots of a
+// segment's tree fold (tree_slots).
 #include <stdio.h>
 #include <string.h>
 
@@ -95,6 +96,14 @@ static int fetch_pack(const char* who, DevScratch& s, const void* d_pack, size_t
   h.resize(bytes);
   s.download(h.data(), d_pack, bytes);
   return scratch_done(nullptr, who, s);
+}
+
+// ---- the slots a segment of `runs` run roots takes for the in-place tree fold (fold_slots_in_place of wave_fold.h): none
+// for no runs, else the power of two at or above `runs`; the slots past the runs stay zero, the tree's padding
+static int64_t tree_slots(int64_t runs) {
+  int64_t slots = runs ? 1 : 0;
+  while (slots < runs) slots <<= 1;
+  return slots;
 }
 
 // ---- result packs: one device buffer per service, so that ONE copy brings a result to the host.  Built over the device buffer
@@ -1322,10 +1331,8 @@ extern "C" int uda_uncert_report_np(int32_t device, int32_t B, int32_t K, int32_
   items.reserve(rows / REPORT_ROWS + (size_t)B);
   for (int b = 0; b < B; ++b) {
     const int64_t n = off[b + 1] - off[b], runs = (n + REPORT_ROWS - 1) / REPORT_ROWS;
-    int64_t slots = runs ? 1 : 0;
-    while (slots < runs) slots <<= 1;
     for (int64_t r = 0; r < runs; ++r) items.push_back(ReportItem{b, (int32_t)(r * REPORT_ROWS), (int32_t)(pbase[b] + r)});
-    pbase[b + 1] = pbase[b] + slots;
+    pbase[b + 1] = pbase[b] + tree_slots(runs);
   }
   const size_t n_sums = REPORT_SEG_SUMS + (size_t)REPORT_COL_SUMS * K;
   const size_t n_seg = (size_t)B * 4, n_col = (size_t)B * K * 3, n_ece = (size_t)B * K * 4 * L, n_ssum = (size_t)B * REPORT_SEG_SUMS,
@@ -1401,12 +1408,10 @@ extern "C" int uda_class_report_np(int32_t device, int32_t B, int32_t M, int32_t
   items.reserve(rows / CLASSREP_ROWS + (size_t)B);
   for (int b = 0; b < B; ++b) {
     const int64_t n = off[b + 1] - off[b], runs = (n + CLASSREP_ROWS - 1) / CLASSREP_ROWS;
-    int64_t slots = runs > 1 ? 2 : 0;
-    while (slots && slots < runs) slots <<= 1;
     for (int64_t r = 0; r < runs; ++r)
       items.push_back(ClassRepItem{b, (int32_t)(r * CLASSREP_ROWS), runs > 1 ? (int32_t)(pbase[b] + r) : -1});
     if (runs > 1) tree_segs.push_back(b);
-    pbase[b + 1] = pbase[b] + slots;
+    pbase[b + 1] = pbase[b] + (runs > 1 ? tree_slots(runs) : 0);
   }
   const size_t S = (size_t)(C + 1) * (E + 1) + C + 1;
   const size_t n_bin = (size_t)B * M * (C + 1) * (E + 1), n_tab = (size_t)B * M * 2, n_bri = (size_t)B * M * C, n_nll = (size_t)B * M;
