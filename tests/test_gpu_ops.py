@@ -75,6 +75,12 @@ CASES = [
     (1, 1, 1, 8, 4, ""),
     (2, 5, 300, 32, 16, "bn,se"),            # shared-input kernel: one tile load for the 5 sample rows of an image
     (1, 4, 131, 16, 24, "bn,res,mask"),
+    # BiFPN / head widths beyond D0 and D2 (test_gpu_widths.py runs them inside a network): the unfused lowering's 1x1 at C = F
+    (2, 1, 150, 20, 20, "bn,act"),           # a multiple of 4, not of 8: half a 16-byte k-quad pair in the last k-step
+    (1, 3, 96, 136, 135, "bias,mask"),       # first width past the fused kernels; 15 classes: one 160-wide column block, scalar epilogue
+    (2, 1, 384, 160, 810, "bias"),           # D3's width, 90 classes: wide-output column choice at 810 (128-wide: the least idle)
+    (1, 1, 96, 384, 384, "bn,act"),          # D6 / D7's width: the skinny kernel (24 k-steps), 192-wide columns when tiled
+    (2, 1, 130, 88, 88, "bn,res"),           # D1's width: K = 5.5 k-steps, three column tiles
 ]
 
 
